@@ -5,10 +5,12 @@ A step = neighbour list + forward energies + forces (adjoint sweep) + L1/L2 loss
 parameter gradients (tangent + dual-reverse sweeps) + gradient all-reduce (RCCL, N>1) + clip + AdamW,
 on a batch of synthetic drug-like conformers already resident in HBM.  fp32 throughout.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).
+Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).  A plain run only sets up, warms up, times the K steps and prints the
+line; every other measurement (instrumented kernel pass and roofline, CPU baseline and accuracy, sustained leg, sibling configuration,
+batch-32 leg, side legs) runs with --full.
 """
 import argparse
 import json
@@ -386,7 +388,7 @@ def bench_gemnet(args, rank, world, local_dev, dev):
                "reference_batch_size_8": None if b8 is None else {k: b8[k] for k in ("value", "unit", "ms_per_step", "atoms")},
                "reference_batch_size_8_prepared_eager_vs_graph_replay": _graph_replay("gemnet") if world == 1 and not args.no_roofline else None,
                "batch_64": big if bf is not None else None}
-        emit(out)
+        emit(out, not args.plain)
     finish(local_dev)
 
 
@@ -429,7 +431,7 @@ def bench_escn(args, rank, world, local_dev, dev, which="escn"):
                "parity": rec.get("parity"), "bf16_mode": bf,
                f"reference_batch_size_{ref_batch}": None if b8 is None else {k: b8[k] for k in ("value", "unit", "ms_per_step", "atoms")},
                f"reference_batch_size_{ref_batch}_prepared_eager_vs_graph_replay": _graph_replay(which) if world == 1 and not args.no_roofline else None}
-        emit(out)
+        emit(out, not args.plain)
     finish(local_dev)
 
 
@@ -461,7 +463,7 @@ def bench_qhnet(args, rank, world, local_dev, dev):
                "final_loss": rec["final_loss"], "roofline": rec.get("roofline"), "cpu_baseline": cpu, "kernel_ms_per_step": rec.get("kernel_ms_per_step"), "gemm_classes_TFLOPs": rec.get("gemm_classes_TFLOPs"),
                "gemm_tflops": rec.get("gemm_tflops"), "reference_batch_size_2": None if small is None else {k: small[k] for k in ("value", "unit", "ms_per_step", "atoms", "ordered_pairs")},
                "reference_batch_size_2_prepared_eager_vs_graph_replay": _graph_replay("qhnet") if world == 1 and not args.no_roofline else None}
-        emit(out)
+        emit(out, not args.plain)
     finish(local_dev)
 
 
@@ -536,8 +538,12 @@ def compact_record(full, full_path=None):
     return rec
 
 
-def emit(full):
+def emit(full, write_full=True):
     """Full record -> gpurun_out/bench_full.json; compact record -> the last stdout line."""
+    global _LINE
+    if not write_full:                     # a plain run writes no file besides its outputs: the compact line is the whole record
+        _LINE = json.dumps(compact_record(full))
+        return
     path = os.path.join("gpurun_out", "bench_full.json")
     try:
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
@@ -545,7 +551,6 @@ def emit(full):
             json.dump(full, fh)
     except OSError:
         path = None
-    global _LINE
     _LINE = json.dumps(compact_record(full, path))
 
 
@@ -750,6 +755,20 @@ def cpu_baseline(seconds_budget=25.0, all_cores=False, gemm_variant=1):
     return out, parity
 
 
+DUMP_LIMIT = 64 << 20   # bytes
+
+
+def dump_outputs(out_dir, step):
+    """What a caller of the timed step holds after its last call, as float32 .npy files: the loss, the per-conformer energies, the forces, the flat
+    parameter gradient and the flat parameters after the optimiser update (PaiNN-OC at 2048 conformers: ~13 MB; the forces grow by 12 bytes per atom)."""
+    arrays = {"loss": step.loss, "energy": step.energy, "forces": step.forces, "grad": step.grad, "params": step._eng.flat()}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT, "--dump-outputs: the outputs exceed 64 MB"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -759,12 +778,24 @@ def main():
     ap.add_argument("--sustain", type=float, default=8.0, help="seconds of extra (untimed) steps after the timed region: keeps the GPU visibly busy for coarse samplers; 0 = off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--full", action="store_true", help="also run the side legs (other engine, sibling config, host feed, inference, QHNet / GemNet-OC / eSCN / "
-                                                        "EquiformerV2 / PhiSNet records) into gpurun_out/bench_full.json; the stdout line stays the compact record")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps, run every other measurement: the instrumented kernel pass and roofline, the "
+                                                        "CPU baseline and accuracy, the sustained, sibling-config and batch-32 legs, and the side legs (other engine, "
+                                                        "host feed, inference, QHNet / GemNet-OC / eSCN / EquiformerV2 / PhiSNet records); the full record goes to "
+                                                        "bench_full.json, the stdout line stays the compact record")
+    ap.add_argument("--no-side-legs", action="store_true", help="with --full: skip the side legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loss, energies, forces, flat gradient, updated flat parameters) "
+                         "as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--model", choices=sorted(WORKLOADS), default="painn-oc",
                     help="painn-oc: in-tree PaiNN (parity pinned by reference golden vectors); painn-spk: config/painn.yaml (schnetpack PaiNN, unpinned)")
     ap.add_argument("--gemm-variant", type=int, default=None, help="tuning: nq_set_gemm_variant (bit0 8 waves, bit1 prefetch)")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.model in ("qhnet", "gemnet", "escn", "equiformer"):
+        ap.error(f"--dump-outputs is not implemented for --model {args.model}")
+    args.plain = not args.full
+    if args.plain:                 # a plain run times the headline step and nothing else
+        args.no_roofline = args.no_cpu_baseline = True
+    args.full = args.full and not args.no_side_legs      # from here on: run the side legs
 
     import nabladft_amd as nq
     from nabladft_amd import _lib, dist as nqdist
@@ -806,6 +837,8 @@ def main():
     dt = time.perf_counter() - t0
     collective = collective_record(step)   # incl. the exposed all-reduce time of the last timed step
     final_loss = float(loss)          # NOW: `loss` is the step's device-side loss buffer, which every later step (roofline pass, side legs) overwrites
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, step)
     t = torch.tensor([dt], device=dev, dtype=torch.float64)
     if dist_on():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1071,7 +1104,7 @@ def main():
             "e2e_algorithmic_GBps_per_gpu": 17.8e6 * value / world / 1e9,
             "kernel_ms_per_step": {k: round(ms, 4) for k, ms, _ in (kernels or [])[:8]},
         }
-        emit(out)
+        emit(out, not args.plain)
     finish(local_dev)
 
 

@@ -41,6 +41,6 @@ else
   for k in 0 ${ABLATIONS:-1 2 3 4}; do
     lib=$PWD/$D/libnablaq_$k.so; [ $k = 0 ] && lib=$PWD/nabladft_amd/libnablaq.so
     echo "== ablate $k"
-    NABLAQ_LIB=$lib timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print({k:v for k,v in d['kernel_ms_per_step'].items() if k.startswith('msgf') or k.startswith('gwr')}, d['ms_per_step'])"
+    NABLAQ_LIB=$lib timeout 300 python bench.py --steps 5 --warmup 2 --full --no-side-legs --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print({k:v for k,v in d['kernel_ms_per_step'].items() if k.startswith('msgf') or k.startswith('gwr')}, d['ms_per_step'])"
   done 2>&1 | tee gpurun_out/ablate.log
 fi

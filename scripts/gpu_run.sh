@@ -3,8 +3,8 @@
 #   bash scripts/gpu_run.sh <out-subdir> <step> [<step> ...]
 # steps:  tests[:<pytest -k expression>]   GPU suite (or a selection) -> pytest.log
 #         smoke                            __graft_entry__.smoke()
-#         bench[:<extra bench.py args>]    default driver command -> bench_default.json, full record, kernel events
-#         benchq                           bench.py --model qhnet
+#         bench[:<extra bench.py args>]    bench.py --full --no-side-legs -> bench_default.json, full record, kernel events
+#         benchq                           bench.py --model qhnet --full
 #         full                             bench.py --full
 #         variants[:<bench args>]          every nabladft_amd/_variants/libnablaq_*.so next to the shipped library (scripts/variants.sh build ...)
 #         prof:<name>:<command...>         rocprofv3 --kernel-trace --stats of a command -> <name>_kernel_stats.csv
@@ -20,7 +20,7 @@ for step in "$@"; do
     tests) if [ -n "$arg" ]; then timeout -k 5 1500 python -m pytest tests -q -m gpu -x -k "$arg" 2>&1 | tail -25 | tee $OUT/pytest.log; else timeout -k 5 2400 python -m pytest tests -q -m gpu 2>&1 | tail -15 | tee $OUT/pytest.log; fi
            cp gpurun_out/parity_report.txt gpurun_out/mixed_sizes_report.txt $OUT/ 2>/dev/null ;;
     smoke) timeout -k 5 600 python __graft_entry__.py --smoke 2>&1 | tail -8 | tee $OUT/smoke.log ;;
-    bench) S=$(date +%s); timeout -k 5 700 python bench.py $arg > $OUT/bench_default.stdout 2> $OUT/bench_default.err; echo "wall $(( $(date +%s) - S )) s" | tee $OUT/bench_default.wall
+    bench) S=$(date +%s); timeout -k 5 700 python bench.py --full --no-side-legs $arg > $OUT/bench_default.stdout 2> $OUT/bench_default.err; echo "wall $(( $(date +%s) - S )) s" | tee $OUT/bench_default.wall
            tail -1 $OUT/bench_default.stdout > $OUT/bench_default.json; cp gpurun_out/bench_full.json $OUT/bench_default_full_record.json 2>/dev/null; cp gpurun_out/kernel_events.txt $OUT/kernel_events.txt 2>/dev/null
            python - $OUT/bench_default.json <<'PY'
 import json, sys
@@ -32,11 +32,11 @@ except Exception as e:
     print("no bench record:", e); print(open(sys.argv[1].replace(".json", ".err")).read()[-1500:])
 PY
            ;;
-    benchq) timeout -k 5 500 python bench.py --model qhnet > $OUT/bench_qhnet.stdout 2> $OUT/bench_qhnet.err; tail -1 $OUT/bench_qhnet.stdout > $OUT/bench_qhnet.json; cp gpurun_out/bench_full.json $OUT/bench_qhnet_full_record.json; tail -c 600 $OUT/bench_qhnet.json; echo ;;
+    benchq) timeout -k 5 500 python bench.py --model qhnet --full > $OUT/bench_qhnet.stdout 2> $OUT/bench_qhnet.err; tail -1 $OUT/bench_qhnet.stdout > $OUT/bench_qhnet.json; cp "$(dirname $OUT)/bench_full.json" $OUT/bench_qhnet_full_record.json; tail -c 600 $OUT/bench_qhnet.json; echo ;;
     full) S=$(date +%s); timeout -k 5 1500 python bench.py --full > $OUT/bench_full.stdout 2> $OUT/bench_full.err; echo "wall $(( $(date +%s) - S )) s" | tee $OUT/bench_full.wall; cp gpurun_out/bench_full.json $OUT/bench_full_record.json ;;
     variants) for lib in nabladft_amd/libnablaq.so nabladft_amd/_variants/libnablaq_*.so; do
                 echo "-- $lib"
-                NABLAQ_LIB=$PWD/$lib timeout 300 python bench.py --steps 4 --warmup 2 --no-cpu-baseline $arg 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_step']; print({n:round(k.get(n,0),3) for n in '${VAR_KEYS:-gwr_mol,msgf_rev_dual_ng,msgf_tan,msgf_rev_force,msgf_fwd,upd_rev}'.split(',')}, round(sum(k.values()),3), round(d['ms_per_step'],3))"
+                NABLAQ_LIB=$PWD/$lib timeout 300 python bench.py --steps 4 --warmup 2 --full --no-side-legs --no-cpu-baseline $arg 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_step']; print({n:round(k.get(n,0),3) for n in '${VAR_KEYS:-gwr_mol,msgf_rev_dual_ng,msgf_tan,msgf_rev_force,msgf_fwd,upd_rev}'.split(',')}, round(sum(k.values()),3), round(d['ms_per_step'],3))"
               done 2>&1 | tee $OUT/variants.txt ;;
     prof) name=${arg%%:*}; cmd=${arg#*:}; rm -rf $OUT/prof_$name
           timeout -k 5 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o $name -- $cmd > $OUT/rocprof_$name.log 2>&1

@@ -92,3 +92,24 @@ def test_compact_record_carries_the_round_5_fields():
     assert set(rec["sibling_config"]) == {"workload", "value", "ms_per_step", "parity"} and rec["sibling_config"]["parity"] == "unpinned"
     assert rec["config"]["collective"]["ranks_seen"] == 8 and rec["config"]["collective"]["allreduce_exposed_ms"] == 0.41
     assert len(json.dumps(rec)) < bench.COMPACT_LIMIT
+
+
+def test_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """--dump-outputs: one float32 .npy per array a caller of the timed step receives, values unchanged."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    flat = torch.randn(5000, generator=g)
+    step = types.SimpleNamespace(loss=torch.tensor([1.25]), energy=torch.randn(40, generator=g), forces=torch.randn(900, 3, generator=g),
+                                 grad=torch.randn(5000, generator=g), _eng=types.SimpleNamespace(flat=lambda: flat))
+    bench.dump_outputs(str(tmp_path / "out"), step)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert set(got) == {"loss", "energy", "forces", "grad", "params"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["forces"], step.forces.numpy())
+    np.testing.assert_array_equal(got["energy"], step.energy.numpy())
+    np.testing.assert_array_equal(got["grad"], step.grad.numpy())
+    np.testing.assert_array_equal(got["params"], step._eng.flat().numpy())
+    assert float(got["loss"][0]) == 1.25

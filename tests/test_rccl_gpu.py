@@ -133,7 +133,8 @@ def test_bench_one_rank_through_the_nccl_branch():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                NQ_DIST_FORCE="1")
     env.pop("NQ_DIST_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--no-cpu-baseline", "--sustain", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--full", "--no-side-legs",
+                        "--no-cpu-baseline", "--sustain", "0"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     last = r.stdout.strip().splitlines()[-1]
