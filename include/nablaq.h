@@ -110,7 +110,12 @@ size_t nq_painn_workspace_bytes(const nq_painn_cfg* cfg, int32_t N, int32_t E, i
 int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* rbf_offsets, const nq_graph* graph, void* workspace,
                      size_t workspace_bytes, float* energy, float* forces, void* stream);
 /* Given dL/dE[B] and dL/dF[N][3] (either may be NULL = zeros) writes dL/dparams[num_params] (overwrites).
- * Must follow nq_painn_forward (with forces) on the same workspace and graph. */
+ * Must follow nq_painn_forward on the same workspace and graph; after a forward call without forces (energy-only training) it runs the full
+ * dual sweep instead of reading the stored force-sweep adjoints.
+ * The workspace layout and every path choice (fused filter, rbf_proj gradient path, stored adjoints) are the ones the last forward call on
+ * this workspace made; environment switches changed after it have no effect.  Returns NQ_ERR_ARG before any device work when no forward call
+ * has prepared the workspace, or when that call was made for another nq_painn_cfg or another batch (N, E, B, max_mol_atoms).
+ * The same holds for nq_painn_backward_events and nq_painn_backward_seeded. */
 int nq_painn_backward(const nq_painn_cfg* cfg, const float* params, const float* rbf_offsets, const nq_graph* graph, void* workspace,
                       size_t workspace_bytes, const float* grad_energy, const float* grad_forces, float* grad_params, void* stream);
 /* nq_painn_backward with completion events: layer_events_host[i] (HOST array of L hipEvent_t, entries may be NULL) is recorded on `stream` as soon as

@@ -188,26 +188,20 @@ int nq_graph_count_impl(const float* pos, const int* mol_ptr, int N, int B, int 
                         int* row_ptr, int* lowptr, int* E_host, hipStream_t st);
 int nq_graph_fill_impl(GraphFillArgs args, int B, int max_mol_atoms, hipStream_t st);
 
-// Bpre (optional): the weight pre-split into bf16 planes by nq_gemm_presplit_kn (same values as W): the split engine then loads it with 16-byte loads, no split arithmetic
 int nq_gemm_nn_epi(hipStream_t st, const float* G, const float* W, float* C, int M, int Nout, int Kin, const float* aux, float ea, float eb, int mode,
-                   const char* tag = nullptr, const void* Bpre = nullptr);
-int nq_gemm_nn_dsilu2(hipStream_t st, const float* G, const float* W, float* C, float* C2, const float* aux, int M, int Nout, int Kin, const char* tag, const void* Bpre = nullptr);
-int nq_gemm_presplit_kn(hipStream_t st, int n, const float* const* W, const int* Kc, const int* N, void* const* out);
+                   const char* tag = nullptr);
+int nq_gemm_nn_dsilu2(hipStream_t st, const float* G, const float* W, float* C, float* C2, const float* aux, int M, int Nout, int Kin, const char* tag);
 int nq_gemm_nt_dsilu(hipStream_t st, const float* A, const float* W, float* C, float* C2, const float* aux, int M, int N, int K, const char* tag = nullptr);
 int nq_gemm_nt_act(hipStream_t, const float* A, const float* W, float* C, float* C2, const float* resid, float ea, float eb, int M, int N, int K,
                    const char* tag = nullptr);
 int nq_gemm_nt(hipStream_t, const float* A, const float* W, float* C, const float* bias, float* C2_silu, int M, int N, int K, int lda,
                int ldw, int ldc, const char* tag = nullptr);
 int nq_gemm_nn(hipStream_t, const float* G, const float* W, float* C, int M, int Nout, int Kin, int ldg, int ldw, int ldc, int accumulate,
-               const char* tag = nullptr, const void* Bpre = nullptr);
+               const char* tag = nullptr);
 int nq_gemm_nt_res(hipStream_t st, const float* A, const float* W, float* C, const float* aux, float ea, int M, int N, int K);
 size_t nq_gemm_tn_scratch_floats(long rows, int Mo, int No);
 int nq_gemm_tn(hipStream_t, const float* GY, const float* X, float* out, long rows, int Mo, int No, int ldg, int ldx, float* scratch,
                const char* tag = nullptr, float* bias_out = nullptr, long bias_rows = 0);
-// several weight-gradient products (+ bias gradients) in one launch and one reduction of the partial tiles; NQ_ERR_ARG = not eligible, nothing launched
-struct NqTnSpec { const float* G; const float* X; float* out; long rows; int Mo, No, ldg, ldx; float* bias_out; long bias_rows; };
-size_t nq_gemm_tn_group_scratch_floats(const NqTnSpec* sp, int n);
-int nq_gemm_tn_group(hipStream_t, const NqTnSpec* sp, int n, float* scratch);
 size_t nq_colsum_scratch_floats(long rows, int cols);
 int nq_colsum(hipStream_t, const float* A, long rows, int cols, int lda, float* out, float* scratch);
 int nq_reduce_partials(hipStream_t, const float* part, int nsplit, long stride, long count, float* out);
@@ -233,7 +227,7 @@ int nq_gwr_sorted(hipStream_t, const float* GPHI, const float* GPSI, const float
 int nq_msgf_fwd(hipStream_t, const MsgArgs&, const FilterArgs&, bool tangent);
 int nq_msgf_rev(hipStream_t, const MsgRevArgs&, const FilterArgs&, bool dual, bool pair_rows = true);   // pair_rows = false: the dual flavour neither writes gphi / gpsi nor GBR (molpair.hip computes the rbf_proj gradient); MsgRevArgs::row_filter selects the rows
 // rbf_proj gradient with the molecule's node rows staged in LDS (molpair.hip): no gphi / gpsi arrays
-int nq_molgw_max_atoms(void);                      // largest molecule whose 20 rows of a 32-channel slice fit the LDS (64)
+int nq_molgw_max_atoms(void);                      // largest molecule whose 20 rows of a 32-channel slice fit the LDS (62)
 bool nq_molgw_config_ok(int F, int R);             // channel count / window count supported
 bool nq_molgw_supported(int F, int R, int max_mol_atoms);
 size_t nq_molgw_sched_ints(int E, int B);
@@ -250,12 +244,11 @@ int nq_msg_rev(hipStream_t, const MsgRevArgs&, bool dual);
 int nq_geom_tan(hipStream_t, const NqGraphView&, const int* dst, const float* pos_dot, float* TD, float* TR);
 int nq_geom_rev(hipStream_t, const NqGraphView&, const float4* GEDGE, int nwaves, float* forces);
 
-// the whole update block of one layer and sweep as one kernel (updfuse.hip; hidden_channels = 128): weight fragments once per forward call, then one launch
+// the whole update block of one layer's forward sweep as one kernel (updfuse.hip; hidden_channels = 128): weight fragments once per forward call, then one launch
 bool nq_gemm_exact_f32_requested();   // the exact-f32 engine was asked for (NQ_GEMM_F32=1 / nq_set_gemm_variant(32)): kernels that only exist on the bf16 matrix pipe step aside
 size_t nq_updfuse_frag_floats(int F);
 int nq_updfuse_presplit(hipStream_t, const float* U, const float* V1, const float* V2, int F, float* frag);
-int nq_upd_fused(hipStream_t, const UpdArgs&, const float* frag, const float* c1, const float* c2, float* ZQ, float* Q, float* TZQ, float* TQ, bool tan);
-int nq_updrev_fused(hipStream_t, const UpdRevArgs&, const float* frag, const float* ZQ);   // force-adjoint sweep: rev1, three input-gradient products, rev2 in one kernel
+int nq_upd_fused(hipStream_t, const UpdArgs&, const float* frag, const float* c1, const float* c2, float* ZQ, float* Q);
 int nq_upd_a(hipStream_t, const UpdArgs&, bool tan);
 int nq_upd_b(hipStream_t, const UpdArgs&, bool tan);
 int nq_silu_tan(hipStream_t, const float* Z, const float* TZ, float* TH, long count);

@@ -104,7 +104,6 @@ struct WsLayer {
   size_t Z1, Hh, XH, PHI, PSI, XM, VM, UU, S, CAT, ZQ, Q, Y;  // float offsets; dual buffers hold [2][rows][w]
   size_t WRT;                                                  // [R][3F] transposed rbf_proj.weight
   size_t UFRAG;                                                // bf16 fragments of the update block's weights (updfuse.hip), rebuilt by every forward call
-  size_t WPRE;                                                 // bf16 planes of V2, V1, U, W2, W1 for the input-gradient products (gemm_split.h PreStageB), rebuilt by every forward call
   // Per-layer adjoint store (fused filter only).  The tangent adjoints of the second-order sweep ARE the adjoints of the force sweep (same recursion, same seeds),
   // so the force sweep writes its gy, gcat, gu, gxh into the SECOND halves of these stacked [2][rows][w] buffers and keeps the four stages of gx / gvec
   // (a: adjoint of x_upd / vec_upd, b: of x_msg / vec_msg); the second-order sweep fills the first halves and reads the second ones instead of recomputing them.
@@ -121,15 +120,9 @@ struct WsLayout {
 };
 static size_t a4(size_t x) { return (x + 3) & ~(size_t)3; }  // keep every buffer 16-byte aligned
 
-static bool use_fused_filter(const nq_painn_cfg* c) {
-  const char* off = getenv("NQ_NO_FUSED_FILTER");
-  return c->rbf_type == 0 && nq_filter_fits_lds(c->hidden_channels, c->num_rbf) && !(off && off[0] == '1');   // the window needs compact Gaussians
-}
-
-static void tn_group_shapes(NqTnSpec (&sp)[5], long N, int F);
-static void make_ws_layout(const nq_painn_cfg* c, size_t N, size_t E, size_t B, WsLayout* W) {
+static void make_ws_layout(const nq_painn_cfg* c, size_t N, size_t E, size_t B, bool fused, WsLayout* W) {
   const size_t F = c->hidden_channels, R = c->num_rbf, H = F / 2, L = c->num_layers, T = c->num_elements;
-  W->fused = use_fused_filter(c);
+  W->fused = fused;
   const size_t EP = W->fused ? 0 : E;
   size_t o = 0;
   auto take = [&](size_t n) { size_t r = o; o += a4(n); return r; };
@@ -141,7 +134,6 @@ static void make_ws_layout(const nq_painn_cfg* c, size_t N, size_t E, size_t B, 
     y.XM = take(2 * N * F); y.VM = take(2 * N * 3 * F); y.UU = take(2 * N * 6 * F);
     y.S = take(2 * N * F); y.CAT = take(2 * N * 2 * F); y.ZQ = take(2 * N * F); y.Q = take(2 * N * F); y.Y = take(2 * N * 3 * F);
     y.UFRAG = take(nq_updfuse_frag_floats((int)F));
-    y.WPRE = take(11 * F * F * 6 / 4);
     const size_t st_ = W->fused ? 1 : 0;
     y.LGY = take(st_ * 2 * N * 3 * F); y.LGCAT = take(st_ * 2 * N * 2 * F); y.LGU = take(st_ * 2 * N * 6 * F); y.LGXH = take(st_ * 2 * N * 3 * F);
     y.LGXA = take(st_ * N * F); y.LGXB = take(st_ * N * F); y.LGVA = take(st_ * N * 3 * F); y.LGVB = take(st_ * N * 3 * F);
@@ -171,7 +163,6 @@ static void make_ws_layout(const nq_painn_cfg* c, size_t N, size_t E, size_t B, 
   mx(W->fused ? nq_gwr_scratch_floats((int)E, (int)F, (int)R) : nq_gemm_tn_scratch_floats(2 * E, 3 * F, R));
   if (W->fused) mx(nq_k0_sort_scratch_ints((int)E, (int)R));
   mx(nq_gemm_tn_scratch_floats(2 * N, F, F)); mx(nq_gemm_tn_scratch_floats(2 * N, H, F));
-  { NqTnSpec sp[5]; tn_group_shapes(sp, (long)N, (int)F); mx(nq_gemm_tn_group_scratch_floats(sp, 5)); }
   mx(nq_colsum_scratch_floats(N > E ? N : E, 3 * F));
   if (c->rbf_type) { mx(nq_colsum_scratch_floats(E, R)); mx(nq_colsum_scratch_floats(E * R, 1)); }
   mx(nq_embed_grad_scratch_floats((int)N, (int)F, (int)T));
@@ -181,82 +172,62 @@ static void make_ws_layout(const nq_painn_cfg* c, size_t N, size_t E, size_t B, 
   (void)B;
 }
 
+// ---- the plan of a step --------------------------------------------------------------------------------------------------------------------------
+// Every path choice that the two calls of a step must agree on is made ONCE, by the forward call, and recorded per workspace; the backward call follows the
+// record and refuses a workspace that no forward call has prepared for this model and batch.  plan_step is the only reader of the switches below.
 // rbf_proj gradient from node rows staged per molecule in LDS (molpair.hip) instead of gphi / gpsi pair rows through HBM: needs the fused filter.
 //   GW_PAIR_ROWS  the dual-reverse kernel writes gphi / gpsi per pair, k_gwr_sorted reads them back (small batches; NQ_NO_MOLGW=1 forces it)
 //   GW_MOLECULE   every molecule fits the LDS of one workgroup (nq_graph::max_mol_atoms <= cap): k_gwr_mol, nothing stored per pair
 //   GW_MIXED      some molecules are larger than cap: THEIR rows go through the pair-row kernels, every other molecule stays on k_gwr_mol
-// The decision is taken ONCE per step, by the forward call (which builds the schedule), and remembered per workspace: the backward call reads it back instead
-// of re-evaluating the environment (a changed NQ_MOLGW between the two calls would consume a schedule that was never built).
 enum { GW_PAIR_ROWS = 0, GW_MOLECULE = 1, GW_MIXED = 2 };
-struct GwMode { int mode; int cap; int lite; };   // lite: the force sweep of this step left its per-layer adjoints in the workspace (WsLayer::LG*)
-static int molgw_cap() {
-  const char* c = getenv("NQ_MOLGW_CAP");   // tests: a small cap sends ordinary molecules down the mixed path
+struct StepPlan {
+  bool fused;          // radial filter evaluated inside the message kernels (WrT resident in LDS); fixes the workspace layout
+  int gw_mode, gw_cap;
+  bool lite;           // the force sweep leaves its per-layer adjoints in the workspace (WsLayer::LG*) for the second-order sweep
+  bool fused_update;   // forward sweep: the update block of a layer as one kernel (updfuse.hip)
+};
+static StepPlan plan_step(const nq_painn_cfg* c, const nq_graph* g, bool want_forces) {
+  auto env_on = [](const char* name) { const char* v = getenv(name); return v && v[0] == '1'; };
+  StepPlan p{};
+  p.fused = c->rbf_type == 0 && nq_filter_fits_lds(c->hidden_channels, c->num_rbf) && !env_on("NQ_NO_FUSED_FILTER");   // the window needs compact Gaussians
+  const char* cap = getenv("NQ_MOLGW_CAP");   // tests: a small cap sends ordinary molecules down the mixed path
   const int hw = nq_molgw_max_atoms();
-  if (c && atoi(c) > 0 && atoi(c) < hw) return atoi(c);
-  return hw;
-}
-static GwMode decide_molgw(const nq_painn_cfg* c, const nq_graph* g, const WsLayout& W) {
-  GwMode r{GW_PAIR_ROWS, molgw_cap(), 0};
-  const char* off = getenv("NQ_NO_MOLGW");
-  if (!W.fused || (off && off[0] == '1') || !nq_molgw_config_ok(c->hidden_channels, c->num_rbf) || g->max_mol_atoms <= 0) return r;
+  p.gw_cap = cap && atoi(cap) > 0 && atoi(cap) < hw ? atoi(cap) : hw;
   // small batches (the reference's 32 conformers): the schedule kernels and the two launches per layer are pure latency there (measured 3.99 vs 3.72 ms per
   // step at 32 conformers), the pair rows are a few MB; NQ_MOLGW=1 forces the per-molecule path at any size (tests)
-  const char* on = getenv("NQ_MOLGW");
-  if (!((on && on[0] == '1') || g->N >= 4096)) return r;
-  r.mode = g->max_mol_atoms <= r.cap ? GW_MOLECULE : GW_MIXED;
-  return r;
+  p.gw_mode = GW_PAIR_ROWS;
+  if (p.fused && !env_on("NQ_NO_MOLGW") && nq_molgw_config_ok(c->hidden_channels, c->num_rbf) && g->max_mol_atoms > 0 && (env_on("NQ_MOLGW") || g->N >= 4096))
+    p.gw_mode = g->max_mol_atoms <= p.gw_cap ? GW_MOLECULE : GW_MIXED;
+  p.lite = p.fused && want_forces && !env_on("NQ_NO_LITE");
+  // NQ_NO_FUSED_UPDATE=1 keeps the five launches (A/B runs, tests); the fused kernel's products exist on the split-bf16 matrix pipe only, so a run that asks
+  // for the exact-f32 engine gets the five launches too
+  p.fused_update = nq_updfuse_frag_floats(c->hidden_channels) > 0 && !env_on("NQ_NO_FUSED_UPDATE") && !nq_gemm_exact_f32_requested();
+  return p;
 }
-static std::mutex g_gw_mu;
-static std::map<const void*, GwMode> g_gw_modes;   // by workspace: written by the forward call, read by the backward call of the same step
-static void remember_molgw(const void* ws, GwMode m) { std::lock_guard<std::mutex> lock(g_gw_mu); g_gw_modes[ws] = m; }
-static bool recall_molgw(const void* ws, GwMode* m) {
-  std::lock_guard<std::mutex> lock(g_gw_mu);
-  auto it = g_gw_modes.find(ws);
-  if (it == g_gw_modes.end()) return false;
-  *m = it->second;
-  return true;
-}
-
-// update block of a layer as one kernel per sweep (updfuse.hip): hidden_channels = 128; NQ_NO_FUSED_UPDATE=1 keeps the five launches of rounds 1-5 (A/B runs, tests)
-static bool use_fused_update(const nq_painn_cfg* c) {
-  const char* off = getenv("NQ_NO_FUSED_UPDATE");
-  // (the fused kernel's products exist on the split-bf16 matrix pipe only: a run that asks for the exact-f32 engine gets the five launches)
-  return nq_updfuse_frag_floats(c->hidden_channels) > 0 && !(off && off[0] == '1') && !nq_gemm_exact_f32_requested();
+// the layout of a workspace sized or inspected outside a step (nq_painn_workspace_bytes, nq_painn_ws_lookup): the plan such a step would make now
+static bool plan_fused(const nq_painn_cfg* c, int32_t N, int32_t E, int32_t B) {
+  nq_graph g{};
+  g.N = N; g.E = E; g.B = B;
+  return plan_step(c, &g, false).fused;
 }
 
-// The five weight-gradient products of one layer's dual-reverse sweep as ONE grouped launch (gemm.hip: nq_gemm_tn_group): built, parity-tested,
-// NOT the default.  Measured (profiles/r06_tn_group_ab.txt): 2048 conformers 49.56-49.85 ms per step grouped vs 49.29-49.40 one launch each; 32 conformers 4.19 vs
-// 3.73 ms -- the separate launches run on the side stream UNDER the layer's critical path, the grouped launch can only start when the layer's last adjoint exists, and
-// at the large size the 4.5x smaller partial-tile traffic does not pay for the longer serial row streams per workgroup.  NQ_TN_GROUP=1 selects it.
-static bool use_tn_group() {
-  const char* on = getenv("NQ_TN_GROUP");
-  return on && on[0] == '1';
+// what the forward call planned, per workspace, with a stamp of the model and batch it was made for
+struct StepRecord { nq_painn_cfg cfg; int32_t N, E, B, max_mol_atoms; StepPlan plan; };
+static std::mutex g_plan_mu;
+static std::map<const void*, StepRecord> g_plans;
+static void record_plan(const void* ws, const nq_painn_cfg* c, const nq_graph* g, const StepPlan& p) {
+  std::lock_guard<std::mutex> lock(g_plan_mu);
+  g_plans[ws] = StepRecord{*c, g->N, g->E, g->B, g->max_mol_atoms, p};
 }
-static void tn_group_shapes(NqTnSpec (&sp)[5], long N, int F) {   // rows / output shapes only (workspace sizing); the engine fills in the pointers
-  const int F2 = 2 * F, F3 = 3 * F;
-  sp[0] = NqTnSpec{nullptr, nullptr, nullptr, 2 * N, F3, F, F3, F, reinterpret_cast<float*>(1), N};    // V2: gy^T q  (+ c2)
-  sp[1] = NqTnSpec{nullptr, nullptr, nullptr, 2 * N, F, F2, F, F2, reinterpret_cast<float*>(1), N};    // V1: gq^T cat (+ c1)
-  sp[2] = NqTnSpec{nullptr, nullptr, nullptr, 6 * N, F2, F, F2, F, nullptr, 0};                        // U:  gu^T vec_msg
-  sp[3] = NqTnSpec{nullptr, nullptr, nullptr, 2 * N, F3, F, F3, F, reinterpret_cast<float*>(1), N};    // W2: gxh^T h (+ b2)
-  sp[4] = NqTnSpec{nullptr, nullptr, nullptr, 2 * N, F, F, F, F, reinterpret_cast<float*>(1), N};      // W1: gh^T x (+ b1)
-}
-
-// Weights pre-split into bf16 planes once per step for the input-gradient products of both reverse sweeps: they load their weight tile with
-// three 16-byte loads per thread instead of eight 4-byte loads + the split arithmetic.  Measured SLOWER at 2048 conformers (49.53 / 49.56 ms per step against
-// 48.81 / 48.95 ms, same box, profiles/r06_presplit_nn_ab.txt: the planes are 6 bytes per element against 4 and one epilogue flavour spills), so it is opt-in:
-// NQ_PRESPLIT=1, hidden_channels % 128 == 0, never under the exact-f32 engine.
-struct PrePlanes { const void* V2; const void* V1; const void* U; const void* W2; const void* W1; };
-static bool use_presplit(const nq_painn_cfg* c) {
-  const char* on = getenv("NQ_PRESPLIT");
-  return c->hidden_channels % 128 == 0 && on && on[0] == '1' && !nq_gemm_exact_f32_requested();
-}
-static PrePlanes pre_planes(const nq_painn_cfg* c, float* base) {
-  PrePlanes q{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (!use_presplit(c)) return q;
-  const size_t F = c->hidden_channels, FF = F * F;
-  unsigned short* b = reinterpret_cast<unsigned short*>(base);
-  q.V2 = b; q.V1 = b + 3 * 3 * FF; q.U = b + 3 * 5 * FF; q.W2 = b + 3 * 7 * FF; q.W1 = b + 3 * 10 * FF;
-  return q;
+static int recall_plan(const void* ws, const nq_painn_cfg* c, const nq_graph* g, StepPlan* p) {
+  std::lock_guard<std::mutex> lock(g_plan_mu);
+  auto it = g_plans.find(ws);
+  if (it == g_plans.end()) return nq_fail(NQ_ERR_ARG, "nq_painn_backward: no forward call has prepared this workspace");
+  const StepRecord& r = it->second;
+  if (memcmp(&r.cfg, c, sizeof(nq_painn_cfg)) != 0 || r.N != g->N || r.E != g->E || r.B != g->B || r.max_mol_atoms != g->max_mol_atoms)
+    return nq_fail(NQ_ERR_ARG, "nq_painn_backward: the last forward call on this workspace was made for a different model or batch");
+  *p = r.plan;
+  return NQ_OK;
 }
 
 static NqGraphView view_of(const nq_graph* g) {
@@ -267,13 +238,13 @@ static NqGraphView view_of(const nq_graph* g) {
   return v;
 }
 
-static int check_common(const nq_painn_cfg* cfg, const nq_graph* g, const void* ws, size_t ws_bytes, WsLayout* W, ParamLayout* P) {
+static int check_common(const nq_painn_cfg* cfg, const nq_graph* g, const void* ws, size_t ws_bytes, bool fused, WsLayout* W, ParamLayout* P) {
   if (!cfg || !g || !ws) return nq_fail(NQ_ERR_ARG, "null argument");
   NQ_TRY(make_param_layout(cfg, P));
   if (g->N <= 0 || g->B <= 0) return nq_fail(NQ_ERR_ARG, "empty batch");
   if (g->E <= 0) return nq_fail(NQ_ERR_NO_EDGES, "batch has no edges within the cutoff");
   if ((reinterpret_cast<uintptr_t>(ws) & 15) != 0) return nq_fail(NQ_ERR_ARG, "workspace must be 16-byte aligned");
-  make_ws_layout(cfg, g->N, g->E, g->B, W);
+  make_ws_layout(cfg, g->N, g->E, g->B, fused, W);
   if (cfg->filter_mode != 0 && cfg->filter_mode != 1) return nq_fail(NQ_ERR_ARG, "filter_mode must be 0 (painn_pyg) or 1 (schnetpack)");
   if (cfg->filter_mode == 1 && !W->fused)
     return nq_fail(NQ_ERR_ARG, "filter_mode 1 (schnetpack) needs the fused-filter path: hidden_channels in {64,128,256} and WrT fitting the LDS");
@@ -351,7 +322,7 @@ size_t nq_painn_workspace_bytes(const nq_painn_cfg* cfg, int32_t N, int32_t E, i
   ParamLayout P;
   if (!cfg || make_param_layout(cfg, &P) != NQ_OK || N <= 0 || E < 0) return 0;
   WsLayout W;
-  make_ws_layout(cfg, N, E, B, &W);
+  make_ws_layout(cfg, N, E, B, plan_fused(cfg, N, E, B), &W);
   return W.total_floats * sizeof(float);
 }
 
@@ -361,7 +332,7 @@ int nq_painn_ws_lookup(const nq_painn_cfg* cfg, int32_t N, int32_t E, int32_t B,
   if (!cfg || !name || !off || !count) return nq_fail(NQ_ERR_ARG, "null argument");
   NQ_TRY(make_param_layout(cfg, &P));
   WsLayout W;
-  make_ws_layout(cfg, N, E, B, &W);
+  make_ws_layout(cfg, N, E, B, plan_fused(cfg, N, E, B), &W);
   const size_t F = cfg->hidden_channels, R = cfg->num_rbf, H = F / 2, n = N, e = E;
   const int L = cfg->num_layers;
   size_t base = 0, rows = 0, w = 0;
@@ -421,9 +392,12 @@ int nq_painn_ws_lookup(const nq_painn_cfg* cfg, int32_t N, int32_t E, int32_t B,
 // ------------------------------------------------------------------------------------------------
 int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* rbf_offsets, const nq_graph* graph, void* workspace,
                      size_t workspace_bytes, float* energy, float* forces, void* stream) {
+  if (!cfg || !graph) return nq_fail(NQ_ERR_ARG, "null argument");
+  const StepPlan plan = plan_step(cfg, graph, forces != nullptr);
   WsLayout W; ParamLayout P;
-  NQ_TRY(check_common(cfg, graph, workspace, workspace_bytes, &W, &P));
+  NQ_TRY(check_common(cfg, graph, workspace, workspace_bytes, plan.fused, &W, &P));
   if (!params || !rbf_offsets || !energy) return nq_fail(NQ_ERR_ARG, "null argument");
+  record_plan(workspace, cfg, graph, plan);
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
   const NqGraphView g = view_of(graph);
@@ -440,36 +414,23 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
   NQ_HIP(hipMemsetAsync(ws + W.X[0] + NF, 0, NF * sizeof(float), st));
   NQ_HIP(hipMemsetAsync(ws + W.V[0], 0, 6 * NF * sizeof(float), st));
   float* rho = ws + W.RHO2; float* drho = rho + (size_t)E * R;
-  GwMode gw = decide_molgw(cfg, graph, W);   // GW_PAIR_ROWS without the fused filter
-  // the force sweep below stores its per-layer adjoints for the second-order sweep (WsLayer::LG*): fused filter, the five-launch update reverse, NQ_NO_LITE unset
-  const bool lite_store = W.fused && forces != nullptr && !(getenv("NQ_FUSED_UPDATE_REV") && getenv("NQ_FUSED_UPDATE_REV")[0] == '1') &&
-                          !(getenv("NQ_NO_LITE") && getenv("NQ_NO_LITE")[0] == '1');
-  gw.lite = lite_store ? 1 : 0;
-  remember_molgw(workspace, gw);
+  const bool lite_store = plan.lite;   // the force sweep below stores its per-layer adjoints for the second-order sweep (WsLayer::LG*)
   if (W.fused) {
     FilterArgs fa0;
     nq_make_filter_args(&fa0, nullptr, nullptr, rbf_offsets, ws + W.RW, R, cfg->cutoff, cfg->envelope_exponent, cfg->rbf_coeff, cfg->filter_mode);
     NQ_TRY(nq_rbf_window(st, g.geom, E, fa0, ws + W.RW));
     int* const sched = reinterpret_cast<int*>(ws + W.SCHED);
-    if (gw.mode != GW_PAIR_ROWS) NQ_TRY(nq_molgw_schedule(st, g, graph->dst, ws + W.RW, R, gw.cap, sched, ws + W.GWREC));
-    if (gw.mode == GW_PAIR_ROWS) NQ_TRY(nq_k0_sort(st, ws + W.RW, E, R, reinterpret_cast<int*>(ws + W.ORDER), reinterpret_cast<int*>(ws + W.scratch), graph->dst, g.col));   // lower slots only
-    else if (gw.mode == GW_MIXED)   // lower slots of the molecules above the cap only; their number stays on the device (last spare int of the schedule block)
+    if (plan.gw_mode != GW_PAIR_ROWS) NQ_TRY(nq_molgw_schedule(st, g, graph->dst, ws + W.RW, R, plan.gw_cap, sched, ws + W.GWREC));
+    if (plan.gw_mode == GW_PAIR_ROWS) NQ_TRY(nq_k0_sort(st, ws + W.RW, E, R, reinterpret_cast<int*>(ws + W.ORDER), reinterpret_cast<int*>(ws + W.scratch), graph->dst, g.col));   // lower slots only
+    else if (plan.gw_mode == GW_MIXED)   // lower slots of the molecules above the cap only; their number stays on the device (last spare int of the schedule block)
       NQ_TRY(nq_k0_sort(st, ws + W.RW, E, R, reinterpret_cast<int*>(ws + W.ORDER), reinterpret_cast<int*>(ws + W.scratch), graph->dst, g.col, g.mol_ptr, g.atom_mol,
-                        gw.cap, sched + nq_molgw_sched_ints(E, g.B) - 1));
+                        plan.gw_cap, sched + nq_molgw_sched_ints(E, g.B) - 1));
   } else {
     NQ_TRY(nq_rbf(st, g.geom, E, R, cfg->cutoff, cfg->envelope_exponent, cfg->rbf_coeff, rbf_offsets, rho, drho, cfg->rbf_type, params + P.basis));
   }
 
-  const bool fused_upd = use_fused_update(cfg);
   for (int l = 0; l < L; ++l) {
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
-    if (use_presplit(cfg)) {
-      const PrePlanes pp = pre_planes(cfg, ws + y.WPRE);
-      const float* Wm[5] = {params + up.V2, params + up.V1, params + up.U, params + mp.W2, params + mp.W1};
-      const int Kc[5] = {3 * F, F, 2 * F, 3 * F, F}, Nc[5] = {F, 2 * F, F, F, F};
-      void* outp[5] = {const_cast<void*>(pp.V2), const_cast<void*>(pp.V1), const_cast<void*>(pp.U), const_cast<void*>(pp.W2), const_cast<void*>(pp.W1)};
-      NQ_TRY(nq_gemm_presplit_kn(st, 5, Wm, Kc, Nc, outp));
-    }
     NQ_TRY(nq_gemm_nt(st, ws + W.X[l], params + mp.W1, ws + y.Z1, params + mp.b1, ws + y.Hh, N, F, F, F, F, F, "W1"));
     NQ_TRY(nq_gemm_nt(st, ws + y.Hh, params + mp.W2, ws + y.XH, params + mp.b2, nullptr, N, 3 * F, F, F, F, 3 * F, "W2"));
     MsgArgs m{};
@@ -489,9 +450,9 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
     UpdArgs u{};
     u.N = N; u.F = F; u.XM = ws + y.XM; u.VM = ws + y.VM; u.U = ws + y.UU; u.Y = ws + y.Y; u.S = ws + y.S; u.CAT = ws + y.CAT;
     u.X1 = ws + W.X[l + 1]; u.V1 = ws + W.V[l + 1];
-    if (fused_upd) {
+    if (plan.fused_update) {
       NQ_TRY(nq_updfuse_presplit(st, params + up.U, params + up.V1, params + up.V2, F, ws + y.UFRAG));
-      NQ_TRY(nq_upd_fused(st, u, ws + y.UFRAG, params + up.c1, params + up.c2, ws + y.ZQ, ws + y.Q, nullptr, nullptr, false));
+      NQ_TRY(nq_upd_fused(st, u, ws + y.UFRAG, params + up.c1, params + up.c2, ws + y.ZQ, ws + y.Q));
       continue;
     }
     NQ_TRY(nq_gemm_nt(st, ws + y.VM, params + up.U, ws + y.UU, nullptr, nullptr, 3 * N, 2 * F, F, F, F, 2 * F, "U"));
@@ -520,7 +481,6 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
   NQ_HIP(hipMemsetAsync(ws + W.GEDGE, 0, (size_t)nwaves * E * 4 * sizeof(float), st));
   for (int l = L - 1; l >= 0; --l) {
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
-    const PrePlanes pp = pre_planes(cfg, ws + y.WPRE);
     float* const GY = lite_store ? ws + y.LGY + 3 * NF : ws + W.GY;
     float* const GCAT = lite_store ? ws + y.LGCAT + 2 * NF : ws + W.GCAT;
     float* const GU = lite_store ? ws + y.LGU + 6 * NF : ws + W.GU;
@@ -533,21 +493,15 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
     u.N = N; u.F = F; u.U = ws + y.UU; u.Y = ws + y.Y; u.S = ws + y.S; u.CAT = ws + y.CAT;
     u.GX = gx_cur; u.GV = gv_cur; u.GY = GY; u.GCAT = GCAT; u.GU = GU;
     u.GX_out = lite_store ? gx_msg : nullptr;
-    // Force-adjoint flavour of the fused update block: built, parity-tested, NOT the default -- 3.47 ms per step against 3.34 ms for the five launches below
-    // (five dependent products with ten barriers and 400 four-byte loads per lane at eight wavefronts per CU: profiles/r06_fused_update_ab.txt); NQ_FUSED_UPDATE_REV=1 selects it.
-    if (fused_upd && getenv("NQ_FUSED_UPDATE_REV") && getenv("NQ_FUSED_UPDATE_REV")[0] == '1') {
-      NQ_TRY(nq_updrev_fused(st, u, ws + y.UFRAG, ws + y.ZQ));   // no weight gradients in this sweep: gy, gq, gcat, gu never leave the chip
-    } else {
     NQ_TRY(nq_upd_rev(st, u, 1, false));
     // G_Q = (G_Y V2) * silu'(Z_Q): the activation's adjoint in the epilogue of the input-gradient product (no separate k_silu_rev pass)
     float* const GQ = lite_store ? ws + y.LGQ + NF : ws + W.GQ;
-    if (lite_store) NQ_TRY(nq_gemm_nn_dsilu2(st, GY, params + up.V2, ws + y.LGQP, GQ, ws + y.ZQ, N, 3 * F, F, "V2", pp.V2));   // keeps G_Y V2 as well (silu'' term of the second-order sweep)
-    else NQ_TRY(nq_gemm_nn_epi(st, GY, params + up.V2, GQ, N, 3 * F, F, ws + y.ZQ, 0.f, 1.f, 1, "V2", pp.V2));
-    NQ_TRY(nq_gemm_nn(st, GQ, params + up.V1, GCAT, N, F, 2 * F, F, 2 * F, 2 * F, 0, "V1", pp.V1));
+    if (lite_store) NQ_TRY(nq_gemm_nn_dsilu2(st, GY, params + up.V2, ws + y.LGQP, GQ, ws + y.ZQ, N, 3 * F, F, "V2"));   // keeps G_Y V2 as well (silu'' term of the second-order sweep)
+    else NQ_TRY(nq_gemm_nn_epi(st, GY, params + up.V2, GQ, N, 3 * F, F, ws + y.ZQ, 0.f, 1.f, 1, "V2"));
+    NQ_TRY(nq_gemm_nn(st, GQ, params + up.V1, GCAT, N, F, 2 * F, F, 2 * F, 2 * F, 0, "V1"));
     NQ_TRY(nq_upd_rev(st, u, 2, false));
-    if (lite_store) NQ_TRY(nq_gemm_nn_epi(st, GU, params + up.U, gv_msg, 3 * N, 2 * F, F, gv_cur, 1.f, 0.f, 0, "U", pp.U));   // gv_msg = gv_upd + gu U
-    else NQ_TRY(nq_gemm_nn(st, GU, params + up.U, gv_cur, 3 * N, 2 * F, F, 2 * F, F, F, 1, "U", pp.U));
-    }
+    if (lite_store) NQ_TRY(nq_gemm_nn_epi(st, GU, params + up.U, gv_msg, 3 * N, 2 * F, F, gv_cur, 1.f, 0.f, 0, "U"));   // gv_msg = gv_upd + gu U
+    else NQ_TRY(nq_gemm_nn(st, GU, params + up.U, gv_cur, 3 * N, 2 * F, F, 2 * F, F, F, 1, "U"));
     MsgRevArgs m{};
     m.g = g; m.F = F; m.V = ws + W.V[l]; m.XH = ws + y.XH; m.PHI = ws + y.PHI; m.PSI = ws + y.PSI;
     m.GX = gx_msg; m.GV = gv_msg; m.GXH = GXH; m.GV_out = gv_next; m.GEDGE = reinterpret_cast<float4*>(ws + W.GEDGE);
@@ -560,14 +514,14 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
       NQ_TRY(nq_msg_rev(st, m, false));
     }
     float* const GH = lite_store ? ws + y.LGH + NF : ws + W.GH;
-    if (lite_store) NQ_TRY(nq_gemm_nn_dsilu2(st, GXH, params + mp.W2, ws + y.LGHP, GH, ws + y.Z1, N, 3 * F, F, "W2", pp.W2));
-    else NQ_TRY(nq_gemm_nn_epi(st, GXH, params + mp.W2, GH, N, 3 * F, F, ws + y.Z1, 0.f, 1.f, 1, "W2", pp.W2));
+    if (lite_store) NQ_TRY(nq_gemm_nn_dsilu2(st, GXH, params + mp.W2, ws + y.LGHP, GH, ws + y.Z1, N, 3 * F, F, "W2"));
+    else NQ_TRY(nq_gemm_nn_epi(st, GXH, params + mp.W2, GH, N, 3 * F, F, ws + y.Z1, 0.f, 1.f, 1, "W2"));
     if (lite_store) {
-      NQ_TRY(nq_gemm_nn_epi(st, GH, params + mp.W1, gx_next, N, F, F, gx_msg, 1.f, 0.f, 0, "W1", pp.W1));   // gx_upd of the layer below = gx_msg + gz1 W1
+      NQ_TRY(nq_gemm_nn_epi(st, GH, params + mp.W1, gx_next, N, F, F, gx_msg, 1.f, 0.f, 0, "W1"));   // gx_upd of the layer below = gx_msg + gz1 W1
       gx_cur = gx_next; gv_cur = gv_next;
     } else {
       { float* t = gv_cur; gv_cur = gv_oth; gv_oth = t; }
-      NQ_TRY(nq_gemm_nn(st, GH, params + mp.W1, gx_cur, N, F, F, F, F, F, 1, "W1", pp.W1));
+      NQ_TRY(nq_gemm_nn(st, GH, params + mp.W1, gx_cur, N, F, F, F, F, F, 1, "W1"));
     }
   }
   NQ_TRY(nq_geom_rev(st, g, reinterpret_cast<const float4*>(ws + W.GEDGE), nwaves, forces));
@@ -640,8 +594,11 @@ static void side_stream_init(SideStream& s, hipStream_t main, int n_atoms) {
 static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, const float* rbf_offsets, const nq_graph* graph, void* workspace,
                                size_t workspace_bytes, const float* grad_energy, const float* grad_forces, float* grad_params, void* stream,
                                bool seeded, const float* seed_x, const float* seed_vec, void* const* layer_events = nullptr) {
+  if (!cfg || !graph || !workspace) return nq_fail(NQ_ERR_ARG, "null argument");
+  StepPlan plan;   // the layout and every path below are the forward call's: checked before anything is enqueued
+  NQ_TRY(recall_plan(workspace, cfg, graph, &plan));
   WsLayout W; ParamLayout P;
-  NQ_TRY(check_common(cfg, graph, workspace, workspace_bytes, &W, &P));
+  NQ_TRY(check_common(cfg, graph, workspace, workspace_bytes, plan.fused, &W, &P));
   if (!params || !grad_params || !rbf_offsets) return nq_fail(NQ_ERR_ARG, "null argument");
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
@@ -699,12 +656,6 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
     u.TXM = ws + y.XM + NF; u.TVM = ws + y.VM + 3 * NF; u.TU = ws + y.UU + 6 * NF; u.TY = ws + y.Y + 3 * NF;
     u.TS = ws + y.S + NF; u.TCAT = ws + y.CAT + 2 * NF; u.TX1 = ws + W.X[l + 1] + NF; u.TV1 = ws + W.V[l + 1] + 3 * NF;
     float* TZQ = ws + y.ZQ + NF; float* TQ = ws + y.Q + NF;
-    // Tangent flavour of the fused update block: built, parity-tested (tests/test_engine_gpu.py), NOT the default -- it re-reads the primal intermediates in the
-    // accumulator layout (4-byte loads) and measured 3.58 ms per step against 3.0 ms for the five launches below (profiles/r06_fused_update_ab.txt); NQ_FUSED_UPDATE_TAN=1 selects it.
-    if (use_fused_update(cfg) && getenv("NQ_FUSED_UPDATE_TAN") && getenv("NQ_FUSED_UPDATE_TAN")[0] == '1') {   // the fragments are the forward call's (same weights: one step)
-      NQ_TRY(nq_upd_fused(st, u, ws + y.UFRAG, nullptr, nullptr, ws + y.ZQ, ws + y.Q, TZQ, TQ, true));
-      continue;
-    }
     NQ_TRY(nq_gemm_nt(st, ws + y.VM + 3 * NF, params + up.U, ws + y.UU + 6 * NF, nullptr, nullptr, 3 * N, 2 * F, F, F, F, 2 * F, "U"));
     NQ_TRY(nq_upd_a(st, u, true));
     NQ_TRY(nq_gemm_nt_dsilu(st, ws + y.CAT + 2 * NF, params + up.V1, TZQ, TQ, ws + y.ZQ, N, F, 2 * F, "V1"));
@@ -726,14 +677,12 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
   if (seeded) NQ_HIP(hipMemsetAsync(ws + W.gte, 0, (size_t)N * sizeof(float), st));   // no Edot term
   r.ge = ws + W.ge; r.gte = ws + W.gte; r.GZO = ws + W.GZO; r.GTZO = ws + W.GZO + NH; r.TMPW = ws + W.TMPW;
   NQ_TRY(nq_readout_rev(st, r, true));
-  GwMode gw;
-  if (!recall_molgw(workspace, &gw)) return nq_fail(NQ_ERR_ARG, "nq_painn_backward: no forward call has prepared this workspace");
   // lite: the tangent adjoints (every GT* operand below) are the force sweep's adjoints of this step, stored per layer by nq_painn_forward: they are read, not
   // recomputed -- every input-gradient product runs over the primal-adjoint rows only, the elementwise and message kernels skip their GT* stores.
   // (The force sweep's V2 / W2 products keep both forms of their result: the adjoint of the SiLU layer's output, for the silu'' term here, and of its pre-activation.)
-  const bool lite = gw.lite && !seeded && W.fused;
+  const bool lite = plan.lite && !seeded;
   SideStream ss;
-  if (gw.mode != GW_MIXED) side_stream_init(ss, st, N);   // mixed batches: the pair-row contraction of the large molecules and the per-molecule kernel add into one
+  if (plan.gw_mode != GW_MIXED) side_stream_init(ss, st, N);   // mixed batches: the pair-row contraction of the large molecules and the per-molecule kernel add into one
                                                            // gradient and share the scratch with the split-K products -- everything stays on the main stream (a rare path)
   hipStream_t sd = ss.fork();          // sd == st when the side stream is off
   NQ_TRY(nq_colsum(sd, ws + W.TMPW, N, H, H, gp + P.w2, scr));
@@ -747,15 +696,13 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
     if (seed_vec) NQ_HIP(hipMemcpyAsync(gv_cur, seed_vec, 3 * NF * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   float* gphi = ws + W.GPHI2; float* gpsi = gphi + (size_t)E * 3 * F;
-  const bool molgw = gw.mode != GW_PAIR_ROWS, mixed = gw.mode == GW_MIXED;
-  const bool tn_group = use_tn_group();
+  const bool molgw = plan.gw_mode != GW_PAIR_ROWS, mixed = plan.gw_mode == GW_MIXED;
   const int* const sched = reinterpret_cast<const int*>(ws + W.SCHED);
   const int* const n_big_pairs = sched + nq_molgw_sched_ints(E, g.B) - 1;
   if (molgw) NQ_TRY(nq_molgw_geometry(st, g, ws + W.RW, ws + W.TD, ws + W.TR, sched, ws + W.GWREC));
   if (mixed) NQ_HIP(hipMemsetAsync(ws + W.GBR, 0, 3 * NF * sizeof(float), st));   // only the rows of the large molecules are written below; the column sum runs over all atoms
   for (int l = L - 1; l >= 0; --l) {
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
-    const PrePlanes pp = pre_planes(cfg, ws + y.WPRE);
     float* const GYs = lite ? ws + y.LGY : ws + W.GY;         // stacked [2][N][3F]: the second half is the force sweep's (lite) or written below
     float* const GCATs = lite ? ws + y.LGCAT : ws + W.GCAT;
     float* const GUs = lite ? ws + y.LGU : ws + W.GU;
@@ -771,28 +718,22 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
     u.lite = lite ? 1 : 0;
     ss.before_main_writes(SB_GY);
     NQ_TRY(nq_upd_rev(st, u, 1, true));
-    if (!tn_group) {
     sd = ss.fork();
     NQ_TRY(nq_gemm_tn(sd, GYs, ws + y.Q, gp + up.V2, 2L * N, 3 * F, F, 3 * F, F, scr, "V2", gp + up.c2, N));
     ss.read_by_side(SB_GY);
-    }
     ss.before_main_writes(SB_GQ);
-    NQ_TRY(nq_gemm_nn(st, GYs, params + up.V2, GQs, lite ? N : 2 * N, 3 * F, F, 3 * F, F, F, 0, "V2", pp.V2));
+    NQ_TRY(nq_gemm_nn(st, GYs, params + up.V2, GQs, lite ? N : 2 * N, 3 * F, F, 3 * F, F, F, 0, "V2"));
     NQ_TRY(nq_silu_rev(st, ws + y.ZQ, ws + y.ZQ + NF, GQs, lite ? ws + y.LGQP : GQs + NF, (long)NF, true, lite));
-    if (!tn_group) {
     sd = ss.fork();
     NQ_TRY(nq_gemm_tn(sd, GQs, ws + y.CAT, gp + up.V1, 2L * N, F, 2 * F, F, 2 * F, scr, "V1", gp + up.c1, N));
     ss.read_by_side(SB_GQ);
-    }
-    NQ_TRY(nq_gemm_nn(st, GQs, params + up.V1, GCATs, lite ? N : 2 * N, F, 2 * F, F, 2 * F, 2 * F, 0, "V1", pp.V1));
+    NQ_TRY(nq_gemm_nn(st, GQs, params + up.V1, GCATs, lite ? N : 2 * N, F, 2 * F, F, 2 * F, 2 * F, 0, "V1"));
     ss.before_main_writes(SB_GU);
     NQ_TRY(nq_upd_rev(st, u, 2, true));
-    if (!tn_group) {
     sd = ss.fork();
     NQ_TRY(nq_gemm_tn(sd, GUs, ws + y.VM, gp + up.U, 6L * N, 2 * F, F, 2 * F, F, scr, "U"));
     ss.read_by_side(SB_GU);
-    }
-    NQ_TRY(nq_gemm_nn(st, GUs, params + up.U, gv_cur, lite ? 3 * N : 6 * N, 2 * F, F, 2 * F, F, F, 1, "U", pp.U));
+    NQ_TRY(nq_gemm_nn(st, GUs, params + up.U, gv_cur, lite ? 3 * N : 6 * N, 2 * F, F, 2 * F, F, F, 1, "U"));
     MsgRevArgs m{};
     m.g = g; m.F = F; m.V = ws + W.V[l]; m.XH = ws + y.XH; m.PHI = ws + y.PHI; m.PSI = ws + y.PSI;
     m.TV = ws + W.V[l] + 3 * NF; m.TXH = ws + y.XH + 3 * NF; m.TD = ws + W.TD; m.TR = ws + W.TR;
@@ -805,7 +746,7 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
       FilterArgs fa;
       nq_make_filter_args(&fa, ws + y.WRT, params + mp.br, rbf_offsets, ws + W.RW, R, cfg->cutoff, cfg->envelope_exponent, cfg->rbf_coeff, cfg->filter_mode);
       fa.row_ctr = row_ctr(3, l);
-      m.mol_cap = gw.cap;
+      m.mol_cap = plan.gw_cap;
       m.row_filter = mixed ? 1 : 0;
       NQ_TRY(nq_msgf_rev(st, m, fa, true, !molgw));
       if (mixed) {   // the molecules that do not fit the LDS of k_gwr_mol: pair rows, k0-sorted contraction and per-atom bias sums as in rounds 1-4, for THEIR rows only
@@ -818,7 +759,7 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
       // rbf_proj weight and bias gradient from the same node rows, staged per molecule in LDS (main stream: it reads the adjoints this layer's input-gradient
       // products overwrite next; the fork below orders the side stream and the layer event behind it); mixed: added to what the pair-row kernels left
       if (molgw)
-        NQ_TRY(nq_gwr_mol(st, g, F, R, gw.cap, m.XH, m.V, m.TXH, m.TV, m.GX, m.GV, m.GTX, m.GTV, sched, ws + W.GWREC, ws + W.GWPART, gp + mp.Wr, gp + mp.br, mixed));
+        NQ_TRY(nq_gwr_mol(st, g, F, R, plan.gw_cap, m.XH, m.V, m.TXH, m.TV, m.GX, m.GV, m.GTX, m.GTV, sched, ws + W.GWREC, ws + W.GWPART, gp + mp.Wr, gp + mp.br, mixed));
     } else {
       NQ_TRY(nq_msg_rev(st, m, true));
     }
@@ -829,35 +770,15 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
     if (cfg->rbf_type)   // adjoints of rho / drho (shared by all layers): [gphi; gpsi] Wr, accumulated over the layers
       NQ_TRY(nq_gemm_nn(st, gphi, params + mp.Wr, ws + W.GRHO, 2 * E, 3 * F, R, 3 * F, R, R, l == L - 1 ? 0 : 1, "Wr"));
     if (!molgw) NQ_TRY(nq_colsum(sd, ws + W.GBR, N, 3 * F, 3 * F, gp + mp.br, scr));
-    if (!tn_group) NQ_TRY(nq_gemm_tn(sd, GXHs, ws + y.Hh, gp + mp.W2, 2L * N, 3 * F, F, 3 * F, F, scr, "W2", gp + mp.b2, N));
-    ss.read_by_side(SB_GPHI); ss.read_by_side(SB_GBR); if (!tn_group) ss.read_by_side(SB_GXH);
+    NQ_TRY(nq_gemm_tn(sd, GXHs, ws + y.Hh, gp + mp.W2, 2L * N, 3 * F, F, 3 * F, F, scr, "W2", gp + mp.b2, N));
+    ss.read_by_side(SB_GPHI); ss.read_by_side(SB_GBR); ss.read_by_side(SB_GXH);
     ss.before_main_writes(SB_GH);
-    NQ_TRY(nq_gemm_nn(st, GXHs, params + mp.W2, GHs, lite ? N : 2 * N, 3 * F, F, 3 * F, F, F, 0, "W2", pp.W2));
+    NQ_TRY(nq_gemm_nn(st, GXHs, params + mp.W2, GHs, lite ? N : 2 * N, 3 * F, F, 3 * F, F, F, 0, "W2"));
     NQ_TRY(nq_silu_rev(st, ws + y.Z1, ws + y.Z1 + NF, GHs, lite ? ws + y.LGHP : GHs + NF, (long)NF, true, lite));
     sd = ss.fork();
-    if (!tn_group) {
-      NQ_TRY(nq_gemm_tn(sd, GHs, ws + W.X[l], gp + mp.W1, 2L * N, F, F, F, F, scr, "W1", gp + mp.b1, N));
-      ss.read_by_side(SB_GH);
-    } else {
-      // all five weight-gradient products of the layer (and their bias gradients) in one launch: gy, gq, gu, gxh, gh are final and stay untouched until the
-      // next layer's kernels overwrite them (each of those waits for this launch through its before_main_writes)
-      NqTnSpec sp[5];
-      tn_group_shapes(sp, N, F);
-      sp[0].G = GYs; sp[0].X = ws + y.Q; sp[0].out = gp + up.V2; sp[0].bias_out = gp + up.c2;
-      sp[1].G = GQs; sp[1].X = ws + y.CAT; sp[1].out = gp + up.V1; sp[1].bias_out = gp + up.c1;
-      sp[2].G = GUs; sp[2].X = ws + y.VM; sp[2].out = gp + up.U;
-      sp[3].G = GXHs; sp[3].X = ws + y.Hh; sp[3].out = gp + mp.W2; sp[3].bias_out = gp + mp.b2;
-      sp[4].G = GHs; sp[4].X = ws + W.X[l]; sp[4].out = gp + mp.W1; sp[4].bias_out = gp + mp.b1;
-      if (nq_gemm_tn_group(sd, sp, 5, scr) != NQ_OK) {   // not eligible for the split engine (exact-f32 engine selected, unaligned operands): one launch each
-        NQ_TRY(nq_gemm_tn(sd, sp[0].G, sp[0].X, sp[0].out, 2L * N, 3 * F, F, 3 * F, F, scr, "V2", sp[0].bias_out, N));
-        NQ_TRY(nq_gemm_tn(sd, sp[1].G, sp[1].X, sp[1].out, 2L * N, F, 2 * F, F, 2 * F, scr, "V1", sp[1].bias_out, N));
-        NQ_TRY(nq_gemm_tn(sd, sp[2].G, sp[2].X, sp[2].out, 6L * N, 2 * F, F, 2 * F, F, scr, "U"));
-        NQ_TRY(nq_gemm_tn(sd, sp[3].G, sp[3].X, sp[3].out, 2L * N, 3 * F, F, 3 * F, F, scr, "W2", sp[3].bias_out, N));
-        NQ_TRY(nq_gemm_tn(sd, sp[4].G, sp[4].X, sp[4].out, 2L * N, F, F, F, F, scr, "W1", sp[4].bias_out, N));
-      }
-      ss.read_by_side(SB_GY); ss.read_by_side(SB_GQ); ss.read_by_side(SB_GU); ss.read_by_side(SB_GXH); ss.read_by_side(SB_GH);
-    }
-    NQ_TRY(nq_gemm_nn(st, GHs, params + mp.W1, ws + W.GX, lite ? N : 2 * N, F, F, F, F, F, 1, "W1", pp.W1));
+    NQ_TRY(nq_gemm_tn(sd, GHs, ws + W.X[l], gp + mp.W1, 2L * N, F, F, F, F, scr, "W1", gp + mp.b1, N));
+    ss.read_by_side(SB_GH);
+    NQ_TRY(nq_gemm_nn(st, GHs, params + mp.W1, ws + W.GX, lite ? N : 2 * N, F, F, F, F, F, 1, "W1"));
     // every gradient slice of layer l (and, for l = L-1, of the read-out head) is final once the weight-gradient stream gets here: the caller's
     // collective stream may start reducing it
     if (layer_events && layer_events[L - 1 - l]) NQ_HIP(hipEventRecord((hipEvent_t)layer_events[L - 1 - l], ss.on ? ss.side : st));

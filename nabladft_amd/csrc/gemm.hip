@@ -459,9 +459,6 @@ static int launch_gemm3(hipStream_t st, const GemmArgs& p, int splits) {
     const dim3 gt((unsigned)(tiles < 256 * WT ? tiles : 256 * WT));
     hipLaunchKernelGGL((k_gemm3<A_KC, B_KC, EPI, WT, true>), gt, dim3(256), 0, st, p);
   } else {
-    if constexpr (A_KC && !B_KC) {   // input-gradient layout: the weight operand may come pre-split (GemmArgs::Bpre)
-      if (p.Bpre) { hipLaunchKernelGGL((k_gemm3<A_KC, B_KC, EPI, WPE, false, false, NQ_GEMM3_TERMS, 0, false, true>), grid, dim3(256), 0, st, p); return NQ_OK; }
-    }
     hipLaunchKernelGGL((k_gemm3<A_KC, B_KC, EPI, WPE, false>), grid, dim3(256), 0, st, p);
   }
   return NQ_OK;
@@ -717,16 +714,15 @@ int nq_gemm_nt_res(hipStream_t st, const float* A, const float* W, float* C, con
 
 // C[M, Kin] (+)= G[M, Nout] * W[Nout, Kin]
 int nq_gemm_nn(hipStream_t st, const float* G, const float* W, float* C, int M, int Nout, int Kin, int ldg, int ldw, int ldc,
-               int accumulate, const char* tag, const void* Bpre) {
+               int accumulate, const char* tag) {
   char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nn:%s[n=%d,k=%d]", tag ? tag : "", Kin, Nout); else nm__[0] = 0;
   NQ_PROF(st, nm__);
   NQ_PROF_FLOPS(2.0 * M * Nout * Kin);
   if (M <= 0) return NQ_OK;
   GemmArgs p{G, W, C, nullptr, nullptr, M, Kin, Nout, ldg, ldw, ldc, 0, 0, nullptr, 0};
-  if (Bpre && !(Kin & 127) && !(Nout & 15) && ldw == Kin) { p.Bpre = Bpre; p.ldbpre = Nout; p.bpre_plane_bytes = Kin * Nout * 2; }
   {
     int rc;
-    if (!p.Bpre && try_splitk<true, false>(st, p, nullptr, accumulate, rc)) { NQ_TRY(rc); NQ_LAUNCH_CHECK(); return NQ_OK; }
+    if (try_splitk<true, false>(st, p, nullptr, accumulate, rc)) { NQ_TRY(rc); NQ_LAUNCH_CHECK(); return NQ_OK; }
   }
   if (gemm3_ok<true, false>(p, Nout, 1)) {
     if (accumulate) NQ_TRY((launch_gemm3<true, false, EPI_ACC>(st, p, 1)));
@@ -755,15 +751,13 @@ int nq_gemm_nn(hipStream_t st, const float* G, const float* W, float* C, int M, 
 }
 
 // C[M, Kin] = epilogue(G[M, Nout] * W[Nout, Kin]): mode 1: eb * v * silu'(aux), mode 2: ea * aux + v   (aux [M, Kin])
-int nq_gemm_nn_epi(hipStream_t st, const float* G, const float* W, float* C, int M, int Nout, int Kin, const float* aux, float ea, float eb, int mode, const char* tag,
-                   const void* Bpre) {
+int nq_gemm_nn_epi(hipStream_t st, const float* G, const float* W, float* C, int M, int Nout, int Kin, const float* aux, float ea, float eb, int mode, const char* tag) {
   char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nn:%s[n=%d,k=%d]", tag ? tag : "", Kin, Nout); else nm__[0] = 0;
   NQ_PROF(st, nm__);
   NQ_PROF_FLOPS(2.0 * M * Nout * Kin);
   if (M <= 0) return NQ_OK;
   GemmArgs p{G, W, C, nullptr, nullptr, M, Kin, Nout, Nout, Kin, Kin, 0, 0, nullptr, 0};
   p.resid = aux; p.ea = ea; p.eb = eb;
-  if (Bpre && !(Kin & 127) && !(Nout & 15)) { p.Bpre = Bpre; p.ldbpre = Nout; p.bpre_plane_bytes = Kin * Nout * 2; }
   if (gemm3_ok<true, false>(p, Nout, 1)) {
     if (mode == 1) NQ_TRY((launch_gemm3<true, false, EPI_DSILU>(st, p, 1)));
     else NQ_TRY((launch_gemm3<true, false, EPI_RES>(st, p, 1)));
@@ -791,14 +785,13 @@ int nq_gemm_nn_epi(hipStream_t st, const float* G, const float* W, float* C, int
 
 // C = G W (the adjoint of a SiLU layer's OUTPUT) and C2 = C * silu'(aux) (the adjoint of its pre-activation) in one pass: the force sweep keeps both, because the
 // second-order sweep needs the first for its silu'' term and the second as an operand of the weight gradient (engine.hip: per-layer adjoint store)
-int nq_gemm_nn_dsilu2(hipStream_t st, const float* G, const float* W, float* C, float* C2, const float* aux, int M, int Nout, int Kin, const char* tag, const void* Bpre) {
+int nq_gemm_nn_dsilu2(hipStream_t st, const float* G, const float* W, float* C, float* C2, const float* aux, int M, int Nout, int Kin, const char* tag) {
   char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nn:%s[n=%d,k=%d]", tag ? tag : "", Kin, Nout); else nm__[0] = 0;
   NQ_PROF(st, nm__);
   NQ_PROF_FLOPS(2.0 * M * Nout * Kin);
   if (M <= 0) return NQ_OK;
   GemmArgs p{G, W, C, nullptr, C2, M, Kin, Nout, Nout, Kin, Kin, 0, 0, nullptr, 0};
   p.resid = aux; p.ea = 0.f; p.eb = 1.f;
-  if (Bpre && !(Kin & 127) && !(Nout & 15)) { p.Bpre = Bpre; p.ldbpre = Nout; p.bpre_plane_bytes = Kin * Nout * 2; }
   if (gemm3_ok<true, false>(p, Nout, 1)) NQ_TRY((launch_gemm3<true, false, EPI_DSILU2>(st, p, 1)));
   else if (gemm2_ok<true, false>(p, Nout)) launch_gemm2<true, false, EPI_DSILU2>(st, p, 1);
   else if (gemm_is_small(M, Kin) && !(g_gemm_variant & 8)) hipLaunchKernelGGL((k_gemm_small<false, EPI_DSILU2>), dim3(nq_cdiv(M, SM), nq_cdiv(Kin, SM), 1), dim3(256), 0, st, p);
@@ -864,130 +857,6 @@ int nq_gemm_tn(hipStream_t st, const float* GY, const float* X, float* out, long
   } else {
     LAUNCH_REDUCE_PARTIALS(st, scratch, nse, cnt, cnt, out);
   }
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
-}
-
-// ---- weights pre-split for the input-gradient products (GemmArgs::Bpre) -----------------------------------------------------------------------
-// W [Kc][N] row-major (Kc = the contracted index of C = G W) -> planes [piece][N][Kc] bf16, Kc-contiguous: what PreStageB (gemm_split.h) loads
-struct PresplitArgs { const float* W[5]; int Kc[5]; int N[5]; unsigned short* out[5]; int first[6]; int n; };
-__global__ __launch_bounds__(256) void k_presplit_kn(PresplitArgs a) {
-  const int b = (int)blockIdx.x;
-  int g = 0;
-#pragma unroll
-  for (int i = 1; i < 5; ++i) g += (i < a.n && b >= a.first[i]) ? 1 : 0;
-  const float* W = nullptr; int Kc = 0, N = 0, first = 0; unsigned short* out = nullptr;
-#pragma unroll
-  for (int i = 0; i < 5; ++i)
-    if (g == i) { W = a.W[i]; Kc = a.Kc[i]; N = a.N[i]; out = a.out[i]; first = a.first[i]; }
-  const long idx = (long)(b - first) * 256 + threadIdx.x;     // (n, k octet), n fastest: coalesced reads of W rows
-  const int n = (int)(idx % N), oct = (int)(idx / N);
-  if (oct >= Kc / 8) return;
-  float v[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = W[(long)(oct * 8 + i) * N + n];
-  unsigned h[4], m[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) sp_split2(v[2 * i], v[2 * i + 1], h[i], m[i], l[i]);
-  const long plane = (long)N * Kc;
-  gemm_u32x4* o = reinterpret_cast<gemm_u32x4*>(out + (long)n * Kc + oct * 8);
-  *o = gemm_u32x4{h[0], h[1], h[2], h[3]};
-  *reinterpret_cast<gemm_u32x4*>(out + plane + (long)n * Kc + oct * 8) = gemm_u32x4{m[0], m[1], m[2], m[3]};
-  *reinterpret_cast<gemm_u32x4*>(out + 2 * plane + (long)n * Kc + oct * 8) = gemm_u32x4{l[0], l[1], l[2], l[3]};
-}
-// up to five matrices in one launch; out[i]: 3 * Kc[i] * N[i] bf16 (16-byte aligned)
-int nq_gemm_presplit_kn(hipStream_t st, int n, const float* const* W, const int* Kc, const int* N, void* const* out) {
-  if (n < 1 || n > 5) return nq_fail(NQ_ERR_ARG, "presplit: 1-5 matrices");
-  NQ_PROF(st, "gemm_presplit");
-  PresplitArgs a{};
-  int blocks = 0;
-  for (int i = 0; i < 5; ++i) {
-    a.first[i] = blocks;
-    if (i >= n) continue;
-    if ((Kc[i] & 7) || !W[i] || !out[i]) return nq_fail(NQ_ERR_ARG, "presplit: bad matrix %d", i);
-    a.W[i] = W[i]; a.Kc[i] = Kc[i]; a.N[i] = N[i]; a.out[i] = reinterpret_cast<unsigned short*>(out[i]);
-    blocks += nq_cdiv((long)N[i] * (Kc[i] / 8), 256);
-  }
-  a.first[5] = blocks; a.n = n;
-  hipLaunchKernelGGL(k_presplit_kn, dim3(blocks), dim3(256), 0, st, a);
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
-}
-
-// ---- several weight-gradient products in one launch (k_gemm3_tn_group, gemm_split.h) + one reduction of all their partial tiles ----------------
-#define RG_MAX (2 * GEMM_GROUP_MAX)
-struct ReduceGroupArgs { const float* part[RG_MAX]; float* out[RG_MAX]; int nsplit[RG_MAX]; int count[RG_MAX]; int first[RG_MAX + 1]; int n; };
-__global__ __launch_bounds__(256) void k_reduce_partials_group(ReduceGroupArgs q) {
-  const int b = (int)blockIdx.x;
-  int g = 0;
-#pragma unroll
-  for (int i = 1; i < RG_MAX; ++i) g += (i < q.n && b >= q.first[i]) ? 1 : 0;
-  // static member indices only (see k_gemm3_tn_group)
-  const float* part = nullptr; float* out = nullptr; int nsplit = 0, count = 0, first = 0;
-#pragma unroll
-  for (int i = 0; i < RG_MAX; ++i)
-    if (g == i) { part = q.part[i]; out = q.out[i]; nsplit = q.nsplit[i]; count = q.count[i]; first = q.first[i]; }
-  reduce_partials_body(part, nsplit, (long)count, (long)count, out, (long)(b - first));   // same combination order as k_reduce_partials
-}
-
-static const int TN_GROUP_SLOTS = 512;   // 2 workgroups per CU (the bias-gradient flavour of the split engine)
-struct TnGroupPlan { int ns[GEMM_GROUP_MAX], kper[GEMM_GROUP_MAX], nse[GEMM_GROUP_MAX]; size_t off[GEMM_GROUP_MAX], boff[GEMM_GROUP_MAX], total; };
-static void tn_group_plan(const NqTnSpec* sp, int n, TnGroupPlan* P) {
-  double wsum = 0.0;
-  long tiles[GEMM_GROUP_MAX];
-  for (int g = 0; g < n; ++g) { tiles[g] = (long)nq_cdiv(sp[g].Mo, 128) * nq_cdiv(sp[g].No, 128); wsum += (double)sp[g].rows * tiles[g]; }
-  size_t o = 0;
-  for (int g = 0; g < n; ++g) {
-    long s = (long)(TN_GROUP_SLOTS * ((double)sp[g].rows * tiles[g] / (wsum > 0 ? wsum : 1.0)) / tiles[g]);   // slots in proportion to rows x tiles, floor: never more than the slots
-    const long by_rows = (sp[g].rows + 127) / 128;
-    if (s > by_rows) s = by_rows;
-    if (s < 1) s = 1;
-    int kper = (int)((sp[g].rows + s - 1) / s);
-    kper = (kper + 31) / 32 * 32;
-    P->ns[g] = (int)s; P->kper[g] = kper; P->nse[g] = nq_cdiv(sp[g].rows, kper);
-    P->off[g] = o; o += (size_t)s * sp[g].Mo * sp[g].No;
-    P->boff[g] = o; o += sp[g].bias_out ? (size_t)s * sp[g].Mo : 0;
-    o = (o + 3) & ~(size_t)3;
-  }
-  P->total = o;
-}
-size_t nq_gemm_tn_group_scratch_floats(const NqTnSpec* sp, int n) {
-  if (n < 1 || n > GEMM_GROUP_MAX) return 0;
-  TnGroupPlan P;
-  tn_group_plan(sp, n, &P);
-  return P.total;
-}
-// All products through the split engine in one launch + one reduction; returns NQ_ERR_ARG (nothing launched) when a product is not eligible
-// (the caller then issues them one by one with nq_gemm_tn).
-int nq_gemm_tn_group(hipStream_t st, const NqTnSpec* sp, int n, float* scratch) {
-  if (n < 1 || n > GEMM_GROUP_MAX || gemm3_disabled()) return nq_fail(NQ_ERR_ARG, "gemm_tn_group: not eligible");
-  TnGroupPlan P;
-  tn_group_plan(sp, n, &P);
-  GemmGroupArgs q{};
-  ReduceGroupArgs r{};
-  int wg = 0, rb = 0, nr = 0;
-  double flops = 0.0;
-  for (int g = 0; g < GEMM_GROUP_MAX; ++g) {
-    q.first[g] = wg;
-    if (g >= n) continue;
-    const NqTnSpec& x = sp[g];
-    if (x.rows <= 0 || x.rows > 2000000000L) return nq_fail(NQ_ERR_ARG, "gemm_tn_group: bad row count");
-    float* bpart = x.bias_out ? scratch + P.boff[g] : nullptr;
-    q.a[g] = GemmArgs{x.G, x.X, scratch + P.off[g], nullptr, nullptr, x.Mo, x.No, (int)x.rows, x.ldg, x.ldx, x.No, P.kper[g], (long)x.Mo * x.No, bpart, (int)x.bias_rows};
-    if (!gemm3_ok<false, false>(q.a[g], P.kper[g], P.nse[g])) return nq_fail(NQ_ERR_ARG, "gemm_tn_group: product %d is not eligible for the split engine", g);
-    wg += nq_cdiv(x.Mo, 128) * nq_cdiv(x.No, 128) * P.nse[g];
-    flops += 2.0 * x.rows * x.Mo * x.No;
-    r.part[nr] = scratch + P.off[g]; r.out[nr] = x.out; r.nsplit[nr] = P.nse[g]; r.count[nr] = x.Mo * x.No; r.first[nr] = rb; rb += (int)reduce_partials_blocks(P.nse[g], (long)x.Mo * x.No); ++nr;
-    if (x.bias_out) { r.part[nr] = bpart; r.out[nr] = x.bias_out; r.nsplit[nr] = P.nse[g]; r.count[nr] = x.Mo; r.first[nr] = rb; rb += (int)reduce_partials_blocks(P.nse[g], (long)x.Mo); ++nr; }
-  }
-  q.first[GEMM_GROUP_MAX] = wg; q.n = n;
-  for (int i = nr; i <= RG_MAX; ++i) r.first[i] = rb;
-  r.n = nr;
-  NQ_PROF(st, "gemm_tn_group");
-  NQ_PROF_FLOPS(flops);
-  hipLaunchKernelGGL(k_gemm3_tn_group<0>, dim3(wg), dim3(256), 0, st, q);
-  NQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_reduce_partials_group, dim3(rb), dim3(256), 0, st, r);
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }

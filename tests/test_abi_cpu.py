@@ -77,6 +77,32 @@ def test_workspace_and_lookup(lib):
         del os.environ["NQ_NO_FUSED_FILTER"]
 
 
+def test_backward_refuses_a_workspace_no_forward_has_prepared(lib):
+    """The backward calls follow the plan that nq_painn_forward recorded for the workspace; without one they fail with NQ_ERR_ARG before any device work
+    (so this runs on a host without a GPU).  Skipped where a device is visible: a regression must not enqueue work on host buffers of a shared GPU."""
+    if torch.cuda.is_available():
+        pytest.skip("host-only check: a device is visible")
+    import nabladft_amd as nq
+    from nabladft_amd import _lib
+    m = nq.PaiNN(64, 2, 20, 3.0, 6, {"name": "gaussian"}, {"name": "polynomial", "exponent": 5}, True, False, False, True, 100)
+    cfg = C.byref(m._cfg)
+    N, E, B = 100, 900, 4
+    ws_bytes = lib.nq_painn_workspace_bytes(cfg, N, E, B)
+    assert ws_bytes > 0
+    ws = (C.c_char * (ws_bytes + 16))()
+    ws_ptr = (C.addressof(ws) + 15) // 16 * 16
+    host = (C.c_float * 4096)()                                # stands in for every device array: nothing may read it
+    dummy = C.addressof(host)
+    g = _lib.Graph()
+    g.N, g.B, g.E, g.max_mol_atoms = N, B, E, 30
+    for f in ("mol_ptr", "row_ptr", "col", "dst", "rev", "geom", "z", "atom_mol", "lowptr"):
+        setattr(g, f, dummy)
+    assert lib.nq_painn_backward(cfg, dummy, dummy, C.byref(g), ws_ptr, ws_bytes, dummy, dummy, dummy, None) == 2       # NQ_ERR_ARG
+    assert b"no forward call has prepared this workspace" in lib.nq_last_error()
+    assert lib.nq_painn_backward_seeded(cfg, dummy, dummy, C.byref(g), ws_ptr, ws_bytes, dummy, None, None, dummy, None) == 2
+    assert b"no forward call has prepared this workspace" in lib.nq_last_error()
+
+
 def test_unsupported_configs_fail_loudly():
     import nabladft_amd as nq
     kw = dict(rbf={"name": "gaussian"}, envelope={"name": "polynomial", "exponent": 5}, regress_forces=True, direct_forces=False,

@@ -521,21 +521,17 @@ def test_second_order_sweep_with_stored_tangent_adjoints_equals_the_full_dual_sw
         assert float(np.abs(a - b).max()) <= 2e-5 * max(float(np.abs(b).max()), 1e-30), k
 
 
-@pytest.mark.parametrize("mode", ["unfused", "fused_forward", "fused_forward_and_tangent", "fused_forward_and_force_adjoint"])
+@pytest.mark.parametrize("mode", ["unfused", "fused_forward"])
 def test_update_block_flavours_agree_with_the_reference(mode, monkeypatch):
-    """csrc/updfuse.hip: the update block of a layer as ONE kernel per sweep (hidden_channels = 128) against the five launches it replaces and against the
-    reference golden vectors of the full configuration: energies, forces, loss and every parameter gradient within the bounds of
-    test_engine_matches_reference_golden, for the default (fused forward sweep), the opt-in fused tangent and force-adjoint sweeps and the unfused path; the fused
-    kernels are seen by the profiler when and only when they are selected."""
+    """csrc/updfuse.hip: the update block of a layer's forward sweep as ONE kernel (hidden_channels = 128) against the five launches it replaces and against
+    the reference golden vectors of the full configuration: energies, forces, loss and every parameter gradient within the bounds of
+    test_engine_matches_reference_golden, for the default (fused forward sweep) and the unfused path; the fused kernel is seen by the profiler when and only
+    when it is selected."""
     import nabladft_amd as nq
     from nabladft_amd import L2Loss
-    monkeypatch.delenv("NQ_NO_FUSED_UPDATE", raising=False); monkeypatch.delenv("NQ_FUSED_UPDATE_TAN", raising=False); monkeypatch.delenv("NQ_FUSED_UPDATE_REV", raising=False)
-    if mode == "fused_forward_and_force_adjoint":
-        monkeypatch.setenv("NQ_FUSED_UPDATE_REV", "1")
+    monkeypatch.delenv("NQ_NO_FUSED_UPDATE", raising=False)
     if mode == "unfused":
         monkeypatch.setenv("NQ_NO_FUSED_UPDATE", "1")
-    if mode == "fused_forward_and_tangent":
-        monkeypatch.setenv("NQ_FUSED_UPDATE_TAN", "1")
     dev = _dev()
     fx, cfg, params = load_case("painn_full_real4.npz")
     assert cfg.hidden_channels == 128
@@ -552,9 +548,8 @@ def test_update_block_flavours_agree_with_the_reference(mode, monkeypatch):
         loss.backward()
         out["e"], out["f"], out["loss"] = energy.detach(), forces.detach(), float(loss.detach())
     names = _kernel_names_of(run)
-    assert ("upd_fused" in names) == (mode != "unfused") and ("upd_fused_tan" in names) == (mode == "fused_forward_and_tangent"), names
-    assert ("upd_a" in names) == (mode != "fused_forward_and_tangent"), names       # the tangent sweep of the default still runs the five launches
-    assert ("updrev_fused" in names) == (mode == "fused_forward_and_force_adjoint"), names
+    assert ("upd_fused" in names) == (mode != "unfused"), names
+    assert "upd_a" in names, names                                                  # the tangent sweep runs the five launches either way
     assert_close(f"update block {mode} E", out["e"].cpu().numpy(), fx["energy"], 1e-5)
     assert_close(f"update block {mode} F", out["f"].cpu().numpy(), fx["forces"], 1e-5)
     assert abs(out["loss"] - float(fx["loss"])) < 1e-5 * abs(float(fx["loss"]))
@@ -562,6 +557,70 @@ def test_update_block_flavours_agree_with_the_reference(mode, monkeypatch):
     e1, f1 = out["e"].clone(), out["f"].clone()
     run()
     assert torch.equal(e1, out["e"]) and torch.equal(f1, out["f"])                  # deterministic
+
+
+def test_backward_follows_the_plan_of_its_forward_call(monkeypatch):
+    """Every path choice of a training step is made by nq_painn_forward and recorded for the workspace: switches changed between the forward and the backward
+    call leave the gradients bitwise unchanged, and a backward call with the graph of another batch is refused (NQ_ERR_ARG) before any device work."""
+    import nabladft_amd as nq
+    from nabladft_amd import L2Loss, _lib
+    lib = _lib.load()
+    dev = _dev()
+    fx, cfg, params = load_case("painn_full_real4.npz")
+    model = _model(cfg, params, dev)
+    batch = _batch(fx, dev)
+    keep = fx["batch"] < fx["batch"].max()                     # another batch: the same conformers but the last
+    other = nq.Batch(torch.tensor(fx["pos"][keep]), torch.tensor(fx["z"][keep]), torch.tensor(fx["batch"][keep])).to(dev)
+    model.train()
+    switches = ("NQ_NO_FUSED_FILTER", "NQ_NO_MOLGW", "NQ_MOLGW", "NQ_MOLGW_CAP", "NQ_NO_LITE")
+
+    def step(forward_env, backward_env):
+        for k in switches:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in forward_env.items():
+            monkeypatch.setenv(k, v)
+        for p in model.parameters():
+            p.grad = None
+        energy, forces = model(batch)
+        loss = torch.nn.L1Loss()(energy, batch.y) + L2Loss()(forces, batch.forces)
+        for k in switches:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in backward_env.items():
+            monkeypatch.setenv(k, v)
+        loss.backward()
+        return {k: p.grad.detach().clone() for k, p in model.named_parameters()}
+
+    flipped = {"NQ_NO_FUSED_FILTER": "1", "NQ_NO_MOLGW": "1", "NQ_MOLGW_CAP": "4", "NQ_NO_LITE": "1"}
+    refs = []
+    for forward_env, backward_env in (({}, {**flipped, "NQ_MOLGW": "1"}),                          # pair rows, stored adjoints
+                                      ({"NQ_MOLGW": "1"}, flipped),                                # per-molecule rbf_proj gradient
+                                      ({"NQ_MOLGW": "1", "NQ_MOLGW_CAP": "4"}, flipped)):          # mixed batch
+        ref = step(forward_env, forward_env)
+        got = step(forward_env, backward_env)
+        refs.append(ref)
+        for k in ref:
+            assert torch.equal(ref[k], got[k]), (forward_env, k)
+    check_grads(fx, {k: g.cpu().numpy() for k, g in got.items()}, 5e-5, "plan of the forward call")
+    for k in switches:
+        monkeypatch.delenv(k, raising=False)
+
+    with torch.no_grad():
+        model(other)
+    nl_other = model._last_nl
+    g_other = nl_other.c
+    energy, forces = model(batch)                              # the same cached workspace, now prepared for `batch`
+    ws, nl = model._last_ws, model._last_nl
+    assert (g_other.N, g_other.E, g_other.B) != (nl.c.N, nl.c.E, nl.c.B)
+    grad = torch.empty_like(model._flat)
+    rc = lib.nq_painn_backward(C.byref(model._cfg), _lib.ptr(model._flat), _lib.ptr(model.radial_basis.engine_buffer()), C.byref(g_other), _lib.ptr(ws),
+                               ws.numel(), None, None, _lib.ptr(grad), _lib.stream_ptr())
+    assert rc == 2 and b"different model or batch" in lib.nq_last_error()
+    loss = torch.nn.L1Loss()(energy, batch.y) + L2Loss()(forces, batch.forces)
+    for p in model.parameters():
+        p.grad = None
+    loss.backward()                                            # the refused call left the step intact
+    for k, p in model.named_parameters():
+        assert torch.equal(p.grad, refs[0][k]), k
 
 
 def test_fused_step_matches_golden_and_is_deterministic():
