@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) void k_gn_quad_bwd_x_atom(GnSet M, GnSet Q, co
   const int a = blockIdx.x, tid = threadIdx.x;
   const int ob = M.ptr[a], on = M.ptr[a + 1] - ob, qb = Q.ptr[a], qe = Q.ptr[a + 1];
   const int PC = min(8, 256 / C);
-  const int NPASS = GQ_PB / PC;                          // <= 8
+  const int NPASS = (GQ_PB + PC - 1) / PC;               // every row of the block (PC = 5..7 does not divide 32); <= 8 since PC >= 4 for C <= 64
   const int pl = tid / C, ch = tid - pl * C;
   const bool active = pl < PC;
   for (int q = qb; q < qe; ++q) {

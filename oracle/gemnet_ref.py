@@ -120,6 +120,14 @@ def zonal(z, ns):
     return torch.stack([math.sqrt((2 * l + 1) / (4 * math.pi)) * P[l] for l in range(ns)], dim=1)
 
 
+def quad_basis(V_ca, V_ba, V_db, ns):
+    """The two factors of the quadruplet basis (gemnet_oc.py:597-655), unscaled: Y_l(cos cab) and Y_l'(cos of the dihedral half angle between the
+    planes (c, a, b) and (d, b, a)); the atan2 argument is floored at 1e-9 as in the reference.  Unit vectors [n, 3] -> ([n, ns], [n, ns])."""
+    ca_x, db_x = torch.cross(V_ca, V_ba, dim=-1), torch.cross(V_db, V_ba, dim=-1)
+    ang = torch.atan2(torch.cross(ca_x, db_x, dim=-1).norm(dim=-1).clamp(min=1e-9), (ca_x * db_x).sum(-1))
+    return zonal((V_ca * V_ba).sum(-1).clamp(-1, 1), ns), zonal(torch.cos(ang), ns)
+
+
 def _sf(P, key):
     v = float(P[key])
     return v if v != 0.0 else 1.0                                   # ScaleFactor: 0 = not fitted = identity (scale_factor.py:66-68,146-149)
@@ -197,9 +205,8 @@ def forward(P, cfg, pos, z, sizes, want=None):
     # quadruplets: cos(abd) on the (qint, main-in) pair, cos(cab) and the dihedral half angle on the full quadruplet (gemnet_oc.py:597-655)
     V_ba, V_db, V_ca = vq[qq], vm[qp], vm[qo]
     Y_abd = zonal(clamp((V_ba * V_db).sum(-1)), ns) * sc("cbf_basis_qint", "cbf")
-    ca_x, db_x = torch.cross(V_ca, V_ba, dim=-1), torch.cross(V_db, V_ba, dim=-1)
-    ang = torch.atan2(torch.cross(ca_x, db_x, dim=-1).norm(dim=-1).clamp(min=1e-9), (ca_x * db_x).sum(-1))
-    Y_quad = (zonal(clamp((V_ca * V_ba).sum(-1)), ns)[:, :, None] * zonal(torch.cos(ang), ns)[:, None, :]).reshape(len(qo), -1) * sc("sbf_basis_qint", "sbf")
+    Y_cab, Y_dih = quad_basis(V_ca, V_ba, V_db, ns)
+    Y_quad = (Y_cab[:, :, None] * Y_dih[:, None, :]).reshape(len(qo), -1) * sc("sbf_basis_qint", "sbf")
     # shared embeddings of the radial parts (gemnet_oc.py:1048-1103)
     W3 = lambda k: P[k + ".weight"].reshape(P[k + ".weight"].shape[0], -1)      # noqa: E731
     base = {"e2e_rad": dense(P, "mlp_rbf_tint", rad_main), "e2e_cir": rad_sph @ W3("mlp_cbf_tint"),
