@@ -582,7 +582,8 @@ int nq_es_frames(const float* geom, int32_t E, float* rot, void* stream) {
   return NQ_OK;
 }
 /* rot [E][3][3] -> W [E][n_red][n_full]; J: the (2l+1)^2 matrices of l = 0..lmax back to back, J_offset[l] their starts; red_l / red_row [n_red]: degree and
- * row inside the degree's block of every kept coefficient (in the order the caller wants them, e.g. m-primary); scratch: f32[3 E]. */
+ * row inside the degree's block of every kept coefficient (in the order the caller wants them, e.g. m-primary); scratch: f64[3 E] (the Euler angles), 8-byte
+ * aligned. */
 int nq_es_wigner(const float* rot, int32_t E, const float* J, const int32_t* J_offset, const int32_t* red_l, const int32_t* red_row, int32_t n_red, int32_t n_full,
                  int32_t lmax, float* scratch, float* W, void* stream) {
   hipStream_t st = (hipStream_t)stream;

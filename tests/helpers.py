@@ -1,7 +1,9 @@
 """Shared helpers for the parity tests (test infrastructure)."""
+import ctypes as C
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import painn_ref as R
@@ -107,3 +109,103 @@ def assert_parity(name, got, ref64, ref32=None, floor=PARITY_FLOOR, factor=1.5):
         assert err <= bound, (name, err, own, bound)
         assert err_el <= bound_el, (name, "element-wise", err_el, own_el, bound_el)
     return err, own
+
+
+# ---- the C-ABI operator tests (test_*_ops_gpu.py): each entry point called through ctypes on device buffers --------------------------------------------
+DEV = "cuda:0"
+NAN = float("nan")
+
+
+def _lib():
+    from nabladft_amd import _lib
+    return _lib
+
+
+def lib():
+    return _lib().load()
+
+
+def st():
+    return _lib().stream_ptr()
+
+
+def P(t):
+    return _lib().ptr(t)
+
+
+_LIVE = []
+
+
+def D(t):
+    """Device pointer of a device copy of t.  The copy is kept until the end of the test: a bare pointer does not hold the memory, and the caching
+    allocator would hand a dropped temporary to the next argument of the same call."""
+    d = t.to(DEV)
+    _LIVE.append(d)
+    return P(d)
+
+
+@pytest.fixture(autouse=True)
+def _release_copies():
+    """Autouse in every module that imports it: drops the copies D() kept once the test's kernels have finished."""
+    yield
+    torch.cuda.synchronize()
+    _LIVE.clear()
+
+
+def check(rc):
+    _lib().check(rc)
+
+
+def rel(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if b.size == 0:
+        return 0.0
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+def assert_sum(name, got, ref64, ref32):
+    """got: device tensor written by a kernel; ref64 / ref32: the same formula in float64 / float32 on the CPU."""
+    g = got.detach().cpu().double().numpy()
+    nan = np.isnan(g)
+    assert not nan.any(), f"{name}: {int(nan.sum())} of {g.size} elements never written"
+    r64 = ref64.detach().double().numpy()
+    err, own = rel(g, r64), rel(ref32.detach().double().numpy(), r64)
+    assert err <= max(3 * own, 2e-6) and err < 1e-5, (name, err, own)
+    return err
+
+
+def rnd(gen, *shape):
+    return torch.randn(*shape, generator=gen, dtype=torch.float32)
+
+
+def nan_dev(*shape):
+    return torch.full(shape, NAN, device=DEV, dtype=torch.float32)
+
+
+def i32(a):
+    return torch.as_tensor(np.asarray(a), dtype=torch.int32)
+
+
+def host_i32(v):
+    return (C.c_int32 * len(v))(*[int(x) for x in v])
+
+
+def host_ptrs(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def twice(call):
+    """Runs ``call`` (which returns the tensors its kernels wrote into fresh buffers) twice; the two results must be bitwise equal."""
+    a, b = call(), call()
+    torch.cuda.synchronize()
+    for x, y in zip(a, b):
+        assert torch.equal(x.cpu().view(torch.int32) if x.dtype == torch.float32 else x.cpu(), y.cpu().view(torch.int32) if y.dtype == torch.float32 else y.cpu())
+    return a
+
+
+def rejected(call, *untouched):
+    with pytest.raises(_lib().NablaqError):
+        check(call())
+    torch.cuda.synchronize()
+    for t in untouched:
+        assert torch.isnan(t).all()

@@ -18,74 +18,7 @@ sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
 
 from oracle import gemnet_ref as R  # noqa: E402
-
-DEV = "cuda:0"
-NAN = float("nan")
-
-
-def _lib():
-    from nabladft_amd import _lib
-    return _lib
-
-
-def lib():
-    return _lib().load()
-
-
-def st():
-    return _lib().stream_ptr()
-
-
-def P(t):
-    return _lib().ptr(t)
-
-
-_LIVE = []
-
-
-def D(t):
-    """Device pointer of a device copy of t.  The copy is kept until the end of the test: a bare pointer does not hold the memory, and the caching
-    allocator would hand a dropped temporary to the next argument of the same call."""
-    d = t.to(DEV)
-    _LIVE.append(d)
-    return P(d)
-
-
-@pytest.fixture(autouse=True)
-def _release_copies():
-    yield
-    torch.cuda.synchronize()
-    _LIVE.clear()
-
-
-def check(rc):
-    _lib().check(rc)
-
-
-def rel(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    if b.size == 0:
-        return 0.0
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def assert_sum(name, got, ref64, ref32):
-    """got: device tensor written by a kernel; ref64 / ref32: the same formula in float64 / float32 on the CPU."""
-    g = got.detach().cpu().double().numpy()
-    nan = np.isnan(g)
-    assert not nan.any(), f"{name}: {int(nan.sum())} of {g.size} elements never written"
-    r64 = ref64.detach().double().numpy()
-    err, own = rel(g, r64), rel(ref32.detach().double().numpy(), r64)
-    assert err <= max(3 * own, 2e-6) and err < 1e-5, (name, err, own)
-    return err
-
-
-def rnd(gen, *shape):
-    return torch.randn(*shape, generator=gen, dtype=torch.float32)
-
-
-def nan_dev(*shape):
-    return torch.full(shape, NAN, device=DEV, dtype=torch.float32)
+from tests.helpers import DEV, D, P, _lib, _release_copies, assert_sum, check, lib, nan_dev, rnd, st  # noqa: E402,F401  (_release_copies: autouse)
 
 
 # ---- graphs -------------------------------------------------------------------------------------------------------------------------------------------
