@@ -287,13 +287,15 @@ __global__ __launch_bounds__(256) void k_qh_gate(const float* __restrict__ x, co
 // y = cst * act(x) (gy == null) or gx = gy * cst * act'(x); kind 0 = SiLU, 1 = shifted softplus (layers.py:21-22) -- the activations of
 // e3nn's FullyConnectedNet (cst = its second-moment normalisation) and of the torch.nn.Sequential heads
 __device__ __forceinline__ float qh_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+// softplus': below -80 the quotient 1 / (1 + e^-x) meets e^-x = inf from -88.7 on and returns 0; there 1 + e^x rounds to 1, so the derivative is e^x itself
+__device__ __forceinline__ float qh_dsoftplus(float x) { return x < -80.f ? expf(x) : nq_sigmoid(x); }
 __global__ __launch_bounds__(256) void k_qh_act(const float* __restrict__ x, const float* __restrict__ gy, int kind, float cst, long count, float* __restrict__ out) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   const float v = x[i];
   float o;
   if (!gy) o = cst * (kind == 0 ? nq_silu(v) : qh_softplus(v) - 0.69314718055994530942f);
-  else o = gy[i] * cst * (kind == 0 ? nq_dsilu(v) : nq_sigmoid(v));
+  else o = gy[i] * cst * (kind == 0 ? nq_dsilu(v) : qh_dsoftplus(v));
   out[i] = o;
 }
 

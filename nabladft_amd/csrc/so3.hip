@@ -188,13 +188,14 @@ int nq_so3_mix_backward(const float* x1, const float* x2, const float* coeff, co
   return NQ_OK;
 }
 
-/* rows a workgroup of the reduced reverse kernel walks: ~1024 workgroups for large inputs, never fewer rows than one pass */
+/* rows a workgroup of the reduced reverse kernel walks: ~1024 workgroups for large inputs, capped at 128 rows, never fewer rows than one pass
+   (F = 1: one pass is 256 rows, above the cap) and always a whole number of passes */
 static int so3_rows_per_block(int64_t rows, int32_t F) {
   const int rpp = 256 / F;
   long k = (rows + 1023) / 1024;
   k = (k + rpp - 1) / rpp * rpp;
-  if (k < rpp) k = rpp;
   if (k > 128) k = 128 / rpp * rpp;
+  if (k < rpp) k = rpp;
   return (int)k;
 }
 int64_t nq_so3_mix_partial_blocks(int64_t rows, int32_t F) {
