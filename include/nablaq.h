@@ -39,7 +39,7 @@ extern "C" {
 #define NQ_ERR_WORKSPACE 4
 #define NQ_ERR_NO_EDGES 5
 
-#define NQ_ABI_VERSION 16
+#define NQ_ABI_VERSION 17
 
 /* Model hyper-parameters = constructor arguments of nablaDFT.painn_pyg.PaiNN (painn.py:28-45). */
 typedef struct nq_painn_cfg {
@@ -639,6 +639,33 @@ int nq_rccl_comm_count(void* comm, int32_t* count);   /* ncclCommCount: the rank
 int nq_allreduce(float* buf, size_t n, void* comm, void* stream);
 int nq_allreduce_mean(float* buf, size_t n, void* comm, void* stream);
 int nq_rccl_broadcast(float* buf, size_t n, int32_t root, void* comm, void* stream);
+
+/* ---- Batched L-BFGS geometry optimisation, state on the device (ABI 17; csrc/lbfgs.hip) -----------------------------------------------------
+ * Replaces: ASEBatchwiseLBFGS.step / update / determine_step (nablaDFT/optimization/optimizers.py:437-605, the branch without line search), the
+ * fixed-atom zeroing of BatchwiseCalculator.get_forces (optimization/calculator.py:85-86), the per-step positions -> float32 model input of
+ * atoms_list_to_PYG (optimization/opt_utils.py) and the convergence test of BatchwiseOptimizer.converged (optimizers.py:244-249).  All arithmetic is float64.
+ * `state` is ONE caller-owned device buffer of nq_lbfgs_state_bytes(N, B, memory) bytes, 16-byte aligned (0 = bad dimensions, see nq_last_error).
+ * nq_lbfgs_state_layout fills offsets_host[10] with the byte offsets of: header int32[16] = {iteration, unconverged molecules at the last step (-2: the
+ * step was called with other N / B / memory / n_small than nq_lbfgs_init and did nothing), first iteration at which no molecule was unconverged (-1: none
+ * yet), normalisations so far, N, B, memory, n_small, 2 internal words}; mol_ptr int32[B+1]; order int32[B]; converged int32[B]; rho f64[memory][B];
+ * r f64[N][3] (master positions); r0; f0; S f64[memory][N][3]; Y f64[memory][N][3] (pair k of a run sits in ring slot k % memory).
+ * nq_lbfgs_init: mol_ptr_host is a HOST array [B+1]; every molecule needs 1..512 atoms (NQ_ERR_MOL_TOO_LARGE above), memory 1..1024; copies `pos`
+ * (float32, or float64 when pos_f64) into r and into pos32 (the model's input tensor), zeroes the counters, writes *n_small_host (molecules of <= 192 atoms,
+ * one wavefront each; the others take one workgroup each) and synchronises `stream` once.
+ * nq_lbfgs_step: ONE kernel launch = one optimiser step on the forces of the current positions (float32, or float64 when forces_f64; fixed_mask uint8[N]
+ * nullable, non-zero = atom fixed): history push, two-loop recursion with H0 = 1/alpha, per-molecule maxstep scaling, damping, r += dr, pos32 = (float) r,
+ * r0 / f0, converged flags, header.  Molecules with max_i |f_i|^2 < fmax^2 do not move.  evaluate_only != 0: only the converged flags, the unconverged
+ * count and the latch are written (the final convergence test of BatchwiseDynamics.irun, optimizers.py:108-111); the iteration does not advance.
+ * Results are bitwise reproducible and do not depend on which other molecules share the batch. */
+size_t nq_lbfgs_state_bytes(int32_t N, int32_t B, int32_t memory);
+int nq_lbfgs_state_layout(int32_t N, int32_t B, int32_t memory, size_t* offsets_host);
+int nq_lbfgs_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, int32_t N, int32_t B, int32_t memory, const void* pos, int32_t pos_f64,
+                  float* pos32, int32_t* n_small_host, void* stream);
+/* nq_lbfgs_step repeats N, B, memory and n_small (the launch geometry is computed from them on the host, without reading the device).  The kernel compares
+ * them with the header nq_lbfgs_init wrote; on a mismatch it touches nothing but header word 1, which it sets to -2: the call still returns NQ_OK (it was
+ * enqueued), and the caller sees the -2 at its next read of the header. */
+int nq_lbfgs_step(void* state, int32_t N, int32_t B, int32_t memory, int32_t n_small, const void* forces, int32_t forces_f64, const uint8_t* fixed_mask,
+                  float* pos32, double fmax, double maxstep, double damping, double alpha, int32_t evaluate_only, void* stream);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NABLAQ_LIB") or os.path.join(_HERE, "libnablaq.so")   # NABLAQ_LIB: development builds (scripts/ablate.sh)
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 NQ_OK, NQ_ERR_HIP, NQ_ERR_ARG, NQ_ERR_MOL_TOO_LARGE, NQ_ERR_WORKSPACE, NQ_ERR_NO_EDGES = range(6)
 
@@ -200,6 +200,10 @@ SYMBOLS = {
     "nq_allreduce": (C.c_int, [_P, _SZ, _P, _P]),
     "nq_allreduce_mean": (C.c_int, [_P, _SZ, _P, _P]),
     "nq_rccl_broadcast": (C.c_int, [_P, _SZ, _I32, _P, _P]),
+    "nq_lbfgs_state_bytes": (_SZ, [_I32, _I32, _I32]),
+    "nq_lbfgs_state_layout": (C.c_int, [_I32, _I32, _I32, C.POINTER(_SZ)]),
+    "nq_lbfgs_init": (C.c_int, [_P, _SZ, _P, _I32, _I32, _I32, _P, _I32, _P, C.POINTER(C.c_int32), _P]),
+    "nq_lbfgs_step": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _D, _D, _D, _D, _I32, _P]),
 }
 
 _lib = None
