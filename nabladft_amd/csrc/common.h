@@ -224,8 +224,8 @@ size_t nq_gwr_scratch_floats(int E, int F, int R, int parts = 3);
 // count_dev (optional): device int holding the number of valid entries of order[] (<= E)
 int nq_gwr_sorted(hipStream_t, const float* GPHI, const float* GPSI, const float* RW, const int* order, int E, int F, int R, float* gWr,
                   float* scratch, int parts = 3, const int* count_dev = nullptr);
-int nq_msgf_fwd(hipStream_t, const MsgArgs&, const FilterArgs&, bool tangent);
-int nq_msgf_rev(hipStream_t, const MsgRevArgs&, const FilterArgs&, bool dual, bool pair_rows = true);   // pair_rows = false: the dual flavour neither writes gphi / gpsi nor GBR (molpair.hip computes the rbf_proj gradient); MsgRevArgs::row_filter selects the rows
+int nq_msgf_fwd(hipStream_t, const MsgArgs&, const FilterArgs&, bool tangent, bool layer0 = false);   // layer0: the flavour for vec_in = 0 and zero input tangents (the model's first layer)
+int nq_msgf_rev(hipStream_t, const MsgRevArgs&, const FilterArgs&, bool dual, bool pair_rows = true, bool layer0 = false);   // pair_rows = false: the dual flavour neither writes gphi / gpsi nor GBR (molpair.hip computes the rbf_proj gradient); MsgRevArgs::row_filter selects the rows
 // rbf_proj gradient with the molecule's node rows staged in LDS (molpair.hip): no gphi / gpsi arrays
 int nq_molgw_max_atoms(void);                      // largest molecule whose 20 rows of a 32-channel slice fit the LDS (62)
 bool nq_molgw_config_ok(int F, int R);             // channel count / window count supported
@@ -239,7 +239,7 @@ int nq_molgw_schedule(hipStream_t, const NqGraphView&, const int* dst, const flo
 int nq_molgw_geometry(hipStream_t, const NqGraphView&, const float* RW, const float* TD, const float* TR, const int* sched_ints, float* recs);
 int nq_gwr_mol(hipStream_t, const NqGraphView&, int F, int R, int max_mol_atoms, const float* XH, const float* V, const float* TXH, const float* TV,
                const float* GX, const float* GV, const float* GTX, const float* GTV, const int* sched_ints, const float* recs, float* part, float* gWr,
-               float* gbr, bool accumulate = false);
+               float* gbr, bool accumulate = false, bool layer0 = false);
 int nq_msg_rev(hipStream_t, const MsgRevArgs&, bool dual);
 int nq_geom_tan(hipStream_t, const NqGraphView&, const int* dst, const float* pos_dot, float* TD, float* TR);
 int nq_geom_rev(hipStream_t, const NqGraphView&, const float4* GEDGE, int nwaves, float* forces);

@@ -267,7 +267,10 @@ __global__ void k_msg_rev(MsgRevArgs q) {
 #define NQ_DUALNG2_THREADS 768  // dual reverse without the pair rows, 2 channels/lane: 165 VGPRs, no spill
 #endif
 // kind: 0 forward, 1 tangent, 2 force adjoint, 3 dual reverse, 4 dual reverse without pair rows.  Workgroup size = VGPR budget (one workgroup per CU: LDS holds WrT)
-__host__ __device__ constexpr int fused_threads(int kind, int ch) {
+__host__ __device__ constexpr int fused_threads(int kind, int ch, bool l0 = false) {
+  // layer-0 flavours (VGPRs, forward / tangent / force adjoint / dual; profiles/layer0_ab.txt section 3): CH=1 74 / 48 / 75 / 79, CH=2 94 / 58 / 77 / 96 -> all
+  // fit the 128 registers of 1024 threads; CH=4 118 / 102 / 172 / 179 -> 512 threads (256 registers).  None spills.
+  if (l0) return ch >= 4 ? 512 : 1024;
   return ch >= 4 ? 512
                  : (ch == 2 ? (kind == 3 ? NQ_DUAL2_THREADS : (kind == 4 ? NQ_DUALNG2_THREADS : (kind == 1 ? NQ_TAN2_THREADS : 1024)))
                             : (kind >= 3 ? 768 : 1024));
@@ -383,27 +386,44 @@ __device__ __forceinline__ void load_row(RowRegs& r, const NqGraphView& g, const
 }
 // phi (and psi) for this lane's CH channels of each of the three parts, from the LDS-resident WrT.
 // Written on CH-wide vectors so that every FMA pair becomes one v_pk_fma_f32 (the scalar form left the psi half unpacked).
-template <bool PSI, int CH>
+// PM / QM: the parts (bit 0 a, 1 b, 2 c) of phi / psi that the caller consumes.  A part in neither mask costs no LDS read and no FMA (the tap reads are
+// volatile, so dead-code elimination alone would keep them); its outputs are 0.  The layer-0 flavours drop part b, which only ever multiplies vec_in0 = 0.
+template <bool PSI, int CH, int PM = 7, int QM = 7>
 __device__ __forceinline__ void filter_eval(const WinRegs<PSI>& w, const float* wrt, int F, int F3, int fb, const float (&bra)[CH],
                                             const float (&brb)[CH], const float (&brc)[CH], float (&pa)[CH], float (&pb)[CH], float (&pc)[CH],
                                             float (&qa)[CH], float (&qb)[CH], float (&qc)[CH]) {
   typedef VOps<CH> O;
   typedef typename O::V V;
+  constexpr int QMM = PSI ? QM : 0, TM = PM | QMM;
+  constexpr bool PA = (PM & 1) != 0, PB = (PM & 2) != 0, PC = (PM & 4) != 0, QA = (QMM & 1) != 0, QB = (QMM & 2) != 0, QC = (QMM & 4) != 0;
   // bias enters as beta*b (phi) and beta'*b (psi); beta = 1, beta' = 0 in painn_pyg mode (exact)
   const V ba = O::from(bra), bb = O::from(brb), bc = O::from(brc);
-  V va = ba * O::splat(w.rr[14]), vb = bb * O::splat(w.rr[14]), vc = bc * O::splat(w.rr[14]);
-  V ua = O::splat(0.f), ub = ua, uc = ua;
-  if (PSI) { ua = ba * O::splat(w.dd[14]); ub = bb * O::splat(w.dd[14]); uc = bc * O::splat(w.dd[14]); }
+  V va = O::splat(0.f), vb = va, vc = va, ua = va, ub = va, uc = va;
+  if (PA) va = ba * O::splat(w.rr[14]);
+  if (PB) vb = bb * O::splat(w.rr[14]);
+  if (PC) vc = bc * O::splat(w.rr[14]);
+  if (QA) ua = ba * O::splat(w.dd[14]);
+  if (QB) ub = bb * O::splat(w.dd[14]);
+  if (QC) uc = bc * O::splat(w.dd[14]);
   const int k0 = __builtin_amdgcn_readfirstlane(__float_as_int(w.rr[13]));
   const float* wk = wrt + k0 * F3 + fb;
 #pragma unroll
   for (int t = 0; t < FWIN; ++t) {  // always 13 taps: LDS rows >= R and window taps >= R are zero
-    const V wa = lds_tap<CH>(wk + t * F3), wb = lds_tap<CH>(wk + t * F3 + F), wc = lds_tap<CH>(wk + t * F3 + 2 * F);
-    const V r = O::splat(w.rr[t]);
-    va = O::fma(wa, r, va); vb = O::fma(wb, r, vb); vc = O::fma(wc, r, vc);
-    if (PSI) {
+    V wa = va, wb = va, wc = va;
+    if (TM & 1) wa = lds_tap<CH>(wk + t * F3);
+    if (TM & 2) wb = lds_tap<CH>(wk + t * F3 + F);
+    if (TM & 4) wc = lds_tap<CH>(wk + t * F3 + 2 * F);
+    if (PM) {
+      const V r = O::splat(w.rr[t]);
+      if (PA) va = O::fma(wa, r, va);
+      if (PB) vb = O::fma(wb, r, vb);
+      if (PC) vc = O::fma(wc, r, vc);
+    }
+    if (QMM) {
       const V d = O::splat(w.dd[t]);
-      ua = O::fma(wa, d, ua); ub = O::fma(wb, d, ub); uc = O::fma(wc, d, uc);
+      if (QA) ua = O::fma(wa, d, ua);
+      if (QB) ub = O::fma(wb, d, ub);
+      if (QC) uc = O::fma(wc, d, uc);
     }
   }
   O::to(pa, va); O::to(pb, vb); O::to(pc, vc);
@@ -499,9 +519,13 @@ struct FwdSrc {
   __amdgpu_buffer_rsrc_t xh, v, txh, tv;
   __device__ __forceinline__ FwdSrc(const MsgArgs& q) : xh(row_rsrc(q.XH)), v(row_rsrc(q.V)), txh(row_rsrc(TAN ? q.TXH : q.XH)), tv(row_rsrc(TAN ? q.TV : q.V)) {}
 };
-template <bool TAN, int CH>
+template <bool TAN, int CH, bool L0 = false>
 __device__ __forceinline__ void load_fwd(FwdOps<TAN, CH>& o, const FwdSrc<TAN>& src, int k, int F, int F3, int fb) {
   const int ob = fb * 4, r0 = k * F3 * 4, r1 = r0 + F * 4, r2 = r1 + F * 4;
+  if (L0) {   // layer 0: vec_j, t_vec_j and t_xh_j are zero rows, part b only multiplies them
+    ldv_buf<CH>(o.xa, src.xh, ob, r0); ldv_buf<CH>(o.xc, src.xh, ob, r2);
+    return;
+  }
   ldv_buf<CH>(o.xa, src.xh, ob, r0); ldv_buf<CH>(o.xb, src.xh, ob, r1); ldv_buf<CH>(o.xc, src.xh, ob, r2);
   ldv_buf<CH>(o.va, src.v, ob, r0); ldv_buf<CH>(o.vb, src.v, ob, r1); ldv_buf<CH>(o.vc, src.v, ob, r2);
   if (TAN) {
@@ -510,8 +534,11 @@ __device__ __forceinline__ void load_fwd(FwdOps<TAN, CH>& o, const FwdSrc<TAN>& 
   }
 }
 
-template <bool TAN, int CH>
-__global__ __launch_bounds__(fused_threads(TAN ? 1 : 0, CH)) void k_msgf_fwd(MsgArgs q, FilterArgs fa, const float* __restrict__ RW) {
+// L0 (layer 0 of the model, engine.hip): vec_in0 = 0 and every tangent of the layer's input is 0 (x_in0 = emb[z] does not depend on the positions), so
+//   dx = xa phi_a, dvec = (xc phi_c) r            /  t_dx = xa psi_a t_d, t_dvec = (xc psi_c t_d) r + (xc phi_c) t_r
+// are the whole message: part b of the filter, the V / TV / TXH gathers and the own-row V / TX / TV reads drop out.
+template <bool TAN, int CH, bool L0 = false>
+__global__ __launch_bounds__(fused_threads(TAN ? 1 : 0, CH, L0)) void k_msgf_fwd(MsgArgs q, FilterArgs fa, const float* __restrict__ RW) {
   FUSED_PROLOGUE
   const FwdSrc<TAN> src(q);
   FUSED_ROWS(TAN ? 1 : 0) {
@@ -528,14 +555,15 @@ __global__ __launch_bounds__(fused_threads(TAN ? 1 : 0, CH)) void k_msgf_fwd(Msg
       // into a wait for the scalar cache), then the arithmetic.
       // Two operand sets in ping-pong (no register copies, so the wait for a gather sits at its first use one edge later).
       FwdOps<TAN, CH> opA, opB;
-      load_fwd<TAN, CH>(opA, src, bl_i(row.kk, 0), F, F3, fb);
+      load_fwd<TAN, CH, L0>(opA, src, bl_i(row.kk, 0), F, F3, fb);
       WinRegs<TAN> win;               // ONE window register set: it is dead once the filter is evaluated
       load_win<TAN>(win, RW, c0);
       auto step = [&](FwdOps<TAN, CH>& cur, FwdOps<TAN, CH>& nxt, int j, auto prefetch) __attribute__((always_inline)) {
         const int jn = min(j + 1, cnt - 1);   // branch-free: past the end the last edge is re-loaded (keeps the loop one basic block)
-        if (decltype(prefetch)::value) load_fwd<TAN, CH>(nxt, src, bl_i(row.kk, jn), F, F3, fb);
+        if (decltype(prefetch)::value) load_fwd<TAN, CH, L0>(nxt, src, bl_i(row.kk, jn), F, F3, fb);
         float pa[CH], pb[CH], pc[CH], qa[CH], qb[CH], qc[CH];
-        filter_eval<TAN, CH>(win, wrt, FL, 3 * FL, lfb, bra, brb, brc, pa, pb, pc, qa, qb, qc);
+        if (L0) filter_eval<TAN, CH, (TAN ? 4 : 5), 5>(win, wrt, FL, 3 * FL, lfb, bra, brb, brc, pa, pb, pc, qa, qb, qc);
+        else filter_eval<TAN, CH>(win, wrt, FL, 3 * FL, lfb, bra, brb, brc, pa, pb, pc, qa, qb, qc);
         __builtin_amdgcn_sched_barrier(0);
         if (decltype(prefetch)::value) load_win<TAN>(win, RW, c0 + jn);
         const float gx = bl_f(row.gx, j), gy = bl_f(row.gy, j), gz = bl_f(row.gz, j);
@@ -543,6 +571,24 @@ __global__ __launch_bounds__(fused_threads(TAN ? 1 : 0, CH)) void k_msgf_fwd(Msg
         if (TAN) { td = bl_f(row.td, j); tr0 = bl_f(row.t0, j); tr1 = bl_f(row.t1, j); tr2 = bl_f(row.t2, j); }
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
+          if (L0) {
+            // Written to keep the roundings the general branch below performs when its zero operands are filled in (products rounded before they are
+            // added, fused multiply-adds where the general expressions contract within a statement under the build's -ffp-contract=on): measured bitwise
+            // equal to the general flavour, and asserted so in tests/test_layer0_gpu.py.
+            const float mc = cur.xc[c] * pc[c];
+            if (!TAN) {
+              const float m0 = mc * gx, m1 = mc * gy, m2 = mc * gz;
+              dx[c] += cur.xa[c] * pa[c];
+              d0[c] += m0; d1[c] += m1; d2[c] += m2;
+            } else {
+              const float tma = cur.xa[c] * (qa[c] * td), tmc = cur.xc[c] * (qc[c] * td);
+              dx[c] += tma;
+              d0[c] += fmaf(mc, tr0, tmc * gx);
+              d1[c] += fmaf(mc, tr1, tmc * gy);
+              d2[c] += fmaf(mc, tr2, tmc * gz);
+            }
+            continue;
+          }
           const float mb = cur.xb[c] * pb[c], mc = cur.xc[c] * pc[c];
           if (!TAN) {
             dx[c] += cur.xa[c] * pa[c];
@@ -571,7 +617,11 @@ __global__ __launch_bounds__(fused_threads(TAN ? 1 : 0, CH)) void k_msgf_fwd(Msg
     }
     const long o = (long)n * F + fb, o3 = (long)n * F3 + fb;
     float x0[CH], w0[CH], w1[CH], w2[CH];
-    if (!TAN) {
+    if (L0) {   // vec_in0 = 0, t_x_in0 = 0, t_vec_in0 = 0: only x_in0 is added
+#pragma unroll
+      for (int c = 0; c < CH; ++c) x0[c] = w0[c] = w1[c] = w2[c] = 0.f;
+      if (!TAN) ldv<CH>(x0, q.X + o);
+    } else if (!TAN) {
       ldv<CH>(x0, q.X + o); ldv<CH>(w0, q.V + o3); ldv<CH>(w1, q.V + o3 + F); ldv<CH>(w2, q.V + o3 + 2 * F);
     } else {
       ldv<CH>(x0, q.TX + o); ldv<CH>(w0, q.TV + o3); ldv<CH>(w1, q.TV + o3 + F); ldv<CH>(w2, q.TV + o3 + 2 * F);
@@ -636,7 +686,10 @@ __device__ __forceinline__ void load_rev(RevOps<DUAL, CH>& o, const RevSrc<DUAL>
 // GW (dual only): this kernel also produces the pair rows gphi / gpsi and the per-atom bias sums for the rbf_proj gradient (rounds 1-4, still the path
 // for molecules that do not fit the LDS of molpair.hip); GW = false: the gradient is recomputed from node rows by k_gwr_mol, nothing is stored per pair.
 // LITE (dual, compile time): the adjoints of t_xh / t_vec are not accumulated at all (MsgRevArgs::lite at run time only skips their stores)
-template <bool DUAL, int CH, bool GW, bool LITE = false>
+// L0 (layer 0; force adjoint and the LITE dual flavour without pair rows): vec_in0 = t_vec_in0 = t_xh0 = 0, so gm_b = gtm_b = 0 (gxh_b = 0 is still
+// written: the W2 products read the whole row), the adjoint of vec_in0 has no consumer (no gv accumulation, no GV read, no GV_out store) and the
+// own rows of n are needed only where the force flavour forms the distance adjoint (xa, xc).
+template <bool DUAL, int CH, bool GW, bool LITE = false, bool L0 = false>
 __device__ __forceinline__ void msgf_rev_body(const MsgRevArgs& q, const FilterArgs& fa, const float* __restrict__ RW) {
   FUSED_PROLOGUE
   const RevSrc<DUAL> src(q);
@@ -650,10 +703,16 @@ __device__ __forceinline__ void msgf_rev_body(const MsgRevArgs& q, const FilterA
     const int nlow = (DUAL && GW) ? __builtin_amdgcn_readfirstlane(q.g.lowptr[n + 1]) - __builtin_amdgcn_readfirstlane(q.g.lowptr[n]) : 0;
     const long o3 = (long)n * F3 + fb;
     float xa[CH], xb[CH], xc[CH], v0[CH], v1[CH], v2[CH], txa[CH], txb[CH], txc[CH], tv0[CH], tv1[CH], tv2[CH];
-    ldv<CH>(xa, q.XH + o3); ldv<CH>(xb, q.XH + o3 + F); ldv<CH>(xc, q.XH + o3 + 2 * F);
-    ldv<CH>(v0, q.V + o3); ldv<CH>(v1, q.V + o3 + F); ldv<CH>(v2, q.V + o3 + 2 * F);
+    if (L0) {
+#pragma unroll
+      for (int c = 0; c < CH; ++c) xa[c] = xb[c] = xc[c] = v0[c] = v1[c] = v2[c] = 0.f;
+      if (!DUAL) { ldv<CH>(xa, q.XH + o3); ldv<CH>(xc, q.XH + o3 + 2 * F); }
+    } else {
+      ldv<CH>(xa, q.XH + o3); ldv<CH>(xb, q.XH + o3 + F); ldv<CH>(xc, q.XH + o3 + 2 * F);
+      ldv<CH>(v0, q.V + o3); ldv<CH>(v1, q.V + o3 + F); ldv<CH>(v2, q.V + o3 + 2 * F);
+    }
     float nA0[CH], nA1[CH], nA2[CH], ngma[CH], nT0[CH], nT1[CH], nT2[CH], ngtma[CH];   // adjoint rows of n itself (dual: reverse-direction gphi)
-    if (DUAL) {
+    if (DUAL && !L0) {
       ldv<CH>(txa, q.TXH + o3); ldv<CH>(txb, q.TXH + o3 + F); ldv<CH>(txc, q.TXH + o3 + 2 * F);
       ldv<CH>(tv0, q.TV + o3); ldv<CH>(tv1, q.TV + o3 + F); ldv<CH>(tv2, q.TV + o3 + 2 * F);
 #if NQ_DUAL_NA_RESIDENT
@@ -667,6 +726,7 @@ __device__ __forceinline__ void msgf_rev_body(const MsgRevArgs& q, const FilterA
 #pragma unroll
       for (int c = 0; c < CH; ++c) txa[c] = txb[c] = txc[c] = tv0[c] = tv1[c] = tv2[c] = 0.f;
     }
+    static_assert(!L0 || !GW, "the pair-row flavour has no layer-0 form");
     float gxa[CH], gxb[CH], gxc[CH], gv0[CH], gv1[CH], gv2[CH], gtxa[CH], gtxb[CH], gtxc[CH], gtv0[CH], gtv1[CH], gtv2[CH], sba[CH], sbb[CH], sbc[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
@@ -703,7 +763,8 @@ __device__ __forceinline__ void msgf_rev_body(const MsgRevArgs& q, const FilterA
 #pragma unroll
         for (int c = 0; c < CH; ++c) { pa[c] = bra[c] * win.rr[0]; pb[c] = brb[c] * win.rr[1]; pc[c] = brc[c] * win.rr[2]; qa[c] = bra[c] * win.dd[0]; qb[c] = brb[c] * win.dd[1]; qc[c] = brc[c] * win.dd[2]; }
 #else
-        filter_eval<true, CH>(win, wrt, FL, 3 * FL, lfb, bra, brb, brc, pa, pb, pc, qa, qb, qc);
+        if (L0) filter_eval<true, CH, 5, 5>(win, wrt, FL, 3 * FL, lfb, bra, brb, brc, pa, pb, pc, qa, qb, qc);
+        else filter_eval<true, CH>(win, wrt, FL, 3 * FL, lfb, bra, brb, brc, pa, pb, pc, qa, qb, qc);
 #endif
         const float beta = win.rr[14], dbeta = win.dd[14];
         __builtin_amdgcn_sched_barrier(0);
@@ -723,6 +784,21 @@ __device__ __forceinline__ void msgf_rev_body(const MsgRevArgs& q, const FilterA
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
           const float A0 = cur.A0[c], A1 = cur.A1[c], A2 = cur.A2[c], gma = cur.gma[c];
+          if (L0) {
+            float gmc = A0 * r0 + A1 * r1 + A2 * r2;
+            if (DUAL) {
+              const float T0 = cur.T0[c], T1 = cur.T1[c], T2 = cur.T2[c], gtma = cur.gtma[c];
+              gmc += T0 * tr0 + T1 * tr1 + T2 * tr2;
+              const float gtmc = T0 * r0 + T1 * r1 + T2 * r2;
+              gxa[c] += gma * pa[c] + gtma * (qa[c] * td); gxc[c] += gmc * pc[c] + gtmc * (qc[c] * td);
+            } else {
+              const float mc = xc[c] * pc[c];
+              gxa[c] += gma * pa[c]; gxc[c] += gmc * pc[c];
+              gd += fmaf(gmc * xc[c], qc[c], gma * xa[c] * qa[c]);   // the general expression with gm_b = 0, same roundings
+              e0 += A0 * mc; e1 += A1 * mc; e2 += A2 * mc;
+            }
+            continue;
+          }
           const float mb = xb[c] * pb[c], mc = xc[c] * pc[c];
           float gmb = A0 * v0[c] + A1 * v1[c] + A2 * v2[c];
           float gmc = A0 * r0 + A1 * r1 + A2 * r2;
@@ -829,6 +905,7 @@ __device__ __forceinline__ void msgf_rev_body(const MsgRevArgs& q, const FilterA
     }
     float g0[CH], g1[CH], g2[CH];
     stv<CH>(q.GXH + o3, gxa); stv<CH>(q.GXH + o3 + F, gxb); stv<CH>(q.GXH + o3 + 2 * F, gxc);
+    if (L0) continue;   // (gxb = 0 above; DUAL implies LITE here: nothing else to store)
     ldv<CH>(g0, q.GV + o3); ldv<CH>(g1, q.GV + o3 + F); ldv<CH>(g2, q.GV + o3 + 2 * F);
 #pragma unroll
     for (int c = 0; c < CH; ++c) { g0[c] += gv0[c]; g1[c] += gv1[c]; g2[c] += gv2[c]; }
@@ -850,6 +927,11 @@ __device__ __forceinline__ void msgf_rev_body(const MsgRevArgs& q, const FilterA
 template <bool DUAL, int CH>
 __global__ __launch_bounds__(fused_threads(DUAL ? 3 : 2, CH)) void k_msgf_rev(MsgRevArgs q, FilterArgs fa, const float* __restrict__ RW) {
   msgf_rev_body<DUAL, CH, DUAL>(q, fa, RW);
+}
+// the layer-0 forms: DUAL = false the force adjoint, DUAL = true the LITE dual flavour without pair rows
+template <bool DUAL, int CH>
+__global__ __launch_bounds__(fused_threads(DUAL ? 4 : 2, CH, true)) void k_msgf_rev_l0(MsgRevArgs q, FilterArgs fa, const float* __restrict__ RW) {
+  msgf_rev_body<DUAL, CH, false, DUAL, true>(q, fa, RW);
 }
 template <bool LITE, int CH>   // always the dual flavour; LITE = the stored-tangent-adjoint form of engine.hip (the default), false = the full dual sweep
 __global__ __launch_bounds__(fused_threads(4, CH)) void k_msgf_rev_nopair(MsgRevArgs q, FilterArgs fa, const float* __restrict__ RW) {
@@ -1231,43 +1313,53 @@ static int fused_grid(int N, int F, int ch, int* threads, size_t* lds, int R, in
 }
 
 // the >64 KB dynamic-LDS opt-in is sticky per (device, kernel): nq_dyn_lds sets it when the requested size grows, not on every launch
-#define FUSED_LAUNCH(KERN, FLAG, CHV, Q)                                                                          \
+#define FUSED_LAUNCH(KERN, Q, ...)                                                                                \
   do {                                                                                                            \
-    NQ_DYN_LDS((KERN<FLAG, CHV>), lds);                                                                           \
-    hipLaunchKernelGGL((KERN<FLAG, CHV>), dim3(grid), dim3(threads), lds, st, Q, fa, fa.RW);                      \
+    NQ_DYN_LDS((KERN<__VA_ARGS__>), lds);                                                                         \
+    hipLaunchKernelGGL((KERN<__VA_ARGS__>), dim3(grid), dim3(threads), lds, st, Q, fa, fa.RW);                    \
   } while (0)
-#define FUSED_DISPATCH(KERN, FLAG, Q)                                   \
+#define FUSED_DISPATCH_CH(Q, LAUNCH1, LAUNCH2, LAUNCH4)                 \
   do {                                                                  \
     switch (ch) {                                                       \
-      case 1: FUSED_LAUNCH(KERN, FLAG, 1, Q); break;                    \
-      case 2: FUSED_LAUNCH(KERN, FLAG, 2, Q); break;                    \
-      case 4: FUSED_LAUNCH(KERN, FLAG, 4, Q); break;                    \
+      case 1: LAUNCH1; break;                                           \
+      case 2: LAUNCH2; break;                                           \
+      case 4: LAUNCH4; break;                                           \
       default: return nq_fail(NQ_ERR_ARG, "fused message kernels need hidden_channels in {64,128,256}"); \
     }                                                                   \
   } while (0)
+#define FUSED_DISPATCH(KERN, FLAG, Q) FUSED_DISPATCH_CH(Q, FUSED_LAUNCH(KERN, Q, FLAG, 1), FUSED_LAUNCH(KERN, Q, FLAG, 2), FUSED_LAUNCH(KERN, Q, FLAG, 4))
+#define FUSED_DISPATCH_FWD_L0(FLAG, Q) \
+  FUSED_DISPATCH_CH(Q, FUSED_LAUNCH(k_msgf_fwd, Q, FLAG, 1, true), FUSED_LAUNCH(k_msgf_fwd, Q, FLAG, 2, true), FUSED_LAUNCH(k_msgf_fwd, Q, FLAG, 4, true))
 
-int nq_msgf_fwd(hipStream_t st, const MsgArgs& q, const FilterArgs& fa, bool tangent) {
-  NQ_PROF(st, tangent ? "msgf_tan" : "msgf_fwd");
+// layer0 (engine.hip, plan_step): the launch is the model's first layer, whose vector input and input tangents are zero -- the flavour that leaves out what
+// those zeros make redundant (k_msgf_fwd<.., true>, k_msgf_rev_l0), under a profile class of its own
+int nq_msgf_fwd(hipStream_t st, const MsgArgs& q, const FilterArgs& fa, bool tangent, bool layer0) {
+  NQ_PROF(st, tangent ? (layer0 ? "msgf_tan_l0" : "msgf_tan") : (layer0 ? "msgf_fwd_l0" : "msgf_fwd"));
   if (q.g.N <= 0) return NQ_OK;
   if ((size_t)q.g.N * 3 * q.F * 4 >= 0xfffff000ull) return nq_fail(NQ_ERR_ARG, "fused message kernels: a node array of %d atoms x %d channels exceeds the 4 GB a buffer descriptor's scalar offset reaches", q.g.N, 3 * q.F);
   int threads; size_t lds;
   const int ch = fused_ch(tangent ? 1 : 0, q.F, q.g.N);
-  const int grid = fused_grid(q.g.N, q.F, ch, &threads, &lds, fa.R, fused_threads(tangent ? 1 : 0, ch));
-  if (tangent) FUSED_DISPATCH(k_msgf_fwd, true, q);
+  const int grid = fused_grid(q.g.N, q.F, ch, &threads, &lds, fa.R, fused_threads(tangent ? 1 : 0, ch, layer0));
+  if (layer0 && tangent) FUSED_DISPATCH_FWD_L0(true, q);
+  else if (layer0) FUSED_DISPATCH_FWD_L0(false, q);
+  else if (tangent) FUSED_DISPATCH(k_msgf_fwd, true, q);
   else FUSED_DISPATCH(k_msgf_fwd, false, q);
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }
 
-int nq_msgf_rev(hipStream_t st, const MsgRevArgs& q, const FilterArgs& fa, bool dual, bool pair_rows) {
-  NQ_PROF(st, dual ? (pair_rows ? "msgf_rev_dual" : "msgf_rev_dual_ng") : "msgf_rev_force");
+int nq_msgf_rev(hipStream_t st, const MsgRevArgs& q, const FilterArgs& fa, bool dual, bool pair_rows, bool layer0) {
+  layer0 = layer0 && (!dual || (!pair_rows && q.lite));   // the pair-row and the full dual flavours have no layer-0 form: they run the general kernel
+  NQ_PROF(st, dual ? (pair_rows ? "msgf_rev_dual" : (layer0 ? "msgf_rev_dual_ng_l0" : "msgf_rev_dual_ng")) : (layer0 ? "msgf_rev_force_l0" : "msgf_rev_force"));
   if (q.g.N <= 0) return NQ_OK;
   if ((size_t)q.g.N * 3 * q.F * 4 >= 0xfffff000ull) return nq_fail(NQ_ERR_ARG, "fused message kernels: a node array of %d atoms x %d channels exceeds the 4 GB a buffer descriptor's scalar offset reaches", q.g.N, 3 * q.F);
   int threads; size_t lds;
   const int kind = dual ? (pair_rows ? 3 : 4) : 2;
   const int ch = fused_ch(dual ? 3 : 2, q.F, q.g.N);
-  const int grid = fused_grid(q.g.N, q.F, ch, &threads, &lds, fa.R, fused_threads(kind, ch));
-  if (dual && !pair_rows && q.lite) FUSED_DISPATCH(k_msgf_rev_nopair, true, q);
+  const int grid = fused_grid(q.g.N, q.F, ch, &threads, &lds, fa.R, fused_threads(kind, ch, layer0));
+  if (layer0 && dual) FUSED_DISPATCH(k_msgf_rev_l0, true, q);
+  else if (layer0) FUSED_DISPATCH(k_msgf_rev_l0, false, q);
+  else if (dual && !pair_rows && q.lite) FUSED_DISPATCH(k_msgf_rev_nopair, true, q);
   else if (dual && !pair_rows) FUSED_DISPATCH(k_msgf_rev_nopair, false, q);
   else if (dual) FUSED_DISPATCH(k_msgf_rev, true, q);
   else FUSED_DISPATCH(k_msgf_rev, false, q);

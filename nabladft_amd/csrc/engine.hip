@@ -185,6 +185,10 @@ struct StepPlan {
   int gw_mode, gw_cap;
   bool lite;           // the force sweep leaves its per-layer adjoints in the workspace (WsLayer::LG*) for the second-order sweep
   bool fused_update;   // forward sweep: the update block of a layer as one kernel (updfuse.hip)
+  // Layer 0 of the model has vec_in0 = 0 and, x_in0 = emb[z] not depending on the positions, zero tangents of x_in0, z1, h, xh and vec_in0 (both set up by
+  // nq_painn_forward itself).  layer0: the five default kernels of the message path run their layer-0 flavours there (edge.hip, molpair.hip), and the node-side
+  // products whose operands are those zeros or whose results nobody reads are left out.  NQ_NO_LAYER0=1: every layer runs the general code (A/B runs, tests).
+  bool layer0;
 };
 static StepPlan plan_step(const nq_painn_cfg* c, const nq_graph* g, bool want_forces) {
   auto env_on = [](const char* name) { const char* v = getenv(name); return v && v[0] == '1'; };
@@ -202,6 +206,7 @@ static StepPlan plan_step(const nq_painn_cfg* c, const nq_graph* g, bool want_fo
   // NQ_NO_FUSED_UPDATE=1 keeps the five launches (A/B runs, tests); the fused kernel's products exist on the split-bf16 matrix pipe only, so a run that asks
   // for the exact-f32 engine gets the five launches too
   p.fused_update = nq_updfuse_frag_floats(c->hidden_channels) > 0 && !env_on("NQ_NO_FUSED_UPDATE") && !nq_gemm_exact_f32_requested();
+  p.layer0 = !env_on("NQ_NO_LAYER0");
   return p;
 }
 // the layout of a workspace sized or inspected outside a step (nq_painn_workspace_bytes, nq_painn_ws_lookup): the plan such a step would make now
@@ -215,9 +220,22 @@ static bool plan_fused(const nq_painn_cfg* c, int32_t N, int32_t E, int32_t B) {
 struct StepRecord { nq_painn_cfg cfg; int32_t N, E, B, max_mol_atoms; StepPlan plan; };
 static std::mutex g_plan_mu;
 static std::map<const void*, StepRecord> g_plans;
+// Tests only ('gxh' of nq_painn_ws_lookup, which has no workspace pointer to look a record up with): the record of the latest forward call of the process.
+// Two models of one configuration and batch shape share it (the later forward call wins); the engine's own calls never read it.  The configuration is
+// compared as recall_plan compares it (memcmp of the caller's struct, which the Python binding builds as a zero-filled ctypes structure: padding bytes, if any, are zeros).
+static StepRecord g_last_plan;
+static bool g_have_last_plan = false;
 static void record_plan(const void* ws, const nq_painn_cfg* c, const nq_graph* g, const StepPlan& p) {
   std::lock_guard<std::mutex> lock(g_plan_mu);
   g_plans[ws] = StepRecord{*c, g->N, g->E, g->B, g->max_mol_atoms, p};
+  g_last_plan = g_plans[ws]; g_have_last_plan = true;
+}
+// the plan of the latest forward call, if that call was made for this model and batch shape
+static bool last_plan_for(const nq_painn_cfg* c, int32_t N, int32_t E, int32_t B, StepPlan* p) {
+  std::lock_guard<std::mutex> lock(g_plan_mu);
+  if (!g_have_last_plan || memcmp(&g_last_plan.cfg, c, sizeof(nq_painn_cfg)) != 0 || g_last_plan.N != N || g_last_plan.E != E || g_last_plan.B != B) return false;
+  *p = g_last_plan.plan;
+  return true;
 }
 static int recall_plan(const void* ws, const nq_painn_cfg* c, const nq_graph* g, StepPlan* p) {
   std::lock_guard<std::mutex> lock(g_plan_mu);
@@ -356,6 +374,16 @@ int nq_painn_ws_lookup(const nq_painn_cfg* cfg, int32_t N, int32_t E, int32_t B,
   else if (!strcmp(name, "zq")) { LAYER_OK(L - 1); base = W.lay[l].ZQ; rows = n; w = F; }
   else if (!strcmp(name, "q")) { LAYER_OK(L - 1); base = W.lay[l].Q; rows = n; w = F; }
   else if (!strcmp(name, "y")) { LAYER_OK(L - 1); base = W.lay[l].Y; rows = n; w = 3 * F; }
+  else if (!strcmp(name, "gxh")) {   // adjoint of xh after a whole step (tests): tangent = 0 the second-order sweep's, tangent = 1 the adjoint of t_xh
+    LAYER_OK(L - 1);
+    StepPlan sp;   // where the step left it depends on the plan the forward call recorded, not on the switches now
+    if (!last_plan_for(cfg, N, E, B, &sp)) return nq_fail(NQ_ERR_ARG, "buffer 'gxh': the latest forward call was not made for this model and batch");
+    if (!sp.fused) return nq_fail(NQ_ERR_ARG, "buffer 'gxh' exists only with the fused filter");
+    if (sp.lite) base = W.lay[l].LGXH;                          // stored per layer (the second half is the force sweep's gxh)
+    else if (l == 0) base = W.GXH;                              // one buffer for all layers: it holds the layer processed last
+    else return nq_fail(NQ_ERR_ARG, "buffer 'gxh' of layer %d is overwritten by the layers below it on this path", l);
+    rows = n; w = 3 * F;
+  }
   else if (!strcmp(name, "rho")) {                                            // tangent=1 -> drho
     if (W.fused) return nq_fail(NQ_ERR_ARG, "buffer 'rho' is not materialised (filter is fused into the message kernels)");
     base = W.RHO2; rows = e; w = R;
@@ -441,7 +469,7 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
       NQ_TRY(nq_transpose(st, params + mp.Wr, 3 * F, R, ws + y.WRT));
       nq_make_filter_args(&fa, ws + y.WRT, params + mp.br, rbf_offsets, ws + W.RW, R, cfg->cutoff, cfg->envelope_exponent, cfg->rbf_coeff, cfg->filter_mode);
       fa.row_ctr = row_ctr(0, l);
-      NQ_TRY(nq_msgf_fwd(st, m, fa, false));
+      NQ_TRY(nq_msgf_fwd(st, m, fa, false, plan.layer0 && l == 0));
     } else {
       NQ_TRY(nq_gemm_nt(st, rho, params + mp.Wr, ws + y.PHI, params + mp.br, nullptr, E, 3 * F, R, R, R, 3 * F, "Wr"));
       NQ_TRY(nq_gemm_nt(st, drho, params + mp.Wr, ws + y.PSI, nullptr, nullptr, E, 3 * F, R, R, R, 3 * F, "Wr"));
@@ -509,13 +537,14 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
       FilterArgs fa;
       nq_make_filter_args(&fa, ws + y.WRT, params + mp.br, rbf_offsets, ws + W.RW, R, cfg->cutoff, cfg->envelope_exponent, cfg->rbf_coeff, cfg->filter_mode);
       fa.row_ctr = row_ctr(1, l);
-      NQ_TRY(nq_msgf_rev(st, m, fa, false));
+      NQ_TRY(nq_msgf_rev(st, m, fa, false, true, plan.layer0 && l == 0));   // layer 0: GV_out (the adjoint of vec_in0) has no reader and is not written
     } else {
       NQ_TRY(nq_msg_rev(st, m, false));
     }
     float* const GH = lite_store ? ws + y.LGH + NF : ws + W.GH;
     if (lite_store) NQ_TRY(nq_gemm_nn_dsilu2(st, GXH, params + mp.W2, ws + y.LGHP, GH, ws + y.Z1, N, 3 * F, F, "W2"));
     else NQ_TRY(nq_gemm_nn_epi(st, GXH, params + mp.W2, GH, N, 3 * F, F, ws + y.Z1, 0.f, 1.f, 1, "W2"));
+    if (plan.layer0 && l == 0) break;   // the adjoint of x_in0 has no reader in this sweep (the embedding gradient comes from the second-order sweep)
     if (lite_store) {
       NQ_TRY(nq_gemm_nn_epi(st, GH, params + mp.W1, gx_next, N, F, F, gx_msg, 1.f, 0.f, 0, "W1"));   // gx_upd of the layer below = gx_msg + gz1 W1
       gx_cur = gx_next; gv_cur = gv_next;
@@ -637,8 +666,14 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
     float* TZ1 = ws + y.Z1 + NF; float* TH = ws + y.Hh + NF; float* TXH = ws + y.XH + 3 * NF;
     // tangent pre-activation and tangent activation TH = TZ1 * silu'(Z1) in one pass
-    NQ_TRY(nq_gemm_nt_dsilu(st, ws + W.X[l] + NF, params + mp.W1, TZ1, TH, ws + y.Z1, N, F, F, "W1"));
-    NQ_TRY(nq_gemm_nt(st, TH, params + mp.W2, TXH, nullptr, nullptr, N, 3 * F, F, F, F, 3 * F, "W2"));
+    if (plan.layer0 && l == 0) {   // t_x_in0 = 0: both products are zero rows (the dual sweep and the traces read these buffers)
+      NQ_HIP(hipMemsetAsync(TZ1, 0, NF * sizeof(float), st));
+      NQ_HIP(hipMemsetAsync(TH, 0, NF * sizeof(float), st));
+      NQ_HIP(hipMemsetAsync(TXH, 0, 3 * NF * sizeof(float), st));
+    } else {
+      NQ_TRY(nq_gemm_nt_dsilu(st, ws + W.X[l] + NF, params + mp.W1, TZ1, TH, ws + y.Z1, N, F, F, "W1"));
+      NQ_TRY(nq_gemm_nt(st, TH, params + mp.W2, TXH, nullptr, nullptr, N, 3 * F, F, F, F, 3 * F, "W2"));
+    }
     MsgArgs m{};
     m.g = g; m.F = F; m.X = ws + W.X[l]; m.V = ws + W.V[l]; m.XH = ws + y.XH; m.PHI = ws + y.PHI; m.PSI = ws + y.PSI;
     m.TX = ws + W.X[l] + NF; m.TV = ws + W.V[l] + 3 * NF; m.TXH = TXH; m.TD = ws + W.TD; m.TR = ws + W.TR;
@@ -647,7 +682,7 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
       FilterArgs fa;
       nq_make_filter_args(&fa, ws + y.WRT, params + mp.br, rbf_offsets, ws + W.RW, R, cfg->cutoff, cfg->envelope_exponent, cfg->rbf_coeff, cfg->filter_mode);
       fa.row_ctr = row_ctr(2, l);
-      NQ_TRY(nq_msgf_fwd(st, m, fa, true));
+      NQ_TRY(nq_msgf_fwd(st, m, fa, true, plan.layer0 && l == 0));
     } else {
       NQ_TRY(nq_msg_fwd(st, m, true));
     }
@@ -703,6 +738,7 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
   if (mixed) NQ_HIP(hipMemsetAsync(ws + W.GBR, 0, 3 * NF * sizeof(float), st));   // only the rows of the large molecules are written below; the column sum runs over all atoms
   for (int l = L - 1; l >= 0; --l) {
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
+    const bool l0 = plan.layer0 && l == 0;   // layer 0: no GV_out / GTV_out reader; t_h0 = 0 and t_x_in0 = 0 are the tangent halves of the W2 / W1 gradient operands
     float* const GYs = lite ? ws + y.LGY : ws + W.GY;         // stacked [2][N][3F]: the second half is the force sweep's (lite) or written below
     float* const GCATs = lite ? ws + y.LGCAT : ws + W.GCAT;
     float* const GUs = lite ? ws + y.LGU : ws + W.GU;
@@ -748,7 +784,7 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
       fa.row_ctr = row_ctr(3, l);
       m.mol_cap = plan.gw_cap;
       m.row_filter = mixed ? 1 : 0;
-      NQ_TRY(nq_msgf_rev(st, m, fa, true, !molgw));
+      NQ_TRY(nq_msgf_rev(st, m, fa, true, !molgw, l0));
       if (mixed) {   // the molecules that do not fit the LDS of k_gwr_mol: pair rows, k0-sorted contraction and per-atom bias sums as in rounds 1-4, for THEIR rows only
         m.row_filter = 2;
         fa.row_ctr = row_ctr(4, l);
@@ -759,7 +795,7 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
       // rbf_proj weight and bias gradient from the same node rows, staged per molecule in LDS (main stream: it reads the adjoints this layer's input-gradient
       // products overwrite next; the fork below orders the side stream and the layer event behind it); mixed: added to what the pair-row kernels left
       if (molgw)
-        NQ_TRY(nq_gwr_mol(st, g, F, R, plan.gw_cap, m.XH, m.V, m.TXH, m.TV, m.GX, m.GV, m.GTX, m.GTV, sched, ws + W.GWREC, ws + W.GWPART, gp + mp.Wr, gp + mp.br, mixed));
+        NQ_TRY(nq_gwr_mol(st, g, F, R, plan.gw_cap, m.XH, m.V, m.TXH, m.TV, m.GX, m.GV, m.GTX, m.GTV, sched, ws + W.GWREC, ws + W.GWPART, gp + mp.Wr, gp + mp.br, mixed, l0));
     } else {
       NQ_TRY(nq_msg_rev(st, m, true));
     }
@@ -770,13 +806,13 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
     if (cfg->rbf_type)   // adjoints of rho / drho (shared by all layers): [gphi; gpsi] Wr, accumulated over the layers
       NQ_TRY(nq_gemm_nn(st, gphi, params + mp.Wr, ws + W.GRHO, 2 * E, 3 * F, R, 3 * F, R, R, l == L - 1 ? 0 : 1, "Wr"));
     if (!molgw) NQ_TRY(nq_colsum(sd, ws + W.GBR, N, 3 * F, 3 * F, gp + mp.br, scr));
-    NQ_TRY(nq_gemm_tn(sd, GXHs, ws + y.Hh, gp + mp.W2, 2L * N, 3 * F, F, 3 * F, F, scr, "W2", gp + mp.b2, N));
+    NQ_TRY(nq_gemm_tn(sd, GXHs, ws + y.Hh, gp + mp.W2, l0 ? (long)N : 2L * N, 3 * F, F, 3 * F, F, scr, "W2", gp + mp.b2, N));
     ss.read_by_side(SB_GPHI); ss.read_by_side(SB_GBR); ss.read_by_side(SB_GXH);
     ss.before_main_writes(SB_GH);
     NQ_TRY(nq_gemm_nn(st, GXHs, params + mp.W2, GHs, lite ? N : 2 * N, 3 * F, F, 3 * F, F, F, 0, "W2"));
     NQ_TRY(nq_silu_rev(st, ws + y.Z1, ws + y.Z1 + NF, GHs, lite ? ws + y.LGHP : GHs + NF, (long)NF, true, lite));
     sd = ss.fork();
-    NQ_TRY(nq_gemm_tn(sd, GHs, ws + W.X[l], gp + mp.W1, 2L * N, F, F, F, F, scr, "W1", gp + mp.b1, N));
+    NQ_TRY(nq_gemm_tn(sd, GHs, ws + W.X[l], gp + mp.W1, l0 ? (long)N : 2L * N, F, F, F, F, scr, "W1", gp + mp.b1, N));
     ss.read_by_side(SB_GH);
     NQ_TRY(nq_gemm_nn(st, GHs, params + mp.W1, ws + W.GX, lite ? N : 2 * N, F, F, F, F, F, 1, "W1"));
     // every gradient slice of layer l (and, for l = L-1, of the read-out head) is final once the weight-gradient stream gets here: the caller's

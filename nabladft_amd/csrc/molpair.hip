@@ -293,6 +293,10 @@ __device__ __forceinline__ float gm_pair_sum(float x, float y) {
 struct GmOps { f4 P0, P1, P2, A, T; };
 struct GmRec { u4 hi, lo; };   // the two A pieces of this lane for one batch
 
+// LZ (layer 0 of the model): vec_in0 = t_vec_in0 = 0 and t_xh0 = 0, so gm_b = gtm_b = 0 and part b of gphi / gpsi is zero for every pair: only the row
+// blocks 0 (xh), 3 and 4 (adjoints) are staged -- 11 of 20 rows --, a pair step forms parts a and c only, and a batch is 6 matrix instructions.
+// The part-b accumulators stay zero and are flushed as zeros (k_gwr_mol_reduce sums every part).
+template <bool LZ>
 __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* __restrict__ PA, const unsigned* __restrict__ PG) {
   extern __shared__ __attribute__((aligned(16))) float rows[];   // [atom][5 blocks][32 channels][4], then one 512-byte scalar ring per wavefront
   const int F = q.F, F3 = 3 * q.F;
@@ -326,7 +330,8 @@ __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* 
     }
     const long n = a0 + min(st_at, na - 1), o = n * F3 + cb + 4 * st_qd;   // threads past the last atom re-read it (no branch around loads that stay in flight)
     r[0] = *reinterpret_cast<const f4*>(s0 + o); r[1] = *reinterpret_cast<const f4*>(s1 + o); r[2] = *reinterpret_cast<const f4*>(s2 + o);
-    r[3] = *reinterpret_cast<const f4*>(s3 + n * st3 + cb + 4 * st_qd);
+    if (LZ && blk == 0) r[3] = f4{0.f, 0.f, 0.f, 0.f};   // t_xh_a at layer 0: a zero row that no pair step reads
+    else r[3] = *reinterpret_cast<const f4*>(s3 + n * st3 + cb + 4 * st_qd);
   };
   auto blk_store = [&](int blk, int na, const f4 (&r)[4]) __attribute__((always_inline)) {
     if (st_at < na) {
@@ -343,8 +348,8 @@ __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* 
     const char* pt = reinterpret_cast<const char*>(rows) + ((ko ^ x) + lbase);
     if (GM_ABLATE & 8) { const float z = __uint_as_float((no ^ x) + lbase); o.P0 = o.P1 = o.P2 = f4{z, z, 1.f, 2.f}; o.A = o.T = f4{1.f, z, __uint_as_float((ko ^ x) + lbase), 3.f}; return; }
     o.P0 = *reinterpret_cast<const f4*>(ps);                          // xa xb xc txa
-    o.P1 = *reinterpret_cast<const f4*>(ps + GM_CH * 16);             // txb txc v0 v1
-    o.P2 = *reinterpret_cast<const f4*>(ps + 2 * GM_CH * 16);         // v2 tv0 tv1 tv2
+    if (!LZ) o.P1 = *reinterpret_cast<const f4*>(ps + GM_CH * 16);             // txb txc v0 v1
+    if (!LZ) o.P2 = *reinterpret_cast<const f4*>(ps + 2 * GM_CH * 16);         // v2 tv0 tv1 tv2
     o.A = *reinterpret_cast<const f4*>(pt + 3 * GM_CH * 16);          // A0 A1 A2 gma
     o.T = *reinterpret_cast<const f4*>(pt + 4 * GM_CH * 16);          // T0 T1 T2 gtma
   };
@@ -378,11 +383,18 @@ __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* 
       if (i == GM_BATCH - 1 && !more) nkn = 0;   // past the segment: atom 0 with itself (rows that exist)
       ops_load(nxt, nkn);
       const float gx = g0[0], gy = g0[1], gz = g0[2], t0 = gc[0], t1 = gc[1], t2 = gc[2];
-      const f4 P0 = cur.P0, P1 = cur.P1, P2 = cur.P2, A = cur.A, T = cur.T;
+      const f4 P0 = cur.P0, A = cur.A, T = cur.T;
+      f4 P1 = f4{0.f, 0.f, 0.f, 0.f}, P2 = P1;
+      if (!LZ) { P1 = cur.P1; P2 = cur.P2; }
       const float xa = P0[0], xb = P0[1], xc = P0[2], txa = P0[3], txb = P1[0], txc = P1[1], v0 = P1[2], v1 = P1[3], v2 = P2[0], tv0 = P2[1],
                   tv1 = P2[2], tv2 = P2[3];
       float ga, gb, gcc, ha, hb, hc;
-      if (GM_ABLATE & 4) { ga = xa + gx; gb = xb + txa; gcc = xc + A[0]; ha = txb + T[0]; hb = v2 + gy + t0; hc = tv2 + v1 + t1 + t2 + gz + txc + v0 + tv0 + tv1; }
+      if (LZ) {   // t_xh = 0, vec = t_vec = 0 (see the general branch below for the signs)
+        const float gmc = (A[0] * gx + A[1] * gy + A[2] * gz) + (T[0] * t0 + T[1] * t1 + T[2] * t2);
+        const float gtmc = T[0] * gx + T[1] * gy + T[2] * gz;
+        ga = A[3] * xa; gcc = gmc * xc; ha = T[3] * xa; hc = gtmc * xc;
+        gb = 0.f; hb = 0.f;
+      } else if (GM_ABLATE & 4) { ga = xa + gx; gb = xb + txa; gcc = xc + A[0]; ha = txb + T[0]; hb = v2 + gy + t0; hc = tv2 + v1 + t1 + t2 + gz + txc + v0 + tv0 + tv1; }
       else {
         // the unit vector of the lane's direction is -geom (n -> k) / +geom (k -> n): gmc, gtmc are computed with +geom here and the sign is applied by
         // the DIFF form of the direction sum below; the factor t_d of gpsi sits in the drho half of the A operands (k_pair_arec)
@@ -395,7 +407,7 @@ __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* 
         ha = gtma * xa; hb = gtmb * xb; hc = gtmc * xc;
       }
       // both directions combined: lanes 0-31 <- gphi(n->k) + gphi(k->n), lanes 32-63 <- gpsi(n->k) + gpsi(k->n) (part c: difference, see gm_pair_sum)
-      ba = gm_pair_sum<false>(ga, ha); bb = gm_pair_sum<false>(gb, hb); bc = gm_pair_sum<true>(gcc, hc);
+      ba = gm_pair_sum<false>(ga, ha); bb = LZ ? 0.f : gm_pair_sum<false>(gb, hb); bc = gm_pair_sum<true>(gcc, hc);
       gc = gn;
     };
     if (!(GM_ABLATE & 1)) {
@@ -406,7 +418,7 @@ __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* 
         step(2 * j, L0, L1, a0_, b0_, c0_);
         step(2 * j + 1, L1, L0, a1_, b1_, c1_);
         gm_split2(a0_, a1_, bh[0][j], bl[0][j]);
-        gm_split2(b0_, b1_, bh[1][j], bl[1][j]);
+        if (!LZ) gm_split2(b0_, b1_, bh[1][j], bl[1][j]);
         gm_split2(c0_, c1_, bh[2][j], bl[2][j]);
       }
     }
@@ -417,13 +429,13 @@ __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* 
       const gm_bf8 h2 = __builtin_bit_cast(gm_bf8, (u4{bh[2][0], bh[2][1], bh[2][2], bh[2][3]})), l2 = __builtin_bit_cast(gm_bf8, (u4{bl[2][0], bl[2][1], bl[2][2], bl[2][3]}));
       // small terms first; the three parts interleave so that no instruction waits for the accumulator of the one before it
       acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, h0, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, h1, acc1, 0, 0, 0);
+      if (!LZ) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, h1, acc1, 0, 0, 0);
       acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, h2, acc2, 0, 0, 0);
       acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, l0, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, l1, acc1, 0, 0, 0);
+      if (!LZ) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, l1, acc1, 0, 0, 0);
       acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, l2, acc2, 0, 0, 0);
       acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, h0, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, h1, acc1, 0, 0, 0);
+      if (!LZ) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, h1, acc1, 0, 0, 0);
       acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, h2, acc2, 0, 0, 0);
     } else { acc0[0] += __uint_as_float(bh[0][0] ^ bl[1][1] ^ bh[2][2] ^ bl[0][3] ^ bh[1][0] ^ bl[2][1] ^ bh[0][1] ^ bl[0][0] ^ bh[1][2] ^ bl[1][3] ^ bh[2][0] ^ bl[2][3] ^ rc.hi[0] ^ rc.lo[1]); }
   };
@@ -445,7 +457,7 @@ __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* 
   if (m < q.g.B && stager) {
     const int a0 = __builtin_amdgcn_readfirstlane(q.g.mol_ptr[m]), na = __builtin_amdgcn_readfirstlane(q.g.mol_ptr[m + 1]) - a0;
 #pragma unroll
-    for (int blk = 0; blk < 5; ++blk) { f4 r[4]; blk_load(blk, a0, na, r); blk_store(blk, na, r); }
+    for (int blk = 0; blk < 5; ++blk) { if (LZ && (blk == 1 || blk == 2)) continue; f4 r[4]; blk_load(blk, a0, na, r); blk_store(blk, na, r); }
   }
   // per segment: A operands of batch j in RX (even j) / RY (odd j), scalar records of batch j in ring slot j & 1; requested one batch ahead
   // (scalars: two), the first ones before the barrier that ends the previous molecule
@@ -498,7 +510,7 @@ __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* 
     f4 stg[5][4];
     if (GM_STAGE_EARLY && mn < q.g.B && stager) {
 #pragma unroll
-      for (int blk = 0; blk < 5; ++blk) blk_load(blk, a0n, nan, stg[blk]);
+      for (int blk = 0; blk < 5; ++blk) { if (LZ && (blk == 1 || blk == 2)) continue; blk_load(blk, a0n, nan, stg[blk]); }
     }
     // the first batches of the next molecule's segment: they arrive while the rows are being written
     if (mn < q.g.B) { rec_load(RX, sgn_.x); gq0 = geo_load(sgn_.x); gq1 = geo_load(sgn_.x + 1); }
@@ -506,6 +518,7 @@ __global__ __launch_bounds__(GM_THREADS) void k_gwr_mol(GwrMolArgs q, const u4* 
     if (mn < q.g.B && stager) {
 #pragma unroll
       for (int blk = 0; blk < 5; ++blk) {
+        if (LZ && (blk == 1 || blk == 2)) continue;
         if (!GM_STAGE_EARLY) blk_load(blk, a0n, nan, stg[blk]);
         blk_store(blk, nan, stg[blk]);
       }
@@ -663,8 +676,8 @@ int nq_molgw_geometry(hipStream_t st, const NqGraphView& g, const float* RW, con
 
 int nq_gwr_mol(hipStream_t st, const NqGraphView& g, int F, int R, int max_mol_atoms, const float* XH, const float* V, const float* TXH, const float* TV,
                const float* GX, const float* GV, const float* GTX, const float* GTV, const int* sched_ints, const float* recs, float* part, float* gWr,
-               float* gbr, bool accumulate) {
-  NQ_PROF(st, "gwr_mol");
+               float* gbr, bool accumulate, bool layer0) {
+  NQ_PROF(st, layer0 ? "gwr_mol_l0" : "gwr_mol");
   const MolGwBufs b = molgw_bufs(const_cast<int*>(sched_ints), g.E, g.B);
   GwrMolArgs q;
   q.g = g; q.F = F; q.nslices = F / GM_CH; q.groups = molgw_groups(g.B, q.nslices);
@@ -674,8 +687,13 @@ int nq_gwr_mol(hipStream_t st, const NqGraphView& g, int F, int R, int max_mol_a
   const u4* PA = reinterpret_cast<const u4*>(recs);
   const unsigned* PG = reinterpret_cast<const unsigned*>(recs + gm_max_batches(g.E, g.B) * GM_PA_DWORDS);
   const size_t lds = (size_t)q.max_atoms * GM_ATOM_BYTES + GM_NW * GM_RING_BYTES;
-  NQ_DYN_LDS(k_gwr_mol, lds);
-  hipLaunchKernelGGL(k_gwr_mol, dim3(q.groups * q.nslices), dim3(GM_THREADS), lds, st, q, PA, PG);
+  if (layer0) {
+    NQ_DYN_LDS(k_gwr_mol<true>, lds);
+    hipLaunchKernelGGL(k_gwr_mol<true>, dim3(q.groups * q.nslices), dim3(GM_THREADS), lds, st, q, PA, PG);
+  } else {
+    NQ_DYN_LDS(k_gwr_mol<false>, lds);
+    hipLaunchKernelGGL(k_gwr_mol<false>, dim3(q.groups * q.nslices), dim3(GM_THREADS), lds, st, q, PA, PG);
+  }
   NQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_gwr_mol_reduce, dim3(nq_cdiv((long)(R + 1) * 3 * F, 256 / GMR_Q)), dim3(256), 0, st, part, b.wlo, q.groups, q.nslices, R, F, gWr, gbr, accumulate ? 1 : 0);
   NQ_LAUNCH_CHECK();
