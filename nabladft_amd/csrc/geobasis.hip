@@ -230,6 +230,19 @@ int nq_bernstein_rbf_grad_alpha(const float* r, const float* grad_out, int64_t P
 // backward: gx in place of a fresh buffer, and per-row partials of dL/dalpha, dL/dbeta (summed over rows by the caller).
 __device__ __forceinline__ float act_sig(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float act_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+// value and the three derivatives of one element; both kernels below go through it, so the scalar rows of the packed form are bitwise those of the plain one
+__device__ __forceinline__ void act_terms(int kind, float xv, float a, float b, float& yv, float& dx, float& da, float& db) {
+  const float ln2 = 0.69314718055994530942f;
+  if (kind == 0) {
+    const float s = act_sig(b * xv);
+    yv = a * xv * s; dx = a * (s + xv * b * s * (1.0f - s)); da = xv * s; db = a * xv * xv * s * (1.0f - s);
+  } else if (b != 0.f) {
+    const float sp = act_softplus(b * xv) - ln2, s = act_sig(b * xv);
+    yv = a * sp / b; dx = a * s; da = sp / b; db = a * (xv * s / b - sp / (b * b));
+  } else {
+    yv = 0.5f * a * xv; dx = 0.5f * a; da = 0.5f * xv; db = a * xv * xv * 0.125f;   // limit beta -> 0 of the derivative
+  }
+}
 template <bool BWD>
 __global__ void k_feature_act(const float* __restrict__ x, const float* __restrict__ alpha, const float* __restrict__ beta, long rows, int F, int kind,
                               float* __restrict__ y, const float* __restrict__ gy, float* __restrict__ gx, float* __restrict__ ga_rows,
@@ -237,29 +250,13 @@ __global__ void k_feature_act(const float* __restrict__ x, const float* __restri
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= rows * F) return;
   const int f = (int)(idx % F);
-  const float xv = x[idx], a = alpha[f], b = beta[f];
-  const float ln2 = 0.69314718055994530942f;
-  if (kind == 0) {
-    const float s = act_sig(b * xv);
-    if (!BWD) { y[idx] = a * xv * s; return; }
-    const float g = gy[idx];
-    gx[idx] = g * a * (s + xv * b * s * (1.0f - s));
-    ga_rows[idx] = g * xv * s;
-    gb_rows[idx] = g * a * xv * xv * s * (1.0f - s);
-  } else {
-    if (b != 0.f) {
-      const float sp = act_softplus(b * xv) - ln2;
-      if (!BWD) { y[idx] = a * sp / b; return; }
-      const float g = gy[idx], s = act_sig(b * xv);
-      gx[idx] = g * a * s;
-      ga_rows[idx] = g * sp / b;
-      gb_rows[idx] = g * a * (xv * s / b - sp / (b * b));
-    } else {
-      if (!BWD) { y[idx] = 0.5f * a * xv; return; }
-      const float g = gy[idx];
-      gx[idx] = g * 0.5f * a; ga_rows[idx] = g * 0.5f * xv; gb_rows[idx] = g * a * xv * xv * 0.125f;   // limit beta -> 0 of the derivative
-    }
-  }
+  float yv, dx, da, db;
+  act_terms(kind, x[idx], alpha[f], beta[f], yv, dx, da, db);
+  if (!BWD) { y[idx] = yv; return; }
+  const float g = gy[idx];
+  gx[idx] = g * dx;
+  ga_rows[idx] = g * da;
+  gb_rows[idx] = g * db;
 }
 
 extern "C" {
@@ -300,18 +297,8 @@ __global__ void k_packed_act0(const float* __restrict__ x, const float* __restri
     return;
   }
   const long r = rc / ncomp;
-  const float xv = x[idx], a = alpha[f], b = beta[f];
-  const float ln2 = 0.69314718055994530942f;
   float yv, dx, da, db;
-  if (kind == 0) {
-    const float s = act_sig(b * xv);
-    yv = a * xv * s; dx = a * (s + xv * b * s * (1.0f - s)); da = xv * s; db = a * xv * xv * s * (1.0f - s);
-  } else if (b != 0.f) {
-    const float sp = act_softplus(b * xv) - ln2, s = act_sig(b * xv);
-    yv = a * sp / b; dx = a * s; da = sp / b; db = a * (xv * s / b - sp / (b * b));
-  } else {
-    yv = 0.5f * a * xv; dx = 0.5f * a; da = 0.5f * xv; db = a * xv * xv * 0.125f;
-  }
+  act_terms(kind, x[idx], alpha[f], beta[f], yv, dx, da, db);
   if (!BWD) { y[idx] = yv; return; }
   const float g = gy[idx];
   gx[idx] = g * dx;
@@ -445,7 +432,7 @@ __global__ void k_radial_basis(int kind, const float* __restrict__ r, long P, in
 extern "C" {
 int nq_radial_basis(int32_t kind, const float* r, int64_t P, int32_t K, float alpha, float cutoff, float width, const float* t0, const float* t1, const float* t2,
                     float* out, void* stream) {
-  if (!r || !t0 || !out || kind < 1 || kind > 4 || (kind >= 3 && (!t1 || !t2))) return nq_fail(NQ_ERR_ARG, "bad argument");
+  if (!r || !t0 || !out || kind < 1 || kind > 4 || (kind >= 3 && (!t1 || !t2)) || K <= 0 || P < 0) return nq_fail(NQ_ERR_ARG, "bad argument");
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "radial_basis");
   if (P > 0) hipLaunchKernelGGL((k_radial_basis<false>), dim3((unsigned)((P * K + 255) / 256)), dim3(256), 0, st, kind, r, (long)P, K, alpha, cutoff, width, t0, t1, t2, out,
@@ -455,7 +442,8 @@ int nq_radial_basis(int32_t kind, const float* r, int64_t P, int32_t K, float al
 }
 int nq_radial_basis_grad_alpha(int32_t kind, const float* r, const float* grad_out, int64_t P, int32_t K, float alpha, float cutoff, float width, const float* t0,
                                const float* t1, const float* t2, float* galpha_rows, void* stream) {
-  if (!r || !t0 || !grad_out || !galpha_rows || (kind != 2 && kind != 3) || (kind == 3 && (!t1 || !t2))) return nq_fail(NQ_ERR_ARG, "bad argument");
+  if (!r || !t0 || !grad_out || !galpha_rows || (kind != 2 && kind != 3) || (kind == 3 && (!t1 || !t2)) || K <= 0 || P < 0)
+    return nq_fail(NQ_ERR_ARG, "bad argument");
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "radial_basis_grad");
   if (P > 0) hipLaunchKernelGGL((k_radial_basis<true>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, kind, r, (long)P, K, alpha, cutoff, width, t0, t1, t2, nullptr,

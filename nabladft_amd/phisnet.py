@@ -225,7 +225,7 @@ class _SphLinearFn(torch.autograd.Function):
             gws = [torch.empty_like(w) for w in ws]
         gwp = (C.c_void_p * len(gws))(*[w.data_ptr() for w in gws])
         gb = torch.empty(Fout, device=g.device, dtype=torch.float32) if ctx.has_bias else None
-        scr = torch.empty(int(lib.nq_sph_weight_grad_scratch_floats(rows, order, Fin, Fout)) + 64, device=g.device, dtype=torch.float32)
+        scr = torch.empty(int(lib.nq_sph_weight_grad_scratch_floats(rows, order, Fin, Fout)), device=g.device, dtype=torch.float32)
         _lib.check(lib.nq_sph_linear_weight_grad(_lib.ptr(g), _lib.ptr(x2), gwp, _lib.ptr(gb), rows, order, Fin, Fout, _lib.ptr(scr), _lib.stream_ptr()))
         if ctx.stacked:
             return gx, gb, gst
