@@ -561,7 +561,7 @@ int nq_profile_read(char* names_host, int32_t name_stride, double* total_ms_host
  * class's TFLOP/s is flops / time without re-deriving shapes from names (every other launcher records 0).  ABI 11. */
 int nq_profile_read2(char* names_host, int32_t name_stride, double* total_ms_host, int64_t* counts_host, double* flops_host, int32_t cap);
 
-/* Engine / tuning switch of the dense products (process-global; default 1):
+/* Engine / tuning switch of the dense products (process-global; default 1; the bits are named by enum GemmVariant in csrc/gemm.hip):
  *   bits 0-1  generic round-1 kernel flavour (bit0 = 8 wavefronts per 128x128 tile, bit1 = register prefetch),
  *   bit 3 (8)   never the small-problem kernel,  bit 4 (16)  only the generic kernels (no k_gemm2 / k_gemm3),
  *   bit 5 (32)  exact-f32 MFMA only: every product on v_mfma_f32_32x32x2_f32.  Without it (the default) launches of >= 192 tiles of 128x128 run on the

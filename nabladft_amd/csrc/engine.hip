@@ -881,39 +881,4 @@ int nq_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_
                        step, scratch);
 }
 
-int nq_linear_forward(const float* A, const float* Wt, const float* bias, float* C, float* C_silu, int32_t M, int32_t N, int32_t K, void* stream) {
-  return nq_gemm_nt((hipStream_t)stream, A, Wt, C, bias, C_silu, M, N, K, K, K, N);
-}
-int nq_linear_forward_act(const float* A, const float* Wt, float* C, float* C_act, const float* resid, float alpha, float beta, int32_t M, int32_t N, int32_t K,
-                          void* stream) {
-  if (!A || !Wt || !C || !C_act) return nq_fail(NQ_ERR_ARG, "null argument");
-  return nq_gemm_nt_act((hipStream_t)stream, A, Wt, C, C_act, resid, alpha, beta, M, N, K);
-}
-int nq_linear_forward_res(const float* A, const float* Wt, const float* aux, float alpha, float* C, int32_t M, int32_t N, int32_t K, void* stream) {
-  if (!A || !Wt || !C || !aux) return nq_fail(NQ_ERR_ARG, "null argument");
-  if (aux == C) return nq_fail(NQ_ERR_ARG, "nq_linear_forward_res: aux must not alias C");
-  return nq_gemm_nt_res((hipStream_t)stream, A, Wt, C, aux, alpha, M, N, K);
-}
-int nq_linear_input_grad(const float* G, const float* Wt, float* C, int32_t M, int32_t N, int32_t K, int32_t accumulate, void* stream) {
-  return nq_gemm_nn((hipStream_t)stream, G, Wt, C, M, N, K, N, K, K, accumulate);
-}
-int nq_linear_input_grad_epi(const float* G, const float* Wt, float* C, int32_t M, int32_t N, int32_t K, const float* aux, float alpha, float beta, int32_t mode,
-                             void* stream) {
-  if (!G || !Wt || !C || !aux || (mode != 1 && mode != 2)) return nq_fail(NQ_ERR_ARG, "bad argument");
-  return nq_gemm_nn_epi((hipStream_t)stream, G, Wt, C, M, N, K, aux, alpha, beta, mode);
-}
-size_t nq_column_sum_scratch_floats(int64_t rows, int32_t cols) { return nq_colsum_scratch_floats((long)rows, cols); }
-int nq_column_sum(const float* A, int64_t rows, int32_t cols, int64_t lda, float* out, float* scratch, void* stream) {
-  if (!A || !out || !scratch || cols < 1 || lda < cols) return nq_fail(NQ_ERR_ARG, "column_sum: bad argument");
-  return nq_colsum((hipStream_t)stream, A, (long)rows, cols, (int)lda, out, scratch);
-}
-size_t nq_weight_grad_scratch_floats(int64_t rows, int32_t N, int32_t K) { return nq_gemm_tn_scratch_floats(rows, N, K); }
-int nq_linear_weight_grad(const float* G, const float* X, float* gW, int64_t rows, int32_t N, int32_t K, float* scratch, void* stream) {
-  return nq_gemm_tn((hipStream_t)stream, G, X, gW, rows, N, K, N, K, scratch);
-}
-int nq_linear_weight_grad_bias(const float* G, const float* X, float* gW, float* gb, int64_t rows, int32_t N, int32_t K, float* scratch, void* stream) {
-  if (!gb) return nq_fail(NQ_ERR_ARG, "null bias gradient");
-  return nq_gemm_tn((hipStream_t)stream, G, X, gW, rows, N, K, N, K, scratch, nullptr, gb, rows);
-}
-
 }  // extern "C"

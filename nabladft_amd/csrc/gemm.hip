@@ -14,6 +14,9 @@
 // ([BK][BM+pad]) so that the MFMA operand fetch (lane l: row l&31, k = l>>5) is a conflict-free
 // ds_read_b32 of 32 consecutive floats per half-wave.
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <vector>
 #include "gemm_tile.h"   // round 3: the persistent, double-buffered tile engine k_gemm2 (every launch whose operands are 16-byte friendly)
 #include "gemm_split.h"  // round 3: the same skeleton on the bf16 matrix pipe, every f32 value split exactly into three bf16 pieces (large launches)
 
@@ -22,12 +25,6 @@
 #define BN 128
 // BKT (template parameter of the kernels) = K depth of one staged tile: 32 by default; the input-gradient (NN) launches use 16 -- half the
 // LDS and 64 VGPRs give four workgroups per CU instead of three, measured +10-20 % for that layout (profiles/r01_gemm_variants_microbench.txt)
-#define GEMM_THREADS 256
-#ifdef NQ_GEMM_WAVES8
-#define GEMM_OCC __attribute__((amdgpu_waves_per_eu(8, 8)))
-#else
-#define GEMM_OCC
-#endif
 
 __device__ __forceinline__ long rm_row(int q, int w, int ncomp, int base) { return (long)(q / w) * ncomp + base + q % w; }
 
@@ -100,7 +97,7 @@ __device__ __forceinline__ void stash_tile(float* __restrict__ tile, const float
 // NW = wavefronts per 128x128 tile: 4 -> each wave owns 64x64 (2x2 MFMA tiles), 8 -> 64x32 (2x1).
 // PF = register prefetch of the next k-tile (one extra barrier-free overlap of global latency with MFMAs).
 template <bool A_KC, bool B_KC, int EPI, int NW, bool PF, int BKT = 32, int RM = 0>
-__global__ __launch_bounds__(NW * 64) GEMM_OCC void k_gemm(GemmArgs p) {
+__global__ __launch_bounds__(NW * 64) void k_gemm(GemmArgs p) {
   constexpr int NT = NW * 64;
   constexpr int TN = NW == 4 ? 2 : 1;
   constexpr int LDA_S = A_KC ? LDS_KC : LDS_MC;
@@ -309,23 +306,33 @@ __global__ __launch_bounds__(256) void k_gemm_small(GemmArgs p) {
 // fewer than one 128x128 tile per CU -> the small-tile kernel
 static bool gemm_is_small(int M, int N) { return (long)nq_cdiv(M, BM) * nq_cdiv(N, BN) < 256; }
 
-// process-global kernel variant (tuning / A-B measurements): bit0 = 8 waves per tile, bit1 = register prefetch, bit3 = never use the small-tile kernel
-static int g_gemm_variant = 1;  // measured best on MI355X (scripts/gemm_bench.py): 8 wavefronts per tile, no prefetch
+// process-global kernel variant (tuning / A-B measurements; the values are the ones nablaq.h documents for nq_set_gemm_variant)
+enum GemmVariant : int {
+  GV_WAVES8 = 1,            // generic kernel: 8 wavefronts per tile
+  GV_PREFETCH = 2,          // generic kernel: register prefetch of the next k-tile
+  GV_NO_SMALL = 8,          // never use the small-tile kernel
+  GV_GENERIC_ONLY = 16,     // force the generic kernels (no tile engines)
+  GV_EXACT_F32 = 32,        // every product on the exact-f32 matrix instruction (no split-bf16 engine)
+  GV_SPLIT_ALWAYS = 64,     // split-bf16 engine on every eligible launch, whatever its tile count (tests)
+  GV_NO_SPLITK = 128,       // never split K
+  GV_SPH_ROW_MAPPED = 256,  // spherical linears keep the row-mapped generic launches
+};
+static int g_gemm_variant = GV_WAVES8;  // measured best on MI355X (scripts/gemm_bench.py): 8 wavefronts per tile, no prefetch
 extern "C" void nq_set_gemm_variant(int32_t v) { g_gemm_variant = v; }
 
 template <bool A_KC, bool B_KC, int EPI, int BKT = 32>
 static void launch_gemm(hipStream_t st, dim3 grid, const GemmArgs& p) {
-  int variant = g_gemm_variant & 3;
+  int variant = g_gemm_variant & (GV_WAVES8 | GV_PREFETCH);
   // latency-bound regime (few workgroups, e.g. batch_size 32): nothing else hides the global-load latency of the serial
   // K loop, so the register-prefetch form pays there (it is neutral-to-slightly-negative on full grids)
-  if (variant == 1 && (long)grid.x * grid.y * grid.z < 512) variant = 3;
+  if (variant == GV_WAVES8 && (long)grid.x * grid.y * grid.z < 512) variant |= GV_PREFETCH;
   // row-major-A layouts (forward, input gradient): the prefetch form also wins on full grids since the input-gradient launches use 16-deep
   // tiles (+14 % on the U / 2x shapes, +3-5 % forward); the weight-gradient layout (A_KC = false) loses 15 % with it and stays on variant 1
-  if (variant == 1 && A_KC) variant = 3;
+  if (variant == GV_WAVES8 && A_KC) variant |= GV_PREFETCH;
   switch (variant) {
     case 0: hipLaunchKernelGGL((k_gemm<A_KC, B_KC, EPI, 4, false, BKT>), grid, dim3(256), 0, st, p); break;
-    case 1: hipLaunchKernelGGL((k_gemm<A_KC, B_KC, EPI, 8, false, BKT>), grid, dim3(512), 0, st, p); break;
-    case 2: hipLaunchKernelGGL((k_gemm<A_KC, B_KC, EPI, 4, true, BKT>), grid, dim3(256), 0, st, p); break;
+    case GV_WAVES8: hipLaunchKernelGGL((k_gemm<A_KC, B_KC, EPI, 8, false, BKT>), grid, dim3(512), 0, st, p); break;
+    case GV_PREFETCH: hipLaunchKernelGGL((k_gemm<A_KC, B_KC, EPI, 4, true, BKT>), grid, dim3(256), 0, st, p); break;
     default: hipLaunchKernelGGL((k_gemm<A_KC, B_KC, EPI, 8, true, BKT>), grid, dim3(512), 0, st, p); break;
   }
 }
@@ -399,7 +406,7 @@ __global__ __launch_bounds__(256) void k_colsum_partial(const float* __restrict_
 // k_gemm2 reads both operands with 16-byte buffer loads and 32-bit offsets from the tile origin.
 template <bool A_KC, bool B_KC>
 static bool gemm2_ok(const GemmArgs& p, long kspan) {
-  if (g_gemm_variant & 16) return false;   // A/B switch: force the generic kernels
+  if (g_gemm_variant & GV_GENERIC_ONLY) return false;   // A/B switch
   if ((reinterpret_cast<uintptr_t>(p.A) & 15) || (reinterpret_cast<uintptr_t>(p.B) & 15) || (p.lda & 3) || (p.ldb & 3)) return false;
   if ((A_KC || B_KC) && (p.K & 3)) return false;   // K-contiguous operand: whole float4s along k
   if (!A_KC && (p.M & 3)) return false;            // MN-contiguous operands: whole float4s along m / n
@@ -436,13 +443,13 @@ static void launch_gemm2(hipStream_t st, const GemmArgs& p, int splits) {
 // problems stay on k_gemm2's 64 x 64 tiles.  nq_set_gemm_variant(32) (or NQ_GEMM_F32=1 in the environment) keeps every product on v_mfma_f32_32x32x2_f32.
 static bool gemm3_disabled() {
   static const int env = [] { const char* e = getenv("NQ_GEMM_F32"); return (e && e[0] && e[0] != '0') ? 1 : 0; }();
-  return env || (g_gemm_variant & 32);
+  return env || (g_gemm_variant & GV_EXACT_F32);
 }
 bool nq_gemm_exact_f32_requested() { return gemm3_disabled(); }   // NQ_GEMM_F32=1 / nq_set_gemm_variant(32): every product on the exact-f32 instruction
 template <bool A_KC, bool B_KC>
 static bool gemm3_ok(const GemmArgs& p, long kspan, int splits) {
   if (gemm3_disabled() || !gemm2_ok<A_KC, B_KC>(p, kspan)) return false;
-  return (g_gemm_variant & 64) || (long)nq_cdiv(p.M, 128) * nq_cdiv(p.N, 128) * splits >= 192;   // bit 6: every eligible launch (tests)
+  return (g_gemm_variant & GV_SPLIT_ALWAYS) || (long)nq_cdiv(p.M, 128) * nq_cdiv(p.N, 128) * splits >= 192;
 }
 template <bool A_KC, bool B_KC, int EPI>
 static int launch_gemm3(hipStream_t st, const GemmArgs& p, int splits) {
@@ -464,18 +471,40 @@ static int launch_gemm3(hipStream_t st, const GemmArgs& p, int splits) {
   return NQ_OK;
 }
 
+// ---- engine choice: the one ladder every dense product goes down --------------------------------------------------------------------------------
+// split-bf16 engine (enough 128 x 128 tiles) -> exact-f32 tile engine (16-byte friendly operands) -> round-1 kernels: the small-tile kernel for few tiles of a
+// row-major-A product, else the generic kernel with GENERIC_BKT-deep tiles (16 for the NN layout, see BKT above).  kspan = the K range one workgroup walks;
+// splits > 1 with EPI_PARTIAL = that many K ranges (grid.z of the generic kernel).  Only the rungs a layout / epilogue can reach are instantiated.
+template <bool A_KC, bool B_KC, int EPI, int GENERIC_BKT = 32>
+static int launch_product(hipStream_t st, const GemmArgs& p, long kspan, int splits = 1) {
+  constexpr bool SPLITK = A_KC && EPI == EPI_PARTIAL;   // partial slabs of try_splitk, which has checked gemm2_ok: the round-1 kernels have no such flavour
+  if (gemm3_ok<A_KC, B_KC>(p, kspan, splits)) NQ_TRY((launch_gemm3<A_KC, B_KC, EPI>(st, p, splits)));
+  else if (SPLITK || gemm2_ok<A_KC, B_KC>(p, kspan)) launch_gemm2<A_KC, B_KC, EPI>(st, p, splits);
+  else if constexpr (!SPLITK) {
+    if (A_KC && gemm_is_small(p.M, p.N) && !(g_gemm_variant & GV_NO_SMALL)) {   // (the TN layout has no small-tile kernel)
+      if constexpr (A_KC) hipLaunchKernelGGL((k_gemm_small<B_KC, EPI>), dim3(nq_cdiv(p.M, SM), nq_cdiv(p.N, SM), 1), dim3(256), 0, st, p);
+    } else {
+      launch_gemm<A_KC, B_KC, EPI, GENERIC_BKT>(st, dim3(nq_cdiv(p.M, BM), nq_cdiv(p.N, BN), splits), p);
+    }
+  }
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+
 // ---- batched launches (round 4): nbatch independent products that differ by operand offsets only (GemmArgs::nbatch, bsA / bsB / bsC, Bz), grid.y = batch.
 // The spherical linears of QHNet / PhiSNet / EquiformerV2 act on packed irreps tensors [rows][ncomp][F]; for ONE packed component the rows form a plain
 // strided matrix (leading dimension ncomp * F), so the whole layer is ncomp plain products = one batched launch of the tile engines instead of the
 // row-mapped launch of the generic round-1 kernel (32-48 TFLOP/s).
+// Its own ladder, not launch_product's: the batched kernel flavours, grids capped per batch entry, no k-tail flavour of the split engine, no round-1 rung
+// (the callers fall back to the row-mapped generic launch).
 template <bool A_KC, bool B_KC, int EPI>
 static bool launch_batched(hipStream_t st, const GemmArgs& p, int splits, long kspan) {
-  if (g_gemm_variant & 256) return false;                                   // bit 8: keep the row-mapped generic launches (A/B switch)
+  if (g_gemm_variant & GV_SPH_ROW_MAPPED) return false;   // A/B switch
   if (!gemm2_ok<A_KC, B_KC>(p, kspan) || p.nbatch < 1) return false;
   if ((p.bsA & 3) || (p.bsB & 3) || (p.bsC & 3) || (p.ldc & 3) || (reinterpret_cast<uintptr_t>(p.C) & 15)) return false;
   if (p.bz) for (int L = 0; L < 7; ++L) if (p.Bz[L] && (reinterpret_cast<uintptr_t>(p.Bz[L]) & 15)) return false;
   const long t128 = (long)nq_cdiv(p.M, 128) * nq_cdiv(p.N, 128) * splits, t64 = (long)nq_cdiv(p.M, 64) * nq_cdiv(p.N, 64) * splits;
-  const bool use3 = !gemm3_disabled() && !p.bpart && EPI != EPI_PARTIAL && ((g_gemm_variant & 64) || t128 * p.nbatch >= 192) && !(p.K & 15);
+  const bool use3 = !gemm3_disabled() && !p.bpart && EPI != EPI_PARTIAL && ((g_gemm_variant & GV_SPLIT_ALWAYS) || t128 * p.nbatch >= 192) && !(p.K & 15);
   if (use3) {
     const long cap = 256 * 3;
     const unsigned gx = (unsigned)std::min<long>(t128, std::max<long>(1, (cap + p.nbatch - 1) / p.nbatch));
@@ -494,12 +523,9 @@ static bool launch_batched(hipStream_t st, const GemmArgs& p, int splits, long k
 // QHNet's generator adjoints are [rows x 5376] x [5376 x 32] and [rows x 8320] x [8320 x 128] at 17-28 k rows: 136-215 output tiles of 128 x 128, each a
 // 1.4-4.3 MB serial stream of the long operand -- one tile per CU at best, 2.2-2.5 TB/s.  With the contraction cut into S ranges (S x tiles workgroups,
 // partial slabs in a per-stream scratch of the library, fixed-order reduction that also applies bias / accumulation) the same bytes are streamed by the whole chip.
-#include <map>
-#include <mutex>
-#include <vector>
 static int splitk_count(int M, int N, int K) {
   const long tiles = (long)nq_cdiv(M, 128) * nq_cdiv(N, 128);
-  if (K < 2048 || (K & 31) || tiles >= 256 || (g_gemm_variant & 128)) return 1;      // bit 7: never split (A/B switch)
+  if (K < 2048 || (K & 31) || tiles >= 256 || (g_gemm_variant & GV_NO_SPLITK)) return 1;
   long s = 768 / tiles;
   if (s > K / 512) s = K / 512;          // >= 512 k per range
   if (s > 16) s = 16;
@@ -592,223 +618,109 @@ static bool try_splitk(hipStream_t st, GemmArgs p, const float* bias, int accumu
   float* scratch = splitk_scratch(st, (size_t)nse * cnt);
   if (!scratch) return false;
   float* out = p.C;
-  p.C = scratch; p.bias = nullptr; p.C2 = nullptr; p.k_per_split = kper; p.part_stride = cnt; p.bpart = nullptr; p.brows = 0;
-  if (gemm3_ok<A_KC, B_KC>(p, kper, nse)) { rc = launch_gemm3<A_KC, B_KC, EPI_PARTIAL>(st, p, nse); if (rc != NQ_OK) return true; }
-  else if (gemm2_ok<A_KC, B_KC>(p, kper)) launch_gemm2<A_KC, B_KC, EPI_PARTIAL>(st, p, nse);
-  else return false;
+  p.C = scratch; p.bias = nullptr; p.C2 = nullptr; p.k_per_split = kper; p.part_stride = cnt;
+  if (!gemm2_ok<A_KC, B_KC>(p, kper)) return false;   // split-K runs on the tile engines only
+  rc = launch_product<A_KC, B_KC, EPI_PARTIAL>(st, p, kper, nse);
+  if (rc != NQ_OK) return true;
   hipLaunchKernelGGL(k_reduce_splitk, dim3((unsigned)nq_cdiv(cnt / 4, 256)), dim3(256), 0, st, scratch, nse, cnt, cnt, p.N, bias, accumulate, out);
   return true;
 }
 
 // ---- host launchers ------------------------------------------------------------------------
+// Every launcher: profiler scope, GemmArgs, (two of them) split-K, then launch_product with the epilogue chosen at run time.
+static GemmArgs gemm_args(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc) {
+  GemmArgs p{};
+  p.A = A; p.B = B; p.C = C;
+  p.M = M; p.N = N; p.K = K;
+  p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+  return p;
+}
+// second operand of the epilogues that read one (EPI_SILU_RES, EPI_DSILU, EPI_DSILU2, EPI_RES) and their two scale factors
+static void gemm_aux(GemmArgs& p, const float* resid, float ea, float eb) { p.resid = resid; p.ea = ea; p.eb = eb; }
+
+// opens the launcher's profiler scope (the name is formatted only while profiling) and records the product's arithmetic
+#define GEMM_PROF(st, fmt, tag, d0, d1, flops)                                                        \
+  char nm__[48];                                                                                      \
+  if (nq_profile_on) snprintf(nm__, sizeof nm__, fmt, (tag) ? (tag) : "", d0, d1); else nm__[0] = 0; \
+  NQ_PROF(st, nm__);                                                                                  \
+  NQ_PROF_FLOPS(flops)
+// NT / NN launchers: scope "gemm_<kind>:<tag>[n=N,k=K]"; an empty product launches nothing
+#define GEMM_PROLOGUE(st, kind, tag, M, N, K)                                              \
+  GEMM_PROF(st, "gemm_" kind ":%s[n=%d,k=%d]", tag, N, K, 2.0 * (M) * (N) * (K));          \
+  if ((M) <= 0) return NQ_OK
+
+// C[M, N] = A W^T (+ bias), optionally C2_silu = silu(C)
 int nq_gemm_nt(hipStream_t st, const float* A, const float* W, float* C, const float* bias, float* C2_silu, int M, int N, int K,
                int lda, int ldw, int ldc, const char* tag) {
-  char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nt:%s[n=%d,k=%d]", tag ? tag : "", N, K); else nm__[0] = 0;
-  NQ_PROF(st, nm__);
-  NQ_PROF_FLOPS(2.0 * M * N * K);
-  if (M <= 0) return NQ_OK;
-  GemmArgs p{A, W, C, bias, C2_silu, M, N, K, lda, ldw, ldc, 0, 0, nullptr, 0};
-  if (!C2_silu) {
-    int rc;
-    if (try_splitk<true, true>(st, p, bias, 0, rc)) { NQ_TRY(rc); NQ_LAUNCH_CHECK(); return NQ_OK; }
-  }
-  if (gemm3_ok<true, true>(p, K, 1)) {
-    if (C2_silu) NQ_TRY((launch_gemm3<true, true, EPI_SILU>(st, p, 1)));
-    else NQ_TRY((launch_gemm3<true, true, EPI_STORE>(st, p, 1)));
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  if (gemm2_ok<true, true>(p, K)) {
-    if (C2_silu) launch_gemm2<true, true, EPI_SILU>(st, p, 1);
-    else launch_gemm2<true, true, EPI_STORE>(st, p, 1);
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  if (gemm_is_small(M, N) && !(g_gemm_variant & 8)) {
-    dim3 gs(nq_cdiv(M, SM), nq_cdiv(N, SM), 1);
-    if (C2_silu) hipLaunchKernelGGL((k_gemm_small<true, EPI_SILU>), gs, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_gemm_small<true, EPI_STORE>), gs, dim3(256), 0, st, p);
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  dim3 grid(nq_cdiv(M, BM), nq_cdiv(N, BN), 1);
-  if (C2_silu) launch_gemm<true, true, EPI_SILU>(st, grid, p);
-  else launch_gemm<true, true, EPI_STORE>(st, grid, p);
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  GEMM_PROLOGUE(st, "nt", tag, M, N, K);
+  GemmArgs p = gemm_args(A, W, C, M, N, K, lda, ldw, ldc);
+  p.bias = bias; p.C2 = C2_silu;
+  if (C2_silu) return launch_product<true, true, EPI_SILU>(st, p, K);
+  int rc;
+  if (try_splitk<true, true>(st, p, bias, 0, rc)) { NQ_TRY(rc); NQ_LAUNCH_CHECK(); return NQ_OK; }
+  return launch_product<true, true, EPI_STORE>(st, p, K);
 }
 
 // C[M, N] = A W^T and C2 = ea * resid + eb * silu(C)  (Dense + ScaledSiLU + residual of the GemNet-OC blocks in one pass)
 int nq_gemm_nt_act(hipStream_t st, const float* A, const float* W, float* C, float* C2, const float* resid, float ea, float eb, int M, int N, int K,
-                   const char* tag) {
-  char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nt:%s[n=%d,k=%d]", tag ? tag : "", N, K); else nm__[0] = 0;
-  NQ_PROF(st, nm__);
-  NQ_PROF_FLOPS(2.0 * M * N * K);
-  if (M <= 0) return NQ_OK;
-  GemmArgs p{A, W, C, nullptr, C2, M, N, K, K, K, N, 0, 0, nullptr, 0};
-  p.resid = resid; p.ea = ea; p.eb = eb;
-  if (gemm3_ok<true, true>(p, K, 1)) {
-    NQ_TRY((launch_gemm3<true, true, EPI_SILU_RES>(st, p, 1)));
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  if (gemm2_ok<true, true>(p, K)) {
-    launch_gemm2<true, true, EPI_SILU_RES>(st, p, 1);
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  if (gemm_is_small(M, N) && !(g_gemm_variant & 8)) {
-    dim3 gs(nq_cdiv(M, SM), nq_cdiv(N, SM), 1);
-    hipLaunchKernelGGL((k_gemm_small<true, EPI_SILU_RES>), gs, dim3(256), 0, st, p);
-  } else {
-    dim3 grid(nq_cdiv(M, BM), nq_cdiv(N, BN), 1);
-    launch_gemm<true, true, EPI_SILU_RES>(st, grid, p);
-  }
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+                   const char* tag = nullptr) {
+  GEMM_PROLOGUE(st, "nt", tag, M, N, K);
+  GemmArgs p = gemm_args(A, W, C, M, N, K, K, K, N);
+  p.C2 = C2; gemm_aux(p, resid, ea, eb);
+  return launch_product<true, true, EPI_SILU_RES>(st, p, K);
 }
 
 // C[M, N] = A W^T (no bias) and C2 = C * silu'(aux): the tangent of a Linear + SiLU layer in one pass (aux = the primal pre-activation Z, C = the tangent
 // pre-activation, C2 = the tangent of the activation); leading dimensions = the matrix widths
 int nq_gemm_nt_dsilu(hipStream_t st, const float* A, const float* W, float* C, float* C2, const float* aux, int M, int N, int K, const char* tag) {
-  char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nt:%s[n=%d,k=%d]", tag ? tag : "", N, K); else nm__[0] = 0;
-  NQ_PROF(st, nm__);
-  NQ_PROF_FLOPS(2.0 * M * N * K);
-  if (M <= 0) return NQ_OK;
-  GemmArgs p{A, W, C, nullptr, C2, M, N, K, K, K, N, 0, 0, nullptr, 0};
-  p.resid = aux; p.ea = 0.f; p.eb = 1.f;
-  if (gemm3_ok<true, true>(p, K, 1)) {
-    NQ_TRY((launch_gemm3<true, true, EPI_DSILU2>(st, p, 1)));
-  } else if (gemm2_ok<true, true>(p, K)) {
-    launch_gemm2<true, true, EPI_DSILU2>(st, p, 1);
-  } else if (gemm_is_small(M, N) && !(g_gemm_variant & 8)) {
-    hipLaunchKernelGGL((k_gemm_small<true, EPI_DSILU2>), dim3(nq_cdiv(M, SM), nq_cdiv(N, SM), 1), dim3(256), 0, st, p);
-  } else {
-    launch_gemm<true, true, EPI_DSILU2>(st, dim3(nq_cdiv(M, BM), nq_cdiv(N, BN), 1), p);
-  }
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  GEMM_PROLOGUE(st, "nt", tag, M, N, K);
+  GemmArgs p = gemm_args(A, W, C, M, N, K, K, K, N);
+  p.C2 = C2; gemm_aux(p, aux, 0.f, 1.f);
+  return launch_product<true, true, EPI_DSILU2>(st, p, K);
 }
 
 // C[M, N] = ea * aux + A W^T   (aux [M, N], must not alias C): the second product of a two-term sum (the +-m pairs of the SO(2) convolutions:
 // out_p = x_p W_r^T - x_m W_i^T is a plain product into t followed by this one with aux = t, ea = -1 -- no separate linear-combination pass)
 int nq_gemm_nt_res(hipStream_t st, const float* A, const float* W, float* C, const float* aux, float ea, int M, int N, int K) {
-  char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nt:[n=%d,k=%d]", N, K); else nm__[0] = 0;
-  NQ_PROF(st, nm__);
-  NQ_PROF_FLOPS(2.0 * M * N * K);
-  if (M <= 0) return NQ_OK;
-  GemmArgs p{A, W, C, nullptr, nullptr, M, N, K, K, K, N, 0, 0, nullptr, 0};
-  p.resid = aux; p.ea = ea; p.eb = 0.f;
-  if (gemm3_ok<true, true>(p, K, 1)) {
-    NQ_TRY((launch_gemm3<true, true, EPI_RES>(st, p, 1)));
-  } else if (gemm2_ok<true, true>(p, K)) {
-    launch_gemm2<true, true, EPI_RES>(st, p, 1);
-  } else if (gemm_is_small(M, N) && !(g_gemm_variant & 8)) {
-    hipLaunchKernelGGL((k_gemm_small<true, EPI_RES>), dim3(nq_cdiv(M, SM), nq_cdiv(N, SM), 1), dim3(256), 0, st, p);
-  } else {
-    launch_gemm<true, true, EPI_RES>(st, dim3(nq_cdiv(M, BM), nq_cdiv(N, BN), 1), p);
-  }
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  GEMM_PROLOGUE(st, "nt", (const char*)nullptr, M, N, K);
+  GemmArgs p = gemm_args(A, W, C, M, N, K, K, K, N);
+  gemm_aux(p, aux, ea, 0.f);
+  return launch_product<true, true, EPI_RES>(st, p, K);
 }
 
 // C[M, Kin] (+)= G[M, Nout] * W[Nout, Kin]
 int nq_gemm_nn(hipStream_t st, const float* G, const float* W, float* C, int M, int Nout, int Kin, int ldg, int ldw, int ldc,
                int accumulate, const char* tag) {
-  char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nn:%s[n=%d,k=%d]", tag ? tag : "", Kin, Nout); else nm__[0] = 0;
-  NQ_PROF(st, nm__);
-  NQ_PROF_FLOPS(2.0 * M * Nout * Kin);
-  if (M <= 0) return NQ_OK;
-  GemmArgs p{G, W, C, nullptr, nullptr, M, Kin, Nout, ldg, ldw, ldc, 0, 0, nullptr, 0};
-  {
-    int rc;
-    if (try_splitk<true, false>(st, p, nullptr, accumulate, rc)) { NQ_TRY(rc); NQ_LAUNCH_CHECK(); return NQ_OK; }
-  }
-  if (gemm3_ok<true, false>(p, Nout, 1)) {
-    if (accumulate) NQ_TRY((launch_gemm3<true, false, EPI_ACC>(st, p, 1)));
-    else NQ_TRY((launch_gemm3<true, false, EPI_STORE>(st, p, 1)));
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  if (gemm2_ok<true, false>(p, Nout)) {
-    if (accumulate) launch_gemm2<true, false, EPI_ACC>(st, p, 1);
-    else launch_gemm2<true, false, EPI_STORE>(st, p, 1);
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  if (gemm_is_small(M, Kin) && !(g_gemm_variant & 8)) {
-    dim3 gs(nq_cdiv(M, SM), nq_cdiv(Kin, SM), 1);
-    if (accumulate) hipLaunchKernelGGL((k_gemm_small<false, EPI_ACC>), gs, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_gemm_small<false, EPI_STORE>), gs, dim3(256), 0, st, p);
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  dim3 grid(nq_cdiv(M, BM), nq_cdiv(Kin, BN), 1);
-  if (accumulate) launch_gemm<true, false, EPI_ACC, 16>(st, grid, p);
-  else launch_gemm<true, false, EPI_STORE, 16>(st, grid, p);
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  GEMM_PROLOGUE(st, "nn", tag, M, Kin, Nout);
+  const GemmArgs p = gemm_args(G, W, C, M, Kin, Nout, ldg, ldw, ldc);
+  int rc;
+  if (try_splitk<true, false>(st, p, nullptr, accumulate, rc)) { NQ_TRY(rc); NQ_LAUNCH_CHECK(); return NQ_OK; }
+  return accumulate ? launch_product<true, false, EPI_ACC, 16>(st, p, Nout) : launch_product<true, false, EPI_STORE, 16>(st, p, Nout);
 }
 
 // C[M, Kin] = epilogue(G[M, Nout] * W[Nout, Kin]): mode 1: eb * v * silu'(aux), mode 2: ea * aux + v   (aux [M, Kin])
 int nq_gemm_nn_epi(hipStream_t st, const float* G, const float* W, float* C, int M, int Nout, int Kin, const float* aux, float ea, float eb, int mode, const char* tag) {
-  char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nn:%s[n=%d,k=%d]", tag ? tag : "", Kin, Nout); else nm__[0] = 0;
-  NQ_PROF(st, nm__);
-  NQ_PROF_FLOPS(2.0 * M * Nout * Kin);
-  if (M <= 0) return NQ_OK;
-  GemmArgs p{G, W, C, nullptr, nullptr, M, Kin, Nout, Nout, Kin, Kin, 0, 0, nullptr, 0};
-  p.resid = aux; p.ea = ea; p.eb = eb;
-  if (gemm3_ok<true, false>(p, Nout, 1)) {
-    if (mode == 1) NQ_TRY((launch_gemm3<true, false, EPI_DSILU>(st, p, 1)));
-    else NQ_TRY((launch_gemm3<true, false, EPI_RES>(st, p, 1)));
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  if (gemm2_ok<true, false>(p, Nout)) {
-    if (mode == 1) launch_gemm2<true, false, EPI_DSILU>(st, p, 1);
-    else launch_gemm2<true, false, EPI_RES>(st, p, 1);
-    NQ_LAUNCH_CHECK();
-    return NQ_OK;
-  }
-  if (gemm_is_small(M, Kin) && !(g_gemm_variant & 8)) {
-    dim3 gs(nq_cdiv(M, SM), nq_cdiv(Kin, SM), 1);
-    if (mode == 1) hipLaunchKernelGGL((k_gemm_small<false, EPI_DSILU>), gs, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_gemm_small<false, EPI_RES>), gs, dim3(256), 0, st, p);
-  } else {
-    dim3 grid(nq_cdiv(M, BM), nq_cdiv(Kin, BN), 1);
-    if (mode == 1) launch_gemm<true, false, EPI_DSILU, 16>(st, grid, p);
-    else launch_gemm<true, false, EPI_RES, 16>(st, grid, p);
-  }
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  GEMM_PROLOGUE(st, "nn", tag, M, Kin, Nout);
+  GemmArgs p = gemm_args(G, W, C, M, Kin, Nout, Nout, Kin, Kin);
+  gemm_aux(p, aux, ea, eb);
+  return mode == 1 ? launch_product<true, false, EPI_DSILU, 16>(st, p, Nout) : launch_product<true, false, EPI_RES, 16>(st, p, Nout);
 }
 
 // C = G W (the adjoint of a SiLU layer's OUTPUT) and C2 = C * silu'(aux) (the adjoint of its pre-activation) in one pass: the force sweep keeps both, because the
 // second-order sweep needs the first for its silu'' term and the second as an operand of the weight gradient (engine.hip: per-layer adjoint store)
 int nq_gemm_nn_dsilu2(hipStream_t st, const float* G, const float* W, float* C, float* C2, const float* aux, int M, int Nout, int Kin, const char* tag) {
-  char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_nn:%s[n=%d,k=%d]", tag ? tag : "", Kin, Nout); else nm__[0] = 0;
-  NQ_PROF(st, nm__);
-  NQ_PROF_FLOPS(2.0 * M * Nout * Kin);
-  if (M <= 0) return NQ_OK;
-  GemmArgs p{G, W, C, nullptr, C2, M, Kin, Nout, Nout, Kin, Kin, 0, 0, nullptr, 0};
-  p.resid = aux; p.ea = 0.f; p.eb = 1.f;
-  if (gemm3_ok<true, false>(p, Nout, 1)) NQ_TRY((launch_gemm3<true, false, EPI_DSILU2>(st, p, 1)));
-  else if (gemm2_ok<true, false>(p, Nout)) launch_gemm2<true, false, EPI_DSILU2>(st, p, 1);
-  else if (gemm_is_small(M, Kin) && !(g_gemm_variant & 8)) hipLaunchKernelGGL((k_gemm_small<false, EPI_DSILU2>), dim3(nq_cdiv(M, SM), nq_cdiv(Kin, SM), 1), dim3(256), 0, st, p);
-  else launch_gemm<true, false, EPI_DSILU2, 16>(st, dim3(nq_cdiv(M, BM), nq_cdiv(Kin, BN), 1), p);
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  GEMM_PROLOGUE(st, "nn", tag, M, Kin, Nout);
+  GemmArgs p = gemm_args(G, W, C, M, Kin, Nout, Nout, Kin, Kin);
+  p.C2 = C2; gemm_aux(p, aux, 0.f, 1.f);
+  return launch_product<true, false, EPI_DSILU2, 16>(st, p, Nout);
 }
 
-// out[Mo, No] = sum_{r<rows} GY[r, Mo] * X[r, No];  scratch must hold nq_gemm_tn_scratch_floats()
-// Split count for the weight-gradient contraction: enough workgroups to fill 256 CUs (~768) given the number
-// of 128x128 output tiles, but at least 512 rows per split so the 64-KB partial slab stays amortised.
-// Split count of the weight-gradient contraction: the persistent engine keeps 2 workgroups of 8 wavefronts per CU = 512 slots; as many
-// (output tile, row range) items as fit WITHOUT exceeding them (one item more would cost a whole extra round), at least 128 rows per split.
+// Split count of the weight-gradient contraction (K = rows): as many (output tile, row range) items as fit the engine's workgroup `slots` WITHOUT
+// exceeding them (one item more would cost a whole extra round), at least 128 rows (4 k-tiles) per split.
 static int tn_splits(long rows, int Mo, int No, int slots) {
   const long tiles = (long)nq_cdiv(Mo, BM) * nq_cdiv(No, BN);
   long s = slots / tiles;
-  const long by_rows = (rows + 127) / 128;   // >= 128 rows (4 k-tiles) per split
+  const long by_rows = (rows + 127) / 128;
   if (s > by_rows) s = by_rows;
   if (s < 1) s = 1;
   return (int)s;
@@ -818,11 +730,10 @@ static int tn_slots(bool with_bias) { return (gemm3_disabled() || with_bias) ? 5
 // (sized for the larger split count: the engine choice may change between the sizing call and the product)
 size_t nq_gemm_tn_scratch_floats(long rows, int Mo, int No) { return (size_t)tn_splits(rows, Mo, No, 768) * ((size_t)Mo * No + Mo); }
 
+// out[Mo, No] = sum_{r<rows} GY[r, Mo] * X[r, No];  scratch must hold nq_gemm_tn_scratch_floats()
 int nq_gemm_tn(hipStream_t st, const float* GY, const float* X, float* out, long rows, int Mo, int No, int ldg, int ldx, float* scratch,
                const char* tag, float* bias_out, long bias_rows) {
-  char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_tn:%s[%dx%d]", tag ? tag : "", Mo, No); else nm__[0] = 0;
-  NQ_PROF(st, nm__);
-  NQ_PROF_FLOPS(2.0 * rows * Mo * No);
+  GEMM_PROF(st, "gemm_tn:%s[%dx%d]", tag, Mo, No, 2.0 * rows * Mo * No);
   if (rows <= 0) {
     NQ_HIP(hipMemsetAsync(out, 0, sizeof(float) * Mo * No, st));
     if (bias_out) NQ_HIP(hipMemsetAsync(bias_out, 0, sizeof(float) * Mo, st));
@@ -832,24 +743,22 @@ int nq_gemm_tn(hipStream_t st, const float* GY, const float* X, float* out, long
   // The split count belongs to the engine that RUNS: sized for the split engine's 3 x 256 workgroup slots first; if that launch turns out not to be
   // eligible for it (operand alignment, M / N not multiples of 4, too few tiles) the count is taken again for the 2 x 256 slots of the exact / generic
   // engines (they used to inherit a split count tuned for the other engine).
-  int ns = 0, kper = 0, nse = 0;
+  int kper = 0, nse = 0;
   float* bpart = nullptr;
   GemmArgs p{};
   auto plan = [&](int slots) {
-    ns = tn_splits(rows, Mo, No, slots);
+    const int ns = tn_splits(rows, Mo, No, slots);
     kper = (int)((rows + ns - 1) / ns);
     kper = (kper + 31) / 32 * 32;   // whole k-tiles (BKT = 32 for the TN launches)
     bpart = bias_out ? scratch + (size_t)ns * Mo * No : nullptr;
-    p = GemmArgs{GY, X, scratch, nullptr, nullptr, Mo, No, (int)rows, ldg, ldx, No, kper, (long)Mo * No, bpart, (int)bias_rows};
+    p = gemm_args(GY, X, scratch, Mo, No, (int)rows, ldg, ldx, No);
+    p.k_per_split = kper; p.part_stride = (long)Mo * No; p.bpart = bpart; p.brows = (int)bias_rows;
     nse = nq_cdiv(rows, kper);      // splits that actually hold rows (<= ns); only their slabs are reduced
   };
   const int slots0 = tn_slots(bias_out != nullptr);
   plan(slots0);
   if (slots0 != 512 && !gemm3_ok<false, false>(p, kper, nse)) plan(512);
-  if (gemm3_ok<false, false>(p, kper, nse)) NQ_TRY((launch_gemm3<false, false, EPI_PARTIAL>(st, p, nse)));
-  else if (gemm2_ok<false, false>(p, kper)) launch_gemm2<false, false, EPI_PARTIAL>(st, p, nse);
-  else launch_gemm<false, false, EPI_PARTIAL>(st, dim3(nq_cdiv(Mo, BM), nq_cdiv(No, BN), nse), p);
-  NQ_LAUNCH_CHECK();
+  NQ_TRY((launch_product<false, false, EPI_PARTIAL>(st, p, kper, nse)));
   const long cnt = (long)Mo * No;
   if (bias_out) {   // weights and bias in one launch (the reduction order of each is the one k_reduce_partials uses)
     const unsigned ba = reduce_partials_blocks(nse, cnt), bb = reduce_partials_blocks(nse, (long)Mo);
@@ -917,57 +826,77 @@ __global__ void k_reduce_grouped(const float* __restrict__ part, int s, long cnt
   o.out[L][i] = (a0 + a1) + (a2 + a3);
 }
 
+// Forward (B_KC: y_L = x_L W_L^T, bias on the scalars) and input gradient (!B_KC: gx_L = gy_L W_L) of all orders; W_L: [Fout][Fin]
+template <bool B_KC>
+static int sph_linear(const float* in, const float* const* W_host, const float* bias0, float* out, int64_t rows, int32_t order, int32_t Fin, int32_t Fout,
+                      const char* name, hipStream_t st) {
+  NQ_TRY(sph_check(rows, order, Fin, Fout));
+  if (!in || !W_host || !out) return nq_fail(NQ_ERR_ARG, "null argument");
+  NQ_PROF(st, name);
+  NQ_PROF_FLOPS(2.0 * rows * (order + 1) * (order + 1) * Fin * Fout);
+  if (rows == 0) return NQ_OK;
+  const int ncomp = (order + 1) * (order + 1), K = B_KC ? Fin : Fout, N = B_KC ? Fout : Fin;
+  GemmArgs p = gemm_args(in, nullptr, out, (int)rows * (2 * order + 1), N, K, K, Fin, N);
+  p.bias = bias0; p.rm_rows = (int)rows; p.rm_ncomp = ncomp;
+  for (int L = 0; L <= order; ++L) { if (!W_host[L]) return nq_fail(NQ_ERR_ARG, "null weight"); p.Bz[L] = W_host[L]; }
+  p.B = p.Bz[0];
+  {   // one plain strided product per packed component on the tile engines (rows x K, leading dimension ncomp * K)
+    GemmArgs b = p;
+    b.M = (int)rows; b.lda = ncomp * K; b.ldc = ncomp * N; b.nbatch = ncomp; b.bz = 1; b.bsA = K; b.bsB = 0; b.bsC = N;
+    if (launch_batched<true, B_KC, EPI_STORE>(st, b, 1, K)) { NQ_LAUNCH_CHECK(); return NQ_OK; }
+  }
+  dim3 grid(nq_cdiv(p.M, BM), nq_cdiv(N, BN), order + 1);
+  hipLaunchKernelGGL((k_gemm<true, B_KC, EPI_STORE, 8, true, B_KC ? 32 : 16, 1>), grid, dim3(512), 0, st, p);
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+
 extern "C" {
+
+int nq_linear_forward(const float* A, const float* Wt, const float* bias, float* C, float* C_silu, int32_t M, int32_t N, int32_t K, void* stream) {
+  return nq_gemm_nt((hipStream_t)stream, A, Wt, C, bias, C_silu, M, N, K, K, K, N);
+}
+int nq_linear_forward_act(const float* A, const float* Wt, float* C, float* C_act, const float* resid, float alpha, float beta, int32_t M, int32_t N, int32_t K,
+                          void* stream) {
+  if (!A || !Wt || !C || !C_act) return nq_fail(NQ_ERR_ARG, "null argument");
+  return nq_gemm_nt_act((hipStream_t)stream, A, Wt, C, C_act, resid, alpha, beta, M, N, K);
+}
+int nq_linear_forward_res(const float* A, const float* Wt, const float* aux, float alpha, float* C, int32_t M, int32_t N, int32_t K, void* stream) {
+  if (!A || !Wt || !C || !aux) return nq_fail(NQ_ERR_ARG, "null argument");
+  if (aux == C) return nq_fail(NQ_ERR_ARG, "nq_linear_forward_res: aux must not alias C");
+  return nq_gemm_nt_res((hipStream_t)stream, A, Wt, C, aux, alpha, M, N, K);
+}
+int nq_linear_input_grad(const float* G, const float* Wt, float* C, int32_t M, int32_t N, int32_t K, int32_t accumulate, void* stream) {
+  return nq_gemm_nn((hipStream_t)stream, G, Wt, C, M, N, K, N, K, K, accumulate);
+}
+int nq_linear_input_grad_epi(const float* G, const float* Wt, float* C, int32_t M, int32_t N, int32_t K, const float* aux, float alpha, float beta, int32_t mode,
+                             void* stream) {
+  if (!G || !Wt || !C || !aux || (mode != 1 && mode != 2)) return nq_fail(NQ_ERR_ARG, "bad argument");
+  return nq_gemm_nn_epi((hipStream_t)stream, G, Wt, C, M, N, K, aux, alpha, beta, mode);
+}
+size_t nq_column_sum_scratch_floats(int64_t rows, int32_t cols) { return nq_colsum_scratch_floats((long)rows, cols); }
+int nq_column_sum(const float* A, int64_t rows, int32_t cols, int64_t lda, float* out, float* scratch, void* stream) {
+  if (!A || !out || !scratch || cols < 1 || lda < cols) return nq_fail(NQ_ERR_ARG, "column_sum: bad argument");
+  return nq_colsum((hipStream_t)stream, A, (long)rows, cols, (int)lda, out, scratch);
+}
+size_t nq_weight_grad_scratch_floats(int64_t rows, int32_t N, int32_t K) { return nq_gemm_tn_scratch_floats(rows, N, K); }
+int nq_linear_weight_grad(const float* G, const float* X, float* gW, int64_t rows, int32_t N, int32_t K, float* scratch, void* stream) {
+  return nq_gemm_tn((hipStream_t)stream, G, X, gW, rows, N, K, N, K, scratch);
+}
+int nq_linear_weight_grad_bias(const float* G, const float* X, float* gW, float* gb, int64_t rows, int32_t N, int32_t K, float* scratch, void* stream) {
+  if (!gb) return nq_fail(NQ_ERR_ARG, "null bias gradient");
+  return nq_gemm_tn((hipStream_t)stream, G, X, gW, rows, N, K, N, K, scratch, nullptr, gb, rows);
+}
 
 int nq_sph_linear_forward(const float* x, const float* const* W_host, const float* bias0, float* y, int64_t rows, int32_t order, int32_t Fin,
                           int32_t Fout, void* stream) {
-  NQ_TRY(sph_check(rows, order, Fin, Fout));
-  if (!x || !W_host || !y) return nq_fail(NQ_ERR_ARG, "null argument");
-  hipStream_t st = (hipStream_t)stream;
-  NQ_PROF(st, "sph_linear_fwd");
-  NQ_PROF_FLOPS(2.0 * rows * (order + 1) * (order + 1) * Fin * Fout);
-  if (rows == 0) return NQ_OK;
-  const int ncomp = (order + 1) * (order + 1);
-  GemmArgs p{};
-  p.A = x; p.C = y; p.bias = bias0; p.M = (int)rows * (2 * order + 1); p.N = Fout; p.K = Fin; p.lda = Fin; p.ldb = Fin; p.ldc = Fout;
-  p.rm_rows = (int)rows; p.rm_ncomp = ncomp;
-  for (int L = 0; L <= order; ++L) { if (!W_host[L]) return nq_fail(NQ_ERR_ARG, "null weight"); p.Bz[L] = W_host[L]; }
-  p.B = p.Bz[0];
-  {   // one plain strided product per packed component on the tile engines (rows x Fin, leading dimension ncomp * Fin)
-    GemmArgs b = p;
-    b.M = (int)rows; b.lda = ncomp * Fin; b.ldc = ncomp * Fout; b.nbatch = ncomp; b.bz = 1; b.bsA = Fin; b.bsB = 0; b.bsC = Fout;
-    if (launch_batched<true, true, EPI_STORE>(st, b, 1, Fin)) { NQ_LAUNCH_CHECK(); return NQ_OK; }
-  }
-  dim3 grid(nq_cdiv(p.M, BM), nq_cdiv(Fout, BN), order + 1);
-  hipLaunchKernelGGL((k_gemm<true, true, EPI_STORE, 8, true, 32, 1>), grid, dim3(512), 0, st, p);
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  return sph_linear<true>(x, W_host, bias0, y, rows, order, Fin, Fout, "sph_linear_fwd", (hipStream_t)stream);
 }
 
 // gx_L = gy_L W_L   (W_L: [Fout][Fin])
 int nq_sph_linear_input_grad(const float* gy, const float* const* W_host, float* gx, int64_t rows, int32_t order, int32_t Fin, int32_t Fout,
                              void* stream) {
-  NQ_TRY(sph_check(rows, order, Fin, Fout));
-  if (!gy || !W_host || !gx) return nq_fail(NQ_ERR_ARG, "null argument");
-  hipStream_t st = (hipStream_t)stream;
-  NQ_PROF(st, "sph_linear_bwd_x");
-  NQ_PROF_FLOPS(2.0 * rows * (order + 1) * (order + 1) * Fin * Fout);
-  if (rows == 0) return NQ_OK;
-  const int ncomp = (order + 1) * (order + 1);
-  GemmArgs p{};
-  p.A = gy; p.C = gx; p.M = (int)rows * (2 * order + 1); p.N = Fin; p.K = Fout; p.lda = Fout; p.ldb = Fin; p.ldc = Fin;
-  p.rm_rows = (int)rows; p.rm_ncomp = ncomp;
-  for (int L = 0; L <= order; ++L) { if (!W_host[L]) return nq_fail(NQ_ERR_ARG, "null weight"); p.Bz[L] = W_host[L]; }
-  p.B = p.Bz[0];
-  {
-    GemmArgs b = p;
-    b.M = (int)rows; b.lda = ncomp * Fout; b.ldc = ncomp * Fin; b.nbatch = ncomp; b.bz = 1; b.bsA = Fout; b.bsB = 0; b.bsC = Fin;
-    if (launch_batched<true, false, EPI_STORE>(st, b, 1, Fout)) { NQ_LAUNCH_CHECK(); return NQ_OK; }
-  }
-  dim3 grid(nq_cdiv(p.M, BM), nq_cdiv(Fin, BN), order + 1);
-  hipLaunchKernelGGL((k_gemm<true, false, EPI_STORE, 8, true, 16, 1>), grid, dim3(512), 0, st, p);
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  return sph_linear<false>(gy, W_host, nullptr, gx, rows, order, Fin, Fout, "sph_linear_bwd_x", (hipStream_t)stream);
 }
 
 size_t nq_sph_weight_grad_scratch_floats(int64_t rows, int32_t order, int32_t Fin, int32_t Fout) {
@@ -1016,14 +945,12 @@ int nq_sph_linear_weight_grad(const float* gy, const float* x, float* const* gW_
     const long cnt = (long)Fout * Fin;
     hipLaunchKernelGGL(k_reduce_grouped, dim3(nq_cdiv(cnt, 64), order + 1), dim3(64), 0, st, scratch, sps, cnt, outs);
     NQ_LAUNCH_CHECK();
-  }
-  if (gbias0) {
-    if (rows == 0) NQ_HIP(hipMemsetAsync(gbias0, 0, sizeof(float) * Fout, st));
-    else {   // fixed-order sum of the per-split partials written by the contraction above (no separate pass over gy)
-      const int sps = sph_tn_splits(rows, ncomp);
-      LAUNCH_REDUCE_PARTIALS(st, scratch + (size_t)ncomp * sps * Fout * Fin, sps, (long)Fout, (long)Fout, gbias0);
+    if (gbias0) {   // fixed-order sum of the per-split partials written by the contraction above (no separate pass over gy)
+      LAUNCH_REDUCE_PARTIALS(st, bpart, sps, (long)Fout, (long)Fout, gbias0);
       NQ_LAUNCH_CHECK();
     }
+  } else if (gbias0) {
+    NQ_HIP(hipMemsetAsync(gbias0, 0, sizeof(float) * Fout, st));
   }
   return NQ_OK;
 }
