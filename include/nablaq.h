@@ -667,6 +667,58 @@ int nq_lbfgs_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, 
 int nq_lbfgs_step(void* state, int32_t N, int32_t B, int32_t memory, int32_t n_small, const void* forces, int32_t forces_f64, const uint8_t* fixed_mask,
                   float* pos32, double fmax, double maxstep, double damping, double alpha, int32_t evaluate_only, void* stream);
 
+/* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
+ * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,
+ * row-major behind pair_ptr int64[B+1] (P = pair_ptr[B]).  "head-major" = per molecule [H][n][n] starting at H * pair_ptr[b]: the layout of the attention bias,
+ * of its accumulated adjoint and of the uint8 dropout keep masks.  max_mol_atoms = the largest n_b of the batch, at most nq_g3d_max_mol_atoms() (above:
+ * NQ_ERR_MOL_TOO_LARGE).  All sums have a fixed order (bitwise reproducible).
+ * Pair featuriser (:126-146 GaussianLayer, :283-293): d = |pos_j - pos_i|, unit = (pos_j - pos_i) / (d + 1e-5), x = mul[64 z_i + z_j] d + bias[...],
+ * gbf[p][k] = exp(-((x - means[k]) / s_k)^2 / 2) / (sqrt(2 * 3.14159) s_k), s_k = |stds[k]| + 1e-5; efeat[i] = sum_j gbf[(i, j)].  K <= 256; the caller
+ * guarantees 0 < z < 64.  Backward: adjoints of means / stds [K] and mul / bias [4096] from grad_gbf [P][K] and / or grad_efeat [N][K] (either nullable; the
+ * latter is broadcast over j in the kernel); order int64[P] = the pairs sorted by edge type, type_ptr int64[4097] = start of each type's run. */
+int32_t nq_g3d_max_mol_atoms(void);
+int nq_g3d_pair_forward(const float* pos, const int32_t* z, const int32_t* ptr, const int32_t* atom_mol, const int64_t* pair_ptr, const float* mul, const float* bias,
+                        const float* means, const float* stds, int32_t N, int32_t K, int32_t max_mol_atoms, float* gbf, float* unit, float* dist, float* efeat,
+                        void* stream);
+size_t nq_g3d_pair_scratch_floats(int32_t N, int64_t P, int32_t K);
+int nq_g3d_pair_backward(const float* pos, const int32_t* z, const int32_t* ptr, const int32_t* atom_mol, const int64_t* pair_ptr, const float* mul, const float* bias,
+                         const float* means, const float* stds, const float* dist, const int64_t* order, const int64_t* type_ptr, int32_t N, int64_t P, int32_t K,
+                         const float* grad_gbf, const float* grad_efeat, float* grad_means, float* grad_stds, float* grad_mul, float* grad_bias, float* scratch,
+                         void* stream);
+/* :300-303: attention bias [P][H] -> head-major and back (the adjoint of the first is the second). */
+int nq_g3d_bias_to_heads(const float* pair_major, const int32_t* ptr, const int32_t* atom_mol, const int64_t* pair_ptr, int32_t N, int32_t H, float* head_major,
+                         void* stream);
+int nq_g3d_bias_from_heads(const float* head_major, const int32_t* ptr, const int32_t* atom_mol, const int64_t* pair_ptr, int32_t N, int32_t H, float* pair_major,
+                           void* stream);
+/* :40-59 SelfMultiheadAttention between in_proj and out_proj: qkv [N][3 H D] (q | k | v), D = 16 or 32; out [N][H D] = softmax((q scaling) k^T + bias)
+ * (* keep_mask * mask_scale when keep_mask is given) v; lse [N][H] = row log-sum-exp.  Backward recomputes the probabilities from lse: grad_qkv [N][3 H D] is
+ * written, grad_bias_heads (head-major) is ADDED TO in place; scratch: N * H floats. */
+int nq_g3d_attention_forward(const float* qkv, const float* bias_heads, const uint8_t* keep_mask, float mask_scale, const int32_t* ptr, const int64_t* pair_ptr,
+                             int32_t B, int32_t N, int32_t H, int32_t D, int32_t max_mol_atoms, float scaling, float* out, float* lse, void* stream);
+int nq_g3d_attention_backward(const float* qkv, const float* bias_heads, const uint8_t* keep_mask, float mask_scale, const int32_t* ptr, const int64_t* pair_ptr,
+                              int32_t B, int32_t N, int32_t H, int32_t D, int32_t max_mol_atoms, float scaling, const float* out, const float* lse,
+                              const float* grad_out, float* grad_qkv, float* grad_bias_heads, float* scratch, void* stream);
+/* :185-224 NodeTaskHead after q_proj / k_proj / v_proj (qkv [N][3 H D]): forces[i][c] = b3[c] + sum_h sum_j P_hij unit[(i, j)][c] (v_jh . W3[c][h D ..]),
+ * W3 [3][H D] = force_proj{1,2,3}.weight, b3 [3] their biases; head_forces [N][H][3] and lse [N][H] are kept for the backward, which writes grad_qkv,
+ * grad_W3, grad_b3 and adds to grad_bias_heads; scratch: nq_g3d_force_scratch_floats floats. */
+int nq_g3d_force_forward(const float* qkv, const float* bias_heads, const uint8_t* keep_mask, float mask_scale, const float* unit, const float* W3, const float* b3,
+                         const int32_t* ptr, const int64_t* pair_ptr, int32_t B, int32_t N, int32_t H, int32_t D, int32_t max_mol_atoms, float scaling,
+                         float* head_forces, float* lse, float* forces, void* stream);
+size_t nq_g3d_force_scratch_floats(int32_t N, int32_t H, int32_t D);
+int nq_g3d_force_backward(const float* qkv, const float* bias_heads, const uint8_t* keep_mask, float mask_scale, const float* unit, const float* W3,
+                          const int32_t* ptr, const int64_t* pair_ptr, int32_t B, int32_t N, int32_t H, int32_t D, int32_t max_mol_atoms, float scaling,
+                          const float* head_forces, const float* lse, const float* grad_forces, float* grad_qkv, float* grad_bias_heads, float* grad_W3,
+                          float* grad_b3, float* scratch, void* stream);
+/* :111, :180 F.gelu (exact, erf) of x [rows][C] + bias [C] (nullable); backward: grad_x = grad_y gelu'(x + bias). */
+int nq_g3d_gelu_forward(const float* x, const float* bias, int64_t rows, int32_t C, float* y, void* stream);
+int nq_g3d_gelu_backward(const float* x, const float* bias, const float* grad_y, int64_t rows, int32_t C, float* grad_x, void* stream);
+/* :311-312 energy_proj.layer2 (Linear C -> 1): y[r] = x[r] . w + b[0]; backward: grad_x [rows][C], grad_w [C], grad_b [1]; scratch:
+ * nq_g3d_rowdot_scratch_floats floats. */
+int nq_g3d_rowdot_forward(const float* x, const float* w, const float* b, int64_t rows, int32_t C, float* y, void* stream);
+size_t nq_g3d_rowdot_scratch_floats(int64_t rows, int32_t C);
+int nq_g3d_rowdot_backward(const float* x, const float* w, const float* grad_y, int64_t rows, int32_t C, float* grad_x, float* grad_w, float* grad_b, float* scratch,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

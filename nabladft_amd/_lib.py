@@ -204,6 +204,22 @@ SYMBOLS = {
     "nq_lbfgs_state_layout": (C.c_int, [_I32, _I32, _I32, C.POINTER(_SZ)]),
     "nq_lbfgs_init": (C.c_int, [_P, _SZ, _P, _I32, _I32, _I32, _P, _I32, _P, C.POINTER(C.c_int32), _P]),
     "nq_lbfgs_step": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _D, _D, _D, _D, _I32, _P]),
+    "nq_g3d_max_mol_atoms": (C.c_int32, []),
+    "nq_g3d_pair_forward": (C.c_int, [_P] * 9 + [_I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "nq_g3d_pair_scratch_floats": (_SZ, [_I32, _I64, _I32]),
+    "nq_g3d_pair_backward": (C.c_int, [_P] * 12 + [_I32, _I64, _I32] + [_P] * 8),
+    "nq_g3d_bias_to_heads": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "nq_g3d_bias_from_heads": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "nq_g3d_attention_forward": (C.c_int, [_P, _P, _P, _F, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),
+    "nq_g3d_attention_backward": (C.c_int, [_P, _P, _P, _F, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "nq_g3d_force_forward": (C.c_int, [_P, _P, _P, _F, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
+    "nq_g3d_force_scratch_floats": (_SZ, [_I32, _I32, _I32]),
+    "nq_g3d_force_backward": (C.c_int, [_P, _P, _P, _F, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nq_g3d_gelu_forward": (C.c_int, [_P, _P, _I64, _I32, _P, _P]),
+    "nq_g3d_gelu_backward": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
+    "nq_g3d_rowdot_forward": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
+    "nq_g3d_rowdot_scratch_floats": (_SZ, [_I64, _I32]),
+    "nq_g3d_rowdot_backward": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
