@@ -719,6 +719,44 @@ size_t nq_g3d_rowdot_scratch_floats(int64_t rows, int32_t C);
 int nq_g3d_rowdot_backward(const float* x, const float* w, const float* grad_y, int64_t rows, int32_t C, float* grad_x, float* grad_w, float* grad_b, float* scratch,
                            void* stream);
 
+/* ---- DimeNet++ building blocks (csrc/dimenet.hip; the core as restated in DESIGN_details.md) ----------------------------------------------------------------
+ * Graph: CSR by target atom as nq_es_graph_* builds it (row_ptr int32[N+1], src / dst int32[E], sources ascending inside a row, geom [E][4] =
+ * {pos[src] - pos[dst], |.|}) plus the edges sorted by source for the transposed walks (src_order int32[E], src_ptr int32[N+1]).  Edge (j->i) has d = |pos_i -
+ * pos_j| and u = (pos_i - pos_j) / d; its triplets are the in-row of j without k = i (never stored).  All sums have a fixed order (bitwise reproducible).
+ * Geometry: backward turns grad_d [E] / grad_u [E][3] (either nullable) into grad_vec [E][3] (scratch) and grad_pos [N][3]. */
+int nq_dn_geom_forward(const float* geom, int64_t E, float* d, float* u, void* stream);
+int nq_dn_geom_backward(const float* d, const float* u, const float* grad_d, const float* grad_u, const int32_t* row_ptr, const int32_t* src_order,
+                        const int32_t* src_ptr, int32_t N, int64_t E, float* grad_vec, float* grad_pos, void* stream);
+/* x = d / cutoff, env(x) = 1/x + a x^(p-1) + b x^p + c x^(p+1); rbf[e][n] = env sin(freq[n] x); rad[e][l][n] = env norms[l][n] j_l(roots[l][n] x), evaluated in
+ * float64 (series below x = l, upward recurrence above) and rounded once; roots / norms: float64 [S][R].  S <= 8, R <= 16, 2 <= p <= 16.  Backward: grad_d [E] and
+ * the per-edge rows grad_freq_rows [E][R] (their column sum is the gradient of freq); grad_rbf / grad_rad nullable. */
+int nq_dn_basis_forward(const float* d, const float* freq, const double* roots, const double* norms, int64_t E, int32_t S, int32_t R, double cutoff,
+                        int32_t envelope_p, float* rbf, float* rad, void* stream);
+int nq_dn_basis_backward(const float* d, const float* freq, const double* roots, const double* norms, int64_t E, int32_t S, int32_t R, double cutoff,
+                         int32_t envelope_p, const float* grad_rbf, const float* grad_rad, float* grad_d, float* grad_freq_rows, void* stream);
+/* m[(j->i)][c] = sum over (k->j), k != i of x_kj[(k->j)][c] sum_b W_sbf2[c][b] sum_l Y_l(u_ji . u_kj) Q[(k->j)][l][b], Y_l = sqrt((2l+1) / 4 pi) P_l;
+ * x_kj [E][I], Q [E][S][Bs], W_sbf2 [I][Bs]; I = 64, 128, 192 or 256, S <= 8, Bs <= 8.  Backward writes grad_x [E][I], grad_Q [E][S][Bs], grad_u [E][3] (both
+ * edges of every triplet) and, unless it is NULL, grad_W_sbf2 [I][Bs]; scratch: nq_dn_triplet_scratch_floats floats (needed only with grad_W_sbf2). */
+int nq_dn_triplet_forward(const float* x_kj, const float* Q, const float* u, const float* W_sbf2, const int32_t* row_ptr, const int32_t* src, const int32_t* dst,
+                          int32_t E, int32_t I, int32_t S, int32_t Bs, float* m, void* stream);
+size_t nq_dn_triplet_scratch_floats(int32_t E, int32_t I, int32_t Bs);
+int nq_dn_triplet_backward(const float* x_kj, const float* Q, const float* u, const float* W_sbf2, const int32_t* row_ptr, const int32_t* src, const int32_t* dst,
+                           const int32_t* src_order, const int32_t* src_ptr, int32_t E, int32_t I, int32_t S, int32_t Bs, const float* grad_m, float* grad_x,
+                           float* grad_Q, float* grad_u, float* grad_W_sbf2, float* scratch, void* stream);
+/* y = x * gate (elementwise, count floats) and its two adjoints. */
+int nq_dn_gate_forward(const float* x, const float* gate, int64_t count, float* y, void* stream);
+int nq_dn_gate_backward(const float* x, const float* gate, const float* grad_y, int64_t count, float* grad_x, float* grad_gate, void* stream);
+/* out[i] = sum over the in-edges e of atom i of x[e] * gate[e] ([E][H] -> [N][H]). */
+int nq_dn_gatesum_forward(const float* x, const float* gate, const int32_t* row_ptr, int32_t N, int32_t H, float* out, void* stream);
+int nq_dn_gatesum_backward(const float* x, const float* gate, const float* grad_out, const int32_t* dst, int64_t E, int32_t H, float* grad_x, float* grad_gate,
+                           void* stream);
+/* Embedding block after its dense products: pre[e] = AB[dst[e]][:H] + AB[src[e]][H:] + Cr[e] + bias, y = silu(pre); AB [N][2H], Cr [E][H].  Backward: grad_pre
+ * [E][H] (= the adjoint of Cr; its column sum is the adjoint of bias) and grad_AB [N][2H]. */
+int nq_dn_embed_forward(const float* AB, const float* Cr, const float* bias, const int32_t* src, const int32_t* dst, int64_t E, int32_t H, float* pre, float* y,
+                        void* stream);
+int nq_dn_embed_backward(const float* pre, const float* grad_y, const int32_t* row_ptr, const int32_t* src_order, const int32_t* src_ptr, int32_t N, int64_t E,
+                         int32_t H, float* grad_pre, float* grad_AB, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

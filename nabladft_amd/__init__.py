@@ -13,6 +13,8 @@ Public surface mirrors the reference plugin classes for this path:
   nabladft_amd.EquiformerV2_OC20 <-> nablaDFT.equiformer_v2.EquiformerV2_OC20 (equiformer_v2/equiformer_v2_oc20.py:51-640)
   nabladft_amd.EquiformerV2_OC20_Lightning <-> nablaDFT.equiformer_v2.EquiformerV2_OC20_Lightning (equiformer_v2/equiformer_v2_oc20.py:643-817)
   nabladft_amd.Graphormer3D / Graphormer3DLightning <-> nablaDFT.graphormer.Graphormer3D / Graphormer3DLightning (graphormer/graphormer_3d.py:227-483)
+  nabladft_amd.DimeNetPlusPlusPotential / DimeNetPlusPlusLightning <-> nablaDFT.dimenetplusplus.* (dimenetplusplus/dimenetplusplus.py:22-270; the
+                                    torch-geometric core restated, unpinned)
   nabladft_amd.AtomisticTaskFixed <-> nablaDFT.ase_model.AtomisticTaskFixed (ase_model/task.py:9-73)
   nabladft_amd.ASEBatchwiseLBFGS / PyGBatchwiseCalculator / BatchwiseOptimizeTask <-> nablaDFT.optimization.* (optimizers.py:293-605, calculator.py:98-132,
                                     task.py:9-73): the `optimize` job, L-BFGS state on the device (optimization.py)
@@ -26,11 +28,12 @@ from .gemnet_oc import GemNetOC  # noqa: F401
 from .escn import eSCN  # noqa: F401
 from .equiformer_v2 import EquiformerV2_OC20  # noqa: F401
 from .graphormer import Graphormer3D, Graphormer3DLightning  # noqa: F401
+from .dimenetplusplus import DimeNetPlusPlusLightning, DimeNetPlusPlusPotential  # noqa: F401
 from . import ema, schedulers  # noqa: F401
 from .trainer import FusedTrainStep, Batch  # noqa: F401
 from . import optimization  # noqa: F401
 from .optimization import ASEBatchwiseLBFGS, BatchwiseOptimizeTask, PyGBatchwiseCalculator  # noqa: F401
 from .data import ArenaLoader, ConformerArena, HamiltonianBatch, HamiltonianDatabase, HamiltonianDataset, hamiltonian_batch, read_energy_database  # noqa: F401
 
-__all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
+__all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
            "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask"]

@@ -220,6 +220,19 @@ SYMBOLS = {
     "nq_g3d_rowdot_forward": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P]),
     "nq_g3d_rowdot_scratch_floats": (_SZ, [_I64, _I32]),
     "nq_g3d_rowdot_backward": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
+    "nq_dn_geom_forward": (C.c_int, [_P, _I64, _P, _P, _P]),
+    "nq_dn_geom_backward": (C.c_int, [_P] * 7 + [_I32, _I64, _P, _P, _P]),
+    "nq_dn_basis_forward": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _D, _I32, _P, _P, _P]),
+    "nq_dn_basis_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _D, _I32, _P, _P, _P, _P, _P]),
+    "nq_dn_triplet_forward": (C.c_int, [_P] * 7 + [_I32, _I32, _I32, _I32, _P, _P]),
+    "nq_dn_triplet_scratch_floats": (_SZ, [_I32, _I32, _I32]),
+    "nq_dn_triplet_backward": (C.c_int, [_P] * 9 + [_I32, _I32, _I32, _I32] + [_P] * 7),
+    "nq_dn_gate_forward": (C.c_int, [_P, _P, _I64, _P, _P]),
+    "nq_dn_gate_backward": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P]),
+    "nq_dn_gatesum_forward": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),
+    "nq_dn_gatesum_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
+    "nq_dn_embed_forward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
+    "nq_dn_embed_backward": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _I32, _P, _P, _P]),
 }
 
 _lib = None
