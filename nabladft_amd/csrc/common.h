@@ -189,8 +189,8 @@ int nq_graph_count_impl(const float* pos, const int* mol_ptr, int N, int B, int 
 int nq_graph_fill_impl(GraphFillArgs args, int B, int max_mol_atoms, hipStream_t st);
 
 int nq_gemm_nn_epi(hipStream_t st, const float* G, const float* W, float* C, int M, int Nout, int Kin, const float* aux, float ea, float eb, int mode,
-                   const char* tag = nullptr);
-int nq_gemm_nn_dsilu2(hipStream_t st, const float* G, const float* W, float* C, float* C2, const float* aux, int M, int Nout, int Kin, const char* tag);
+                   const char* tag = nullptr, int ldg = 0);   // ldg: leading dimension of G (0: Nout)
+int nq_gemm_nn_dsilu2(hipStream_t st, const float* G, const float* W, float* C, float* C2, const float* aux, int M, int Nout, int Kin, const char* tag, int ldg = 0);
 int nq_gemm_nt_dsilu(hipStream_t st, const float* A, const float* W, float* C, float* C2, const float* aux, int M, int N, int K, const char* tag = nullptr);
 int nq_gemm_nt(hipStream_t, const float* A, const float* W, float* C, const float* bias, float* C2_silu, int M, int N, int K, int lda,
                int ldw, int ldc, const char* tag = nullptr);
@@ -250,7 +250,7 @@ int nq_upd_a(hipStream_t, const UpdArgs&, bool tan);
 int nq_upd_b(hipStream_t, const UpdArgs&, bool tan);
 int nq_silu_tan(hipStream_t, const float* Z, const float* TZ, float* TH, long count);
 int nq_silu_rev(hipStream_t, const float* Z, const float* TZ, float* G, float* GT, long count, bool dual, bool lite = false);   // lite: GT = the tangent adjoint of the layer OUTPUT, read only
-int nq_upd_rev(hipStream_t, const UpdRevArgs&, int stage, bool dual);
+int nq_upd_rev(hipStream_t, const UpdRevArgs&, int stage, bool dual, bool top = false);   // top: GV = GTV = 0 (the last layer of an energy-seeded sweep), neither is read
 int nq_embed(hipStream_t, const int* z, const float* emb, int N, int F, float* X0);
 size_t nq_embed_grad_scratch_floats(int N, int F, int T);
 int nq_embed_grad(hipStream_t, const int* z, const float* GX, int N, int F, int T, float* out, float* scratch);

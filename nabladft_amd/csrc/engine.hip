@@ -189,6 +189,11 @@ struct StepPlan {
   // nq_painn_forward itself).  layer0: the five default kernels of the message path run their layer-0 flavours there (edge.hip, molpair.hip), and the node-side
   // products whose operands are those zeros or whose results nobody reads are left out.  NQ_NO_LAYER0=1: every layer runs the general code (A/B runs, tests).
   bool layer0;
+  // The energy is read from x alone, so in both reverse sweeps the adjoint of vec_upd entering layer L-1 (and its tangent-adjoint twin) is a zero array.
+  // top_layer: the update-block reverse kernels of that layer run their TOP flavours (node.hip), its U input-gradient product stores instead of adding to the
+  // zeros, and its V2 input-gradient product contracts the first 2F columns of G_Y only (the last F are zeros).  Not for the seeded (direct-force) sweep, whose
+  // head seeds a vector adjoint.  NQ_NO_TOPLAYER=1: the general code (A/B runs, tests).
+  bool top_layer;
 };
 static StepPlan plan_step(const nq_painn_cfg* c, const nq_graph* g, bool want_forces) {
   auto env_on = [](const char* name) { const char* v = getenv(name); return v && v[0] == '1'; };
@@ -207,6 +212,7 @@ static StepPlan plan_step(const nq_painn_cfg* c, const nq_graph* g, bool want_fo
   // for the exact-f32 engine gets the five launches too
   p.fused_update = nq_updfuse_frag_floats(c->hidden_channels) > 0 && !env_on("NQ_NO_FUSED_UPDATE") && !nq_gemm_exact_f32_requested();
   p.layer0 = !env_on("NQ_NO_LAYER0");
+  p.top_layer = !env_on("NQ_NO_TOPLAYER");
   return p;
 }
 // the layout of a workspace sized or inspected outside a step (nq_painn_workspace_bytes, nq_painn_ws_lookup): the plan such a step would make now
@@ -504,11 +510,13 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
   float* gx_cur = lite_store ? ws + W.lay[L - 1].LGXA : ws + W.GX;     // adjoint of x_upd of the layer being processed
   NQ_TRY(nq_gemm_nn(st, ws + W.GZO, params + P.O1, gx_cur, N, H, F, H, F, F, 0, "O1"));
   float* gv_cur = lite_store ? ws + W.lay[L - 1].LGVA : ws + W.GVa; float* gv_oth = ws + W.GVb;
-  NQ_HIP(hipMemsetAsync(gv_cur, 0, 3 * NF * sizeof(float), st));
+  if (lite_store || !plan.top_layer) NQ_HIP(hipMemsetAsync(gv_cur, 0, 3 * NF * sizeof(float), st));   // (top_layer: read by nobody in this sweep; the stored-adjoint layout keeps its zeros)
   const int nwaves = F / 64;
   NQ_HIP(hipMemsetAsync(ws + W.GEDGE, 0, (size_t)nwaves * E * 4 * sizeof(float), st));
   for (int l = L - 1; l >= 0; --l) {
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
+    const bool top = plan.top_layer && l == L - 1;   // gv_cur = 0: its rows are not read, the last F columns of GY are zeros
+    const int KY = top ? 2 * F : 3 * F;
     float* const GY = lite_store ? ws + y.LGY + 3 * NF : ws + W.GY;
     float* const GCAT = lite_store ? ws + y.LGCAT + 2 * NF : ws + W.GCAT;
     float* const GU = lite_store ? ws + y.LGU + 6 * NF : ws + W.GU;
@@ -521,15 +529,15 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
     u.N = N; u.F = F; u.U = ws + y.UU; u.Y = ws + y.Y; u.S = ws + y.S; u.CAT = ws + y.CAT;
     u.GX = gx_cur; u.GV = gv_cur; u.GY = GY; u.GCAT = GCAT; u.GU = GU;
     u.GX_out = lite_store ? gx_msg : nullptr;
-    NQ_TRY(nq_upd_rev(st, u, 1, false));
+    NQ_TRY(nq_upd_rev(st, u, 1, false, top));
     // G_Q = (G_Y V2) * silu'(Z_Q): the activation's adjoint in the epilogue of the input-gradient product (no separate k_silu_rev pass)
     float* const GQ = lite_store ? ws + y.LGQ + NF : ws + W.GQ;
-    if (lite_store) NQ_TRY(nq_gemm_nn_dsilu2(st, GY, params + up.V2, ws + y.LGQP, GQ, ws + y.ZQ, N, 3 * F, F, "V2"));   // keeps G_Y V2 as well (silu'' term of the second-order sweep)
-    else NQ_TRY(nq_gemm_nn_epi(st, GY, params + up.V2, GQ, N, 3 * F, F, ws + y.ZQ, 0.f, 1.f, 1, "V2"));
+    if (lite_store) NQ_TRY(nq_gemm_nn_dsilu2(st, GY, params + up.V2, ws + y.LGQP, GQ, ws + y.ZQ, N, KY, F, "V2", 3 * F));   // keeps G_Y V2 as well (silu'' term of the second-order sweep)
+    else NQ_TRY(nq_gemm_nn_epi(st, GY, params + up.V2, GQ, N, KY, F, ws + y.ZQ, 0.f, 1.f, 1, "V2", 3 * F));
     NQ_TRY(nq_gemm_nn(st, GQ, params + up.V1, GCAT, N, F, 2 * F, F, 2 * F, 2 * F, 0, "V1"));
-    NQ_TRY(nq_upd_rev(st, u, 2, false));
-    if (lite_store) NQ_TRY(nq_gemm_nn_epi(st, GU, params + up.U, gv_msg, 3 * N, 2 * F, F, gv_cur, 1.f, 0.f, 0, "U"));   // gv_msg = gv_upd + gu U
-    else NQ_TRY(nq_gemm_nn(st, GU, params + up.U, gv_cur, 3 * N, 2 * F, F, 2 * F, F, F, 1, "U"));
+    NQ_TRY(nq_upd_rev(st, u, 2, false, top));
+    if (lite_store && !top) NQ_TRY(nq_gemm_nn_epi(st, GU, params + up.U, gv_msg, 3 * N, 2 * F, F, gv_cur, 1.f, 0.f, 0, "U"));   // gv_msg = gv_upd + gu U
+    else NQ_TRY(nq_gemm_nn(st, GU, params + up.U, gv_msg, 3 * N, 2 * F, F, 2 * F, F, F, top ? 0 : 1, "U"));   // (top: gv_upd = 0, a plain store)
     MsgRevArgs m{};
     m.g = g; m.F = F; m.V = ws + W.V[l]; m.XH = ws + y.XH; m.PHI = ws + y.PHI; m.PSI = ws + y.PSI;
     m.GX = gx_msg; m.GV = gv_msg; m.GXH = GXH; m.GV_out = gv_next; m.GEDGE = reinterpret_cast<float4*>(ws + W.GEDGE);
@@ -604,9 +612,10 @@ static void side_stream_init(SideStream& s, hipStream_t main, int n_atoms) {
   // a chain of ~330 small dependent kernels) 4.40 vs 4.71 ms, at 256 conformers 11.57 vs 11.78 ms: the weight gradients leave the critical path.  Re-measured on
   // the round-6 kernels (profiles/r06_helper_kernels_ab.txt, item 6): now a small gain at every size (2048 conformers 45.45 -> 45.1-45.2 ms, 512: 13.74 -> 13.14),
   // but two streams sharing the chip make every per-kernel duration (HIP events and rocprofv3 alike) depend on what ran beside it, and the record's roofline
-  // is a per-kernel figure: the default stays "on up to 16 k atoms"; NQ_SIDE_STREAM=0 / 1 forces it.
+  // is a per-kernel figure: above 16 k atoms the side stream is on unless the launch profiler is recording (the instrumented HIP-event pass stays single-stream;
+  // a rocprofv3 pass is taken with NQ_SIDE_STREAM=0); NQ_SIDE_STREAM=0 / 1 forces it.  Re-measured on this tree: profiles/reverse_passes_ab.txt.
   const char* env = getenv("NQ_SIDE_STREAM");
-  const bool want = env && (env[0] == '0' || env[0] == '1') ? env[0] == '1' : n_atoms <= 16384;
+  const bool want = env && (env[0] == '0' || env[0] == '1') ? env[0] == '1' : (n_atoms <= 16384 || !nq_profile_on);
   if (!want) return;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return;
@@ -725,7 +734,8 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
   NQ_TRY(nq_gemm_tn(sd, ws + W.GZO, ws + W.X[L], gp + P.O1, 2L * N, H, F, H, F, scr, "O1", gp + P.o1, N));
   NQ_TRY(nq_gemm_nn(st, ws + W.GZO, params + P.O1, ws + W.GX, lite ? N : 2 * N, H, F, H, F, F, 0, "O1"));
   float* gv_cur = ws + W.GVa; float* gv_oth = ws + W.GVb;
-  NQ_HIP(hipMemsetAsync(gv_cur, 0, (lite ? 3 : 6) * NF * sizeof(float), st));
+  const bool top_layer = plan.top_layer && !seeded;   // the force head seeds a vector adjoint
+  if (!top_layer) NQ_HIP(hipMemsetAsync(gv_cur, 0, (lite ? 3 : 6) * NF * sizeof(float), st));   // (top_layer: first touched by the U product of layer L-1, which stores)
   if (seeded) {   // adjoints of the final (x, vec) coming from the force head
     if (seed_x) NQ_TRY(nq_axpy(st, seed_x, ws + W.GX, (long)NF));
     if (seed_vec) NQ_HIP(hipMemcpyAsync(gv_cur, seed_vec, 3 * NF * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -738,6 +748,7 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
   if (mixed) NQ_HIP(hipMemsetAsync(ws + W.GBR, 0, 3 * NF * sizeof(float), st));   // only the rows of the large molecules are written below; the column sum runs over all atoms
   for (int l = L - 1; l >= 0; --l) {
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
+    const bool top = top_layer && l == L - 1;   // gv_cur = 0 and GTV = 0
     const bool l0 = plan.layer0 && l == 0;   // layer 0: no GV_out / GTV_out reader; t_h0 = 0 and t_x_in0 = 0 are the tangent halves of the W2 / W1 gradient operands
     float* const GYs = lite ? ws + y.LGY : ws + W.GY;         // stacked [2][N][3F]: the second half is the force sweep's (lite) or written below
     float* const GCATs = lite ? ws + y.LGCAT : ws + W.GCAT;
@@ -753,23 +764,23 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
     u.GU = GUs; u.GTU = GUs + 6 * NF;
     u.lite = lite ? 1 : 0;
     ss.before_main_writes(SB_GY);
-    NQ_TRY(nq_upd_rev(st, u, 1, true));
+    NQ_TRY(nq_upd_rev(st, u, 1, true, top));
     sd = ss.fork();
     NQ_TRY(nq_gemm_tn(sd, GYs, ws + y.Q, gp + up.V2, 2L * N, 3 * F, F, 3 * F, F, scr, "V2", gp + up.c2, N));
     ss.read_by_side(SB_GY);
     ss.before_main_writes(SB_GQ);
-    NQ_TRY(nq_gemm_nn(st, GYs, params + up.V2, GQs, lite ? N : 2 * N, 3 * F, F, 3 * F, F, F, 0, "V2"));
+    NQ_TRY(nq_gemm_nn(st, GYs, params + up.V2, GQs, lite ? N : 2 * N, top ? 2 * F : 3 * F, F, 3 * F, F, F, 0, "V2"));   // (top: the last F columns of GY are zeros)
     NQ_TRY(nq_silu_rev(st, ws + y.ZQ, ws + y.ZQ + NF, GQs, lite ? ws + y.LGQP : GQs + NF, (long)NF, true, lite));
     sd = ss.fork();
     NQ_TRY(nq_gemm_tn(sd, GQs, ws + y.CAT, gp + up.V1, 2L * N, F, 2 * F, F, 2 * F, scr, "V1", gp + up.c1, N));
     ss.read_by_side(SB_GQ);
     NQ_TRY(nq_gemm_nn(st, GQs, params + up.V1, GCATs, lite ? N : 2 * N, F, 2 * F, F, 2 * F, 2 * F, 0, "V1"));
     ss.before_main_writes(SB_GU);
-    NQ_TRY(nq_upd_rev(st, u, 2, true));
+    NQ_TRY(nq_upd_rev(st, u, 2, true, top));
     sd = ss.fork();
     NQ_TRY(nq_gemm_tn(sd, GUs, ws + y.VM, gp + up.U, 6L * N, 2 * F, F, 2 * F, F, scr, "U"));
     ss.read_by_side(SB_GU);
-    NQ_TRY(nq_gemm_nn(st, GUs, params + up.U, gv_cur, lite ? 3 * N : 6 * N, 2 * F, F, 2 * F, F, F, 1, "U"));
+    NQ_TRY(nq_gemm_nn(st, GUs, params + up.U, gv_cur, lite ? 3 * N : 6 * N, 2 * F, F, 2 * F, F, F, top ? 0 : 1, "U"));
     MsgRevArgs m{};
     m.g = g; m.F = F; m.V = ws + W.V[l]; m.XH = ws + y.XH; m.PHI = ws + y.PHI; m.PSI = ws + y.PSI;
     m.TV = ws + W.V[l] + 3 * NF; m.TXH = ws + y.XH + 3 * NF; m.TD = ws + W.TD; m.TR = ws + W.TR;

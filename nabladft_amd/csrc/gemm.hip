@@ -699,18 +699,18 @@ int nq_gemm_nn(hipStream_t st, const float* G, const float* W, float* C, int M, 
 }
 
 // C[M, Kin] = epilogue(G[M, Nout] * W[Nout, Kin]): mode 1: eb * v * silu'(aux), mode 2: ea * aux + v   (aux [M, Kin])
-int nq_gemm_nn_epi(hipStream_t st, const float* G, const float* W, float* C, int M, int Nout, int Kin, const float* aux, float ea, float eb, int mode, const char* tag) {
+int nq_gemm_nn_epi(hipStream_t st, const float* G, const float* W, float* C, int M, int Nout, int Kin, const float* aux, float ea, float eb, int mode, const char* tag, int ldg) {
   GEMM_PROLOGUE(st, "nn", tag, M, Kin, Nout);
-  GemmArgs p = gemm_args(G, W, C, M, Kin, Nout, Nout, Kin, Kin);
+  GemmArgs p = gemm_args(G, W, C, M, Kin, Nout, ldg > 0 ? ldg : Nout, Kin, Kin);
   gemm_aux(p, aux, ea, eb);
   return mode == 1 ? launch_product<true, false, EPI_DSILU, 16>(st, p, Nout) : launch_product<true, false, EPI_RES, 16>(st, p, Nout);
 }
 
 // C = G W (the adjoint of a SiLU layer's OUTPUT) and C2 = C * silu'(aux) (the adjoint of its pre-activation) in one pass: the force sweep keeps both, because the
 // second-order sweep needs the first for its silu'' term and the second as an operand of the weight gradient (engine.hip: per-layer adjoint store)
-int nq_gemm_nn_dsilu2(hipStream_t st, const float* G, const float* W, float* C, float* C2, const float* aux, int M, int Nout, int Kin, const char* tag) {
+int nq_gemm_nn_dsilu2(hipStream_t st, const float* G, const float* W, float* C, float* C2, const float* aux, int M, int Nout, int Kin, const char* tag, int ldg) {
   GEMM_PROLOGUE(st, "nn", tag, M, Kin, Nout);
-  GemmArgs p = gemm_args(G, W, C, M, Kin, Nout, Nout, Kin, Kin);
+  GemmArgs p = gemm_args(G, W, C, M, Kin, Nout, ldg > 0 ? ldg : Nout, Kin, Kin);
   p.C2 = C2; gemm_aux(p, aux, 0.f, 1.f);
   return launch_product<true, false, EPI_DSILU2, 16>(st, p, Nout);
 }

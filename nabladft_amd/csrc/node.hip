@@ -16,6 +16,9 @@ template <typename V> __device__ __forceinline__ V nq_ld(const float* p) { retur
 template <typename V> __device__ __forceinline__ void nq_st(float* p, V v) { *reinterpret_cast<V*>(p) = v; }
 __device__ __forceinline__ float nq_vsqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ nq_f4 nq_vsqrt(nq_f4 x) { return nq_f4{sqrtf(x[0]), sqrtf(x[1]), sqrtf(x[2]), sqrtf(x[3])}; }
+// a product that stays a rounded product: never contracted into the addition that consumes it
+__device__ __forceinline__ float nq_mul_rn(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ nq_f4 nq_mul_rn(nq_f4 a, nq_f4 b) { return nq_f4{__fmul_rn(a[0], b[0]), __fmul_rn(a[1], b[1]), __fmul_rn(a[2], b[2]), __fmul_rn(a[3], b[3])}; }
 #define NQ_NODE_INDEX                                                            \
   constexpr int VW = NqVW<V>::w;                                                 \
   const int F = q.F, FV = F / VW;                                                \
@@ -107,28 +110,39 @@ __global__ void k_silu_rev(const float* __restrict__ Z, const float* __restrict_
 // ---------------------------------------------------------------------------------------------
 
 // rev1: adjoints of y = (ya, yb, yc) from x_upd = x_msg + ya + yb s, vec_upd = vec_msg + yc v1
-template <bool DUAL, typename V>
+// TOP (both reverse kernels): the launch is the model's last layer in a sweep seeded through the energy alone, where the adjoint of vec_upd and its
+// tangent-adjoint twin are zero arrays (engine.hip, plan_step's top_layer).  The flavour neither reads them nor the rows they multiply; what is left is
+// written so that it rounds as the general expressions do with the zeros filled in (a product that the general statement rounds before it adds stays a
+// rounded product: __fmul_rn is never contracted).  Every output is still written; the results are value-equal (tests/test_reverse_passes_gpu.py).
+template <bool DUAL, typename V, bool TOP = false>
 __global__ void k_upd_rev1(UpdRevArgs q) {
   NQ_NODE_INDEX
-  const float* u = q.U + n * 6 * F;
   const V gx = nq_ld<V>(q.GX + nf), s = nq_ld<V>(q.S + nf);
-  const float* gv = q.GV + n * 3 * F;
-  const V gv0 = nq_ld<V>(gv + f), gv1 = nq_ld<V>(gv + F + f), gv2 = nq_ld<V>(gv + 2 * F + f);
-  const V u0 = nq_ld<V>(u + f), u1 = nq_ld<V>(u + 2 * F + f), u2 = nq_ld<V>(u + 4 * F + f);
   V gyb = gx * s;
-  V gyc = gv0 * u0 + gv1 * u1 + gv2 * u2;
+  V gyc = gx * 0.f;
+  if (!TOP) {
+    const float* u = q.U + n * 6 * F;
+    const float* gv = q.GV + n * 3 * F;
+    const V gv0 = nq_ld<V>(gv + f), gv1 = nq_ld<V>(gv + F + f), gv2 = nq_ld<V>(gv + 2 * F + f);
+    const V u0 = nq_ld<V>(u + f), u1 = nq_ld<V>(u + 2 * F + f), u2 = nq_ld<V>(u + 4 * F + f);
+    gyc = gv0 * u0 + gv1 * u1 + gv2 * u2;
+    if (DUAL) {
+      const float* tu = q.TU + n * 6 * F;
+      const float* gtv = q.GTV + n * 3 * F;
+      const V gtv0 = nq_ld<V>(gtv + f), gtv1 = nq_ld<V>(gtv + F + f), gtv2 = nq_ld<V>(gtv + 2 * F + f);
+      gyc += gtv0 * nq_ld<V>(tu + f) + gtv1 * nq_ld<V>(tu + 2 * F + f) + gtv2 * nq_ld<V>(tu + 4 * F + f);
+      if (!q.lite) nq_st<V>(q.GTY + n * 3 * F + 2 * F + f, gtv0 * u0 + gtv1 * u1 + gtv2 * u2);
+    }
+  } else if (DUAL && !q.lite) {
+    nq_st<V>(q.GTY + n * 3 * F + 2 * F + f, gyc);
+  }
   if (DUAL) {
-    const float* tu = q.TU + n * 6 * F;
     const V gtx = nq_ld<V>(q.GTX + nf);
-    const float* gtv = q.GTV + n * 3 * F;
-    const V gtv0 = nq_ld<V>(gtv + f), gtv1 = nq_ld<V>(gtv + F + f), gtv2 = nq_ld<V>(gtv + 2 * F + f);
     gyb += gtx * nq_ld<V>(q.TS + nf);
-    gyc += gtv0 * nq_ld<V>(tu + f) + gtv1 * nq_ld<V>(tu + 2 * F + f) + gtv2 * nq_ld<V>(tu + 4 * F + f);
     if (!q.lite) {
       float* gty = q.GTY + n * 3 * F;
       nq_st<V>(gty + f, gtx);
       nq_st<V>(gty + F + f, gtx * s);
-      nq_st<V>(gty + 2 * F + f, gtv0 * u0 + gtv1 * u1 + gtv2 * u2);
     }
   }
   float* gy = q.GY + n * 3 * F;
@@ -136,18 +150,19 @@ __global__ void k_upd_rev1(UpdRevArgs q) {
 }
 
 // rev2: given gcat = adjoint of [x_msg | n]: adjoints of u = (v1, v2) and gx_msg = gx_upd + gcat[:F]
-template <bool DUAL, typename V>
+template <bool DUAL, typename V, bool TOP = false>
 __global__ void k_upd_rev2(UpdRevArgs q) {
   NQ_NODE_INDEX
   const float* u = q.U + n * 6 * F;
   const float* y = q.Y + n * 3 * F;
-  const V yb = nq_ld<V>(y + F + f), yc = nq_ld<V>(y + 2 * F + f);
+  const V yb = nq_ld<V>(y + F + f);
   const V nn = nq_ld<V>(q.CAT + n * 2 * F + F + f);
   const V gx = nq_ld<V>(q.GX + nf);
   const float* gv = q.GV + n * 3 * F;
   const V gn = nq_ld<V>(q.GCAT + n * 2 * F + F + f);
   V gs = gx * yb;
-  V gts = gx * 0.f, gtn = gts, tn = gts, tyc = gts, gtx = gts;
+  V gts = gx * 0.f, gtn = gts, tn = gts, tyc = gts, gtx = gts, yc = gts;
+  if (!TOP) yc = nq_ld<V>(y + 2 * F + f);
   const float* tu = nullptr; const float* gtv = nullptr;
   if (DUAL) {
     tu = q.TU + n * 6 * F;
@@ -156,7 +171,7 @@ __global__ void k_upd_rev2(UpdRevArgs q) {
     const float* ty = q.TY + n * 3 * F;
     gs += gtx * nq_ld<V>(ty + F + f);
     gts = gtx * yb;
-    tyc = nq_ld<V>(ty + 2 * F + f);
+    if (!TOP) tyc = nq_ld<V>(ty + 2 * F + f);
     gtn = nq_ld<V>(q.GTCAT + n * 2 * F + F + f);
     tn = nq_ld<V>(q.TCAT + n * 2 * F + F + f);
   }
@@ -165,16 +180,21 @@ __global__ void k_upd_rev2(UpdRevArgs q) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const V a = nq_ld<V>(u + c * 2 * F + f), b = nq_ld<V>(u + c * 2 * F + F + f);
-    V g1 = nq_ld<V>(gv + c * F + f) * yc + gs * b;
+    V g1 = TOP ? gs * b : nq_ld<V>(gv + c * F + f) * yc + gs * b;   // TOP: gv = 0, the sum is the rounded product
     V g2 = gn_n * b + gs * a;
     if (DUAL) {
       const V ta = nq_ld<V>(tu + c * 2 * F + f), tb = nq_ld<V>(tu + c * 2 * F + F + f);
-      const V gtvc = nq_ld<V>(gtv + c * F + f);
-      g1 += gtvc * tyc + gts * tb;
+      if (TOP) {
+        g1 += nq_mul_rn(gts, tb);            // gtv = 0: (gtv tyc + gts tb) is the rounded product, added unfused as the general sum is
+      } else {
+        const V gtvc = nq_ld<V>(gtv + c * F + f);
+        g1 += gtvc * tyc + gts * tb;
+        if (!q.lite) nq_st<V>(q.GTU + n * 6 * F + c * 2 * F + f, gtvc * yc + gts * b);
+      }
       g2 += gtn_n * (tb - tn_n * b) + gts * ta;
       if (!q.lite) {
         float* gtu = q.GTU + n * 6 * F;
-        nq_st<V>(gtu + c * 2 * F + f, gtvc * yc + gts * b);
+        if (TOP) nq_st<V>(gtu + c * 2 * F + f, gts * b);
         nq_st<V>(gtu + c * 2 * F + F + f, gtn_n * b + gts * a);
       }
     }
@@ -390,15 +410,20 @@ int nq_silu_rev(hipStream_t st, const float* Z, const float* TZ, float* G, float
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }
-int nq_upd_rev(hipStream_t st, const UpdRevArgs& q, int stage, bool dual) {
-  NQ_PROF(st, "upd_rev");
+// top: the flavour for a zero adjoint of vec_upd (GV, GTV are not read); a profiler class of its own, so that the per-launch figure of upd_rev stays comparable
+int nq_upd_rev(hipStream_t st, const UpdRevArgs& q, int stage, bool dual, bool top) {
+  NQ_PROF(st, top ? "upd_rev_top" : "upd_rev");
   if (q.N <= 0) return NQ_OK;
   dim3 g = grid1d((long)q.N * q.F / NqVW<NQ_NODE_V>::w, 256), b(256);
   if (stage == 1) {
-    if (dual) hipLaunchKernelGGL((k_upd_rev1<true, NQ_NODE_V>), g, b, 0, st, q);
+    if (dual && top) hipLaunchKernelGGL((k_upd_rev1<true, NQ_NODE_V, true>), g, b, 0, st, q);
+    else if (top) hipLaunchKernelGGL((k_upd_rev1<false, NQ_NODE_V, true>), g, b, 0, st, q);
+    else if (dual) hipLaunchKernelGGL((k_upd_rev1<true, NQ_NODE_V>), g, b, 0, st, q);
     else hipLaunchKernelGGL((k_upd_rev1<false, NQ_NODE_V>), g, b, 0, st, q);
   } else {
-    if (dual) hipLaunchKernelGGL((k_upd_rev2<true, NQ_NODE_V>), g, b, 0, st, q);
+    if (dual && top) hipLaunchKernelGGL((k_upd_rev2<true, NQ_NODE_V, true>), g, b, 0, st, q);
+    else if (top) hipLaunchKernelGGL((k_upd_rev2<false, NQ_NODE_V, true>), g, b, 0, st, q);
+    else if (dual) hipLaunchKernelGGL((k_upd_rev2<true, NQ_NODE_V>), g, b, 0, st, q);
     else hipLaunchKernelGGL((k_upd_rev2<false, NQ_NODE_V>), g, b, 0, st, q);
   }
   NQ_LAUNCH_CHECK();
