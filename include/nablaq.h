@@ -757,6 +757,31 @@ int nq_dn_embed_forward(const float* AB, const float* Cr, const float* bias, con
 int nq_dn_embed_backward(const float* pre, const float* grad_y, const int32_t* row_ptr, const int32_t* src_order, const int32_t* src_ptr, int32_t N, int64_t E,
                          int32_t H, float* grad_pre, float* grad_AB, void* stream);
 
+/* ---- DimeNet++, second sweep (a loss on the forces: d loss / d parameters = -d/d parameters <v, dE/dpos>, v = d loss / d forces).  The adjoint that reaches the
+ * first-backward node of a kernel is the kernel's tangent along a position displacement; the reverse of that tangent goes on to the parameters.  No adjoint of d, u
+ * or the positions is formed.  A tangent argument that is NULL counts as zero (and gives the bits of a zero array).  Fixed summation order, no atomics.
+ * geometry: w = tpos[dst] - tpos[src], td [E] = w . u, tu [E][3] = (w - (w . u) u) / d.
+ * basis (float64 inside, rounded once): rbf_t [E][R] = t[e] drbf/dd, rad_t [E][S][R] = t[e] dRad/dd, freq_rows [E][R] = t[e] grad_rbf[e][n] d2rbf/(dd dfreq_n)
+ * (grad_rbf nullable; the column sum of freq_rows is the adjoint of freq).
+ * triplet forward: mt [E][I] = the tangent of nq_dn_triplet_forward along (tx [E][I], tQ [E][S][Bs], tu [E][3]), W_sbf2 fixed.  Triplet backward: the adjoints of
+ * <g, mt> with respect to x_kj (a_x), Q (a_Q) and, unless NULL, W_sbf2 (a_W_sbf2; scratch: nq_dn_triplet_scratch_floats floats).  One launch each.
+ * silu: a = the adjoint of g silu'(pre): a_g = a silu'(pre), a_pre = a g silu''(pre).
+ * gate: the adjoints (a_gx, a_gg, either nullable) of nq_dn_gate_backward's outputs: a_g = a_gx gate + a_gg x, a_x = a_gg g, a_gate = a_gx g.
+ * embed_scatter: out [N][2H] = {sum of rows [E][H] over the in-edges, sum over the out-edges} of every atom (the adjoint of the embedding block's gather). */
+int nq_dnt_geom(const float* d, const float* u, const float* tpos, const int32_t* src, const int32_t* dst, int64_t E, float* td, float* tu, void* stream);
+int nq_dnt_basis(const float* d, const float* freq, const double* roots, const double* norms, int64_t E, int32_t S, int32_t R, double cutoff, int32_t envelope_p,
+                 const float* t, const float* grad_rbf, float* rbf_t, float* rad_t, float* freq_rows, void* stream);
+int nq_dnt_triplet_forward(const float* x_kj, const float* Q, const float* u, const float* W_sbf2, const float* tx, const float* tQ, const float* tu,
+                           const int32_t* row_ptr, const int32_t* src, const int32_t* dst, int32_t E, int32_t I, int32_t S, int32_t Bs, float* mt, void* stream);
+int nq_dnt_triplet_backward(const float* x_kj, const float* Q, const float* u, const float* W_sbf2, const float* tx, const float* tQ, const float* tu,
+                            const int32_t* row_ptr, const int32_t* src, const int32_t* dst, const int32_t* src_order, const int32_t* src_ptr, int32_t E, int32_t I,
+                            int32_t S, int32_t Bs, const float* g, float* a_x, float* a_Q, float* a_W_sbf2, float* scratch, void* stream);
+int nq_dnt_silu(const float* pre, const float* g, const float* a, int64_t count, float* a_g, float* a_pre, void* stream);
+int nq_dnt_gate(const float* x, const float* gate, const float* g, const float* a_gx, const float* a_gg, int64_t count, float* a_g, float* a_x, float* a_gate,
+                void* stream);
+int nq_dnt_embed_scatter(const float* rows, const int32_t* row_ptr, const int32_t* src_order, const int32_t* src_ptr, int32_t N, int64_t E, int32_t H, float* out,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

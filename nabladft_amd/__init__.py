@@ -28,12 +28,12 @@ from .gemnet_oc import GemNetOC  # noqa: F401
 from .escn import eSCN  # noqa: F401
 from .equiformer_v2 import EquiformerV2_OC20  # noqa: F401
 from .graphormer import Graphormer3D, Graphormer3DLightning  # noqa: F401
-from .dimenetplusplus import DimeNetPlusPlusLightning, DimeNetPlusPlusPotential  # noqa: F401
+from .dimenetplusplus import DimeNetPlusPlusForceLightning, DimeNetPlusPlusLightning, DimeNetPlusPlusPotential  # noqa: F401
 from . import ema, schedulers  # noqa: F401
 from .trainer import FusedTrainStep, Batch  # noqa: F401
 from . import optimization  # noqa: F401
 from .optimization import ASEBatchwiseLBFGS, BatchwiseOptimizeTask, PyGBatchwiseCalculator  # noqa: F401
 from .data import ArenaLoader, ConformerArena, HamiltonianBatch, HamiltonianDatabase, HamiltonianDataset, hamiltonian_batch, read_energy_database  # noqa: F401
 
-__all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
+__all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "DimeNetPlusPlusForceLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
            "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask"]

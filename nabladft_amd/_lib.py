@@ -233,6 +233,13 @@ SYMBOLS = {
     "nq_dn_gatesum_backward": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "nq_dn_embed_forward": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P]),
     "nq_dn_embed_backward": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I64, _I32, _P, _P, _P]),
+    "nq_dnt_geom": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "nq_dnt_basis": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I32, _D, _I32, _P, _P, _P, _P, _P, _P]),
+    "nq_dnt_triplet_forward": (C.c_int, [_P] * 10 + [_I32, _I32, _I32, _I32, _P, _P]),
+    "nq_dnt_triplet_backward": (C.c_int, [_P] * 12 + [_I32, _I32, _I32, _I32] + [_P] * 6),
+    "nq_dnt_silu": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P]),
+    "nq_dnt_gate": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "nq_dnt_embed_scatter": (C.c_int, [_P, _P, _P, _P, _I32, _I64, _I32, _P, _P]),
 }
 
 _lib = None

@@ -369,6 +369,200 @@ __global__ __launch_bounds__(256) void k_dn_embed_gab(const float* __restrict__ 
   gAB[t] = a;
 }
 
+// ---- second sweep (a loss on the forces): tangents along a position displacement and their reverses ------------------------------------------------------------
+// The adjoint that reaches the first-backward node of a kernel is the kernel's tangent (JVP) along the displacement v = dL/dF; what flows on to the parameters is the
+// reverse of that tangent with respect to the parameter-dependent inputs.  d, u, rbf and Rad depend on the positions only: no adjoint of u or d is formed here.
+struct DnTan { const float* tx; const float* tQ; const float* tu; };       // each nullable = a zero tangent (the arithmetic is the same, so the bits are too)
+
+// w = tpos[dst] - tpos[src]: td = w . u, tu = (w - (w . u) u) / d
+__global__ __launch_bounds__(256) void k_dn_geom_tan(const float* __restrict__ d, const float* __restrict__ u, const float* __restrict__ tpos,
+                                                     const int* __restrict__ src, const int* __restrict__ dst, long E, float* __restrict__ td,
+                                                     float* __restrict__ tu) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  const long a = 3L * dst[e], b = 3L * src[e];
+  const float wx = tpos[a] - tpos[b], wy = tpos[a + 1] - tpos[b + 1], wz = tpos[a + 2] - tpos[b + 2];
+  const float ux = u[3 * e], uy = u[3 * e + 1], uz = u[3 * e + 2], dot = wx * ux + wy * uy + wz * uz, inv = 1.0f / d[e];
+  td[e] = dot;
+  tu[3 * e] = (wx - dot * ux) * inv; tu[3 * e + 1] = (wy - dot * uy) * inv; tu[3 * e + 2] = (wz - dot * uz) * inv;
+}
+
+// thread (e, l): l < S the row t[e] dRad[e][l][:]/dd, l == S the rows t[e] drbf[e][:]/dd and t[e] g_rbf[e][n] d2rbf/(dd dfreq_n)
+__global__ __launch_bounds__(256) void k_dn_basis_tan(const float* __restrict__ d, const float* __restrict__ freq, const double* __restrict__ roots,
+                                                      const double* __restrict__ norms, long E, int S, int R, double inv_cutoff, int p,
+                                                      const float* __restrict__ t, const float* __restrict__ g_rbf, float* __restrict__ rbf_t,
+                                                      float* __restrict__ rad_t, float* __restrict__ freq_rows) {
+  const long th = (long)blockIdx.x * 256 + threadIdx.x;
+  if (th >= E * (S + 1)) return;
+  const long e = th / (S + 1);
+  const int l = (int)(th - e * (S + 1));
+  const double x = (double)d[e] * inv_cutoff, te = (double)t[e] * inv_cutoff;
+  double env, denv;
+  dn_env(x, p, env, denv);
+  if (l == S) {
+    for (int n = 0; n < R; ++n) {
+      const double f = (double)freq[n], sn = sin(f * x), cs = cos(f * x), g = g_rbf ? (double)g_rbf[e * R + n] : 0.0;
+      rbf_t[e * R + n] = (float)(te * (denv * sn + env * f * cs));
+      freq_rows[e * R + n] = (float)(te * g * (denv * x * cs + env * cs - env * f * x * sn));
+    }
+  } else {
+    for (int n = 0; n < R; ++n) {
+      const double z = roots[l * R + n], j = dn_jl(l, z * x);
+      rad_t[(e * S + l) * R + n] = (float)(te * norms[l * R + n] * (denv * j + env * z * dn_djl(l, z * x, j)));
+    }
+  }
+}
+
+// the walk of k_dn_trip_fwd: mt[e][c] = sum_{e2} sum_b W2[c][b] (tx[e2][c] s_b + x[e2][c] st_b), st_b = sum_l (Y_l tQ[e2][l][b] + Y_l' cdot Q[e2][l][b])
+template <int NQ>
+__global__ __launch_bounds__(256) void k_dn_trip_tan_fwd(DnTrip p, DnTan t, float* __restrict__ mt) {
+  constexpr int I = 64 * NQ;
+  const int lane = threadIdx.x & 63;
+  const int e = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (e >= p.E) return;
+  const int j = p.src[e], i = p.dst[e];
+  const float ux = p.u[3 * (long)e], uy = p.u[3 * (long)e + 1], uz = p.u[3 * (long)e + 2];
+  const float tux = t.tu ? t.tu[3 * (long)e] : 0.f, tuy = t.tu ? t.tu[3 * (long)e + 1] : 0.f, tuz = t.tu ? t.tu[3 * (long)e + 2] : 0.f;
+  float w[NQ][DN_MAXB], acc[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    acc[q] = 0.f;
+#pragma unroll
+    for (int b = 0; b < DN_MAXB; ++b) w[q][b] = b < p.Bs ? p.W2[(long)(lane + 64 * q) * p.Bs + b] : 0.f;
+  }
+  const int r0 = p.row_ptr[j], r1 = p.row_ptr[j + 1];
+  for (int e2 = r0; e2 < r1; ++e2) {
+    if (p.src[e2] == i) continue;
+    const float vx = p.u[3 * (long)e2], vy = p.u[3 * (long)e2 + 1], vz = p.u[3 * (long)e2 + 2];
+    const float tvx = t.tu ? t.tu[3 * (long)e2] : 0.f, tvy = t.tu ? t.tu[3 * (long)e2 + 1] : 0.f, tvz = t.tu ? t.tu[3 * (long)e2 + 2] : 0.f;
+    const float c = ux * vx + uy * vy + uz * vz;
+    const float cd = (tux * vx + tuy * vy + tuz * vz) + (ux * tvx + uy * tvy + uz * tvz);
+    float Y[DN_MAXS], dY[DN_MAXS];
+    dn_legendre(c, p.S, Y, dY);
+    float s = 0.f, sd = 0.f;
+    if (lane < p.Bs) {
+      const long off = (long)e2 * p.S * p.Bs + lane;
+#pragma unroll
+      for (int l = 0; l < DN_MAXS; ++l)
+        if (l < p.S) {
+          const float q = p.Q[off + l * p.Bs], tq = t.tQ ? t.tQ[off + l * p.Bs] : 0.f;
+          s = fmaf(Y[l], q, s);
+          sd = fmaf(Y[l], tq, fmaf(dY[l] * cd, q, sd));
+        }
+    }
+    float ts[NQ], tt[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) ts[q] = tt[q] = 0.f;
+#pragma unroll
+    for (int b = 0; b < DN_MAXB; ++b) {
+      const float sb = dn_lane_bcast(s, b), sdb = dn_lane_bcast(sd, b);
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) { ts[q] = fmaf(sb, w[q][b], ts[q]); tt[q] = fmaf(sdb, w[q][b], tt[q]); }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const long at = (long)e2 * I + lane + 64 * q;
+      acc[q] = fmaf(p.x[at], tt[q], fmaf(t.tx ? t.tx[at] : 0.f, ts[q], acc[q]));
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) mt[(long)e * I + lane + 64 * q] = acc[q];
+}
+
+// the transposed walk of k_dn_trip_bwd_in, owner e2 = (k->j): the adjoints of <g, mt> with respect to x, Q and (as partial sums per chunk) W2.  Nothing is
+// written for u or the tangents, so there is no owner-side pass.  lane = l Bs + b holds a_Q[e2][l][b].
+template <int NQ>
+__global__ __launch_bounds__(256) void k_dn_trip_tan_bwd(DnTrip p, DnTan t, const float* __restrict__ gm, float* __restrict__ ax, float* __restrict__ aQ,
+                                                         float* __restrict__ aW2_part) {
+  constexpr int I = 64 * NQ;
+  const int lane = threadIdx.x & 63;
+  const int chunk = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  const int e_lo = chunk * DN_CHUNK;
+  if (e_lo >= p.E) return;
+  const int e_hi = min(p.E, e_lo + DN_CHUNK);
+  const int SB = p.S * p.Bs, myl = lane / p.Bs, myb = lane - myl * p.Bs;
+  float w[NQ][DN_MAXB], gw[NQ][DN_MAXB];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+#pragma unroll
+    for (int b = 0; b < DN_MAXB; ++b) { w[q][b] = b < p.Bs ? p.W2[(long)(lane + 64 * q) * p.Bs + b] : 0.f; gw[q][b] = 0.f; }
+  for (int e2 = e_lo; e2 < e_hi; ++e2) {
+    const int k = p.src[e2], j = p.dst[e2];
+    const float vx = p.u[3 * (long)e2], vy = p.u[3 * (long)e2 + 1], vz = p.u[3 * (long)e2 + 2];
+    const float tvx = t.tu ? t.tu[3 * (long)e2] : 0.f, tvy = t.tu ? t.tu[3 * (long)e2 + 1] : 0.f, tvz = t.tu ? t.tu[3 * (long)e2 + 2] : 0.f;
+    float xq[NQ], txq[NQ], acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const long at = (long)e2 * I + lane + 64 * q;
+      xq[q] = p.x[at]; txq[q] = t.tx ? t.tx[at] : 0.f; acc[q] = 0.f;
+    }
+    float Qcol[DN_MAXS], tQcol[DN_MAXS];                   // lane b < Bs: Q[e2][l][b], tQ[e2][l][b]
+#pragma unroll
+    for (int l = 0; l < DN_MAXS; ++l) {
+      const bool on = lane < p.Bs && l < p.S;
+      Qcol[l] = on ? p.Q[(long)e2 * SB + l * p.Bs + lane] : 0.f;
+      tQcol[l] = (on && t.tQ) ? t.tQ[(long)e2 * SB + l * p.Bs + lane] : 0.f;
+    }
+    float gq = 0.f;
+    for (int s_ = p.src_ptr[j]; s_ < p.src_ptr[j + 1]; ++s_) {
+      const int e = p.src_order[s_];
+      if (p.dst[e] == k) continue;
+      const float ux = p.u[3 * (long)e], uy = p.u[3 * (long)e + 1], uz = p.u[3 * (long)e + 2];
+      const float tux = t.tu ? t.tu[3 * (long)e] : 0.f, tuy = t.tu ? t.tu[3 * (long)e + 1] : 0.f, tuz = t.tu ? t.tu[3 * (long)e + 2] : 0.f;
+      const float c = ux * vx + uy * vy + uz * vz;
+      const float cd = (tux * vx + tuy * vy + tuz * vz) + (ux * tvx + uy * tvy + uz * tvz);
+      float Y[DN_MAXS], dY[DN_MAXS], g1[NQ], g2[NQ], G1[DN_MAXB], G2[DN_MAXB], g[NQ], tt[NQ];
+      dn_legendre(c, p.S, Y, dY);
+      float s = 0.f, sd = 0.f;
+#pragma unroll
+      for (int l = 0; l < DN_MAXS; ++l) { s = fmaf(Y[l], Qcol[l], s); sd = fmaf(Y[l], tQcol[l], fmaf(dY[l] * cd, Qcol[l], sd)); }
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) { g[q] = gm[(long)e * I + lane + 64 * q]; g1[q] = g[q] * txq[q]; g2[q] = g[q] * xq[q]; tt[q] = 0.f; }
+#pragma unroll
+      for (int b = 0; b < DN_MAXB; ++b) {
+        const float sb = dn_lane_bcast(s, b), sdb = dn_lane_bcast(sd, b);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) { tt[q] = fmaf(sdb, w[q][b], tt[q]); gw[q][b] = fmaf(g2[q], sdb, fmaf(g1[q], sb, gw[q][b])); }
+      }
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) acc[q] = fmaf(g[q], tt[q], acc[q]);
+      dn_gs<NQ>(g1, w, G1);
+      dn_gs<NQ>(g2, w, G2);
+      gq = fmaf(dn_pick(dY, myl) * cd, dn_pick(G2, myb), fmaf(dn_pick(Y, myl), dn_pick(G1, myb), gq));
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) ax[(long)e2 * I + lane + 64 * q] = acc[q];
+    if (lane < SB) aQ[(long)e2 * SB + lane] = gq;
+  }
+  if (aW2_part) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+      for (int b = 0; b < DN_MAXB; ++b)
+        if (b < p.Bs) aW2_part[((long)chunk * I + lane + 64 * q) * p.Bs + b] = gw[q][b];
+  }
+}
+
+// a = the adjoint of gp = g silu'(pre): a_g = a silu'(pre), a_pre = a g silu''(pre)
+__global__ __launch_bounds__(256) void k_dn_silu_rev2(const float* __restrict__ pre, const float* __restrict__ g, const float* __restrict__ a, long count,
+                                                      float* __restrict__ a_g, float* __restrict__ a_pre) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= count) return;
+  const float z = pre[t], v = a[t];
+  a_g[t] = v * nq_dsilu(z);
+  a_pre[t] = v * g[t] * nq_d2silu(z);
+}
+// gx = g gate, gg = g x with the adjoints a_gx, a_gg (either nullable = zero): a_g = a_gx gate + a_gg x, a_x = a_gg g, a_gate = a_gx g
+__global__ __launch_bounds__(256) void k_dn_gate_rev2(const float* __restrict__ x, const float* __restrict__ gate, const float* __restrict__ g,
+                                                      const float* __restrict__ a_gx, const float* __restrict__ a_gg, long count, float* __restrict__ a_g,
+                                                      float* __restrict__ a_x, float* __restrict__ a_gate) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= count) return;
+  const float p = a_gx ? a_gx[t] : 0.f, q = a_gg ? a_gg[t] : 0.f, v = g[t];
+  a_g[t] = fmaf(p, gate[t], q * x[t]);
+  a_x[t] = q * v; a_gate[t] = p * v;
+}
+
 int dn_trip_check(const DnTrip& p, int I) {
   if (!p.x || !p.Q || !p.u || !p.W2 || !p.row_ptr || !p.src || !p.dst) return nq_fail(NQ_ERR_ARG, "dimenet triplet: null argument");
   if (I < 64 || I > 256 || I % 64 != 0) return nq_fail(NQ_ERR_ARG, "dimenet triplet: int_emb_size %d must be 64, 128, 192 or 256", I);
@@ -533,6 +727,90 @@ int nq_dn_embed_backward(const float* pre, const float* grad_y, const int32_t* r
   if (E > 0) hipLaunchKernelGGL(k_dn_embed_gpre, DN_GRID((long)E * H), pre, grad_y, (long)E * H, grad_pre);
   NQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_dn_embed_gab, DN_GRID((long)N * 2 * H), (const float*)grad_pre, row_ptr, src_order, src_ptr, N, H, grad_AB);
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+
+/* ---- second sweep ---- */
+int nq_dnt_geom(const float* d, const float* u, const float* tpos, const int32_t* src, const int32_t* dst, int64_t E, float* td, float* tu, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  NQ_PROF(st, "dn_geom_tan");
+  if (E == 0) return NQ_OK;
+  if (!d || !u || !tpos || !src || !dst || !td || !tu || E < 0) return nq_fail(NQ_ERR_ARG, "dimenet geometry tangent: bad argument");
+  hipLaunchKernelGGL(k_dn_geom_tan, DN_GRID(E), d, u, tpos, src, dst, (long)E, td, tu);
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+int nq_dnt_basis(const float* d, const float* freq, const double* roots, const double* norms, int64_t E, int32_t S, int32_t R, double cutoff, int32_t envelope_p,
+                 const float* t, const float* grad_rbf, float* rbf_t, float* rad_t, float* freq_rows, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  NQ_PROF(st, "dn_basis_tan");
+  if (E == 0) return NQ_OK;
+  NQ_TRY(dn_basis_check(d, freq, roots, norms, E, S, R, cutoff, envelope_p));
+  if (!t || !rbf_t || !rad_t || !freq_rows) return nq_fail(NQ_ERR_ARG, "dimenet basis tangent: null argument");
+  hipLaunchKernelGGL(k_dn_basis_tan, DN_GRID((long)E * (S + 1)), d, freq, roots, norms, (long)E, S, R, 1.0 / cutoff, envelope_p, t, grad_rbf, rbf_t, rad_t,
+                     freq_rows);
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+int nq_dnt_triplet_forward(const float* x_kj, const float* Q, const float* u, const float* W_sbf2, const float* tx, const float* tQ, const float* tu,
+                           const int32_t* row_ptr, const int32_t* src, const int32_t* dst, int32_t E, int32_t I, int32_t S, int32_t Bs, float* mt, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  NQ_PROF(st, "dn_triplet_tan_fwd");
+  if (E == 0) return NQ_OK;
+  DnTrip p{x_kj, Q, u, W_sbf2, row_ptr, src, dst, nullptr, nullptr, E, S, Bs};
+  NQ_TRY(dn_trip_check(p, I));
+  if (!mt || E < 0) return nq_fail(NQ_ERR_ARG, "dimenet triplet tangent: bad argument");
+  DnTan t{tx, tQ, tu};
+  DN_DISPATCH(I, k_dn_trip_tan_fwd, nq_cdiv(E, 4), p, t, mt);
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+int nq_dnt_triplet_backward(const float* x_kj, const float* Q, const float* u, const float* W_sbf2, const float* tx, const float* tQ, const float* tu,
+                            const int32_t* row_ptr, const int32_t* src, const int32_t* dst, const int32_t* src_order, const int32_t* src_ptr, int32_t E, int32_t I,
+                            int32_t S, int32_t Bs, const float* g, float* a_x, float* a_Q, float* a_W_sbf2, float* scratch, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  NQ_PROF(st, "dn_triplet_tan_bwd");
+  if (E == 0) {
+    if (a_W_sbf2 && I > 0 && Bs > 0) NQ_HIP(hipMemsetAsync(a_W_sbf2, 0, sizeof(float) * I * Bs, st));
+    return NQ_OK;
+  }
+  DnTrip p{x_kj, Q, u, W_sbf2, row_ptr, src, dst, src_order, src_ptr, E, S, Bs};
+  NQ_TRY(dn_trip_check(p, I));
+  if (!src_order || !src_ptr || !g || !a_x || !a_Q || E < 0 || (a_W_sbf2 && !scratch)) return nq_fail(NQ_ERR_ARG, "dimenet triplet tangent: bad argument");
+  const int chunks = nq_cdiv(E, DN_CHUNK);
+  float* part = a_W_sbf2 ? scratch : nullptr;
+  DnTan t{tx, tQ, tu};
+  DN_DISPATCH(I, k_dn_trip_tan_bwd, nq_cdiv(chunks, 4), p, t, g, a_x, a_Q, part);
+  NQ_LAUNCH_CHECK();
+  if (a_W_sbf2) NQ_TRY(nq_colsum(st, part, (long)chunks, I * Bs, I * Bs, a_W_sbf2, scratch + (size_t)chunks * I * Bs));
+  return NQ_OK;
+}
+int nq_dnt_silu(const float* pre, const float* g, const float* a, int64_t count, float* a_g, float* a_pre, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  NQ_PROF(st, "dn_silu_rev2");
+  if (count == 0) return NQ_OK;
+  if (!pre || !g || !a || !a_g || !a_pre || count < 0) return nq_fail(NQ_ERR_ARG, "dimenet SiLU second order: bad argument");
+  hipLaunchKernelGGL(k_dn_silu_rev2, DN_GRID(count), pre, g, a, (long)count, a_g, a_pre);
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+int nq_dnt_gate(const float* x, const float* gate, const float* g, const float* a_gx, const float* a_gg, int64_t count, float* a_g, float* a_x, float* a_gate,
+                void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  NQ_PROF(st, "dn_gate_rev2");
+  if (count == 0) return NQ_OK;
+  if (!x || !gate || !g || !a_g || !a_x || !a_gate || count < 0) return nq_fail(NQ_ERR_ARG, "dimenet gate second order: bad argument");
+  hipLaunchKernelGGL(k_dn_gate_rev2, DN_GRID(count), x, gate, g, a_gx, a_gg, (long)count, a_g, a_x, a_gate);
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+int nq_dnt_embed_scatter(const float* rows, const int32_t* row_ptr, const int32_t* src_order, const int32_t* src_ptr, int32_t N, int64_t E, int32_t H, float* out,
+                         void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  NQ_PROF(st, "dn_embed_scatter");
+  if (!row_ptr || !src_ptr || !out || N < 1 || E < 0 || H < 1 || (E > 0 && (!rows || !src_order))) return nq_fail(NQ_ERR_ARG, "dimenet embedding scatter: bad argument");
+  hipLaunchKernelGGL(k_dn_embed_gab, DN_GRID((long)N * 2 * H), rows, row_ptr, src_order, src_ptr, N, H, out);
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }

@@ -8,9 +8,10 @@ torch-geometric (``torch_geometric.nn.models.DimeNetPlusPlus``, 2.4.0) is not pa
 What runs where
   * edge geometry and its adjoint, the float64 radial basis / radial table of the spherical basis, the triplet product (no [T, .] array, no triplet index
     list), x * gate, the output block's gated in-edge sum, the embedding block's gather + SiLU: csrc/dimenet.hip (``nq_dn_*``);
-  * every Linear (+ SiLU in the epilogue): the GEMM launchers; the atom embedding and the molecule sum: escn._EmbeddingFn / gemnet_oc._SegSumFn;
-  * forces: ONE ``torch.autograd.grad`` through the backward functions of these kernels.  They are first-order only, so a loss on the energies trains and a
-    loss on the forces (second-order derivatives) does not: ``training_step`` with ``forces_loss_coef != 0`` raises.  No CPU path.
+  * every Linear (+ SiLU in the epilogue): the GEMM launchers; the atom embedding: escn._EmbeddingFn; the molecule sum: nq_gn_segment_sum / nq_gn_gather;
+  * forces: ONE ``torch.autograd.grad`` through the backward functions of these kernels.  Each of them is differentiable once more (the tangent kernels
+    ``nq_dnt_*``), so with ``create_graph=True`` the forces carry the graph of the parameters and a loss on them trains: ``DimeNetPlusPlusForceLightning``.
+    ``DimeNetPlusPlusLightning.training_step`` keeps refusing ``forces_loss_coef != 0``.  No CPU path.
 """
 import math
 from types import SimpleNamespace
@@ -22,7 +23,7 @@ from torch import nn
 
 from . import _lib
 from .escn import _EmbeddingFn, _inverse_lists
-from .gemnet_oc import _SegSumFn, _new, _st
+from .gemnet_oc import _gather_raw, _new, _segsum_raw, _st
 from .lightning import _Task
 from .qhnet import _f32
 
@@ -124,8 +125,31 @@ def _colsum(rows_t):
 
 
 # ---- autograd wrappers ----------------------------------------------------------------------------------------------------------------------------------------
+# Every ``backward`` below is itself a Function (``_*Bwd``) with the launches the first-order path always had, so it can be differentiated once more: a loss on the
+# forces needs d/d parameters <v, dE/dpos>, v = d loss / d forces.  The adjoint that reaches a ``_*Bwd`` node is the tangent of the kernel along the position
+# displacement; its ``backward`` returns that tangent pushed through the kernel (the adjoint of ``g``) and the reverse of the tangent with respect to the
+# parameter-dependent inputs.  d, u and the positions get None there: the position gradient of a force loss is not provided.  Under ``create_graph=False`` the
+# ``_*Bwd.apply`` calls run without recording anything: the same launches and the same bits as before.
+_FORCE_PASS = [False]      # set around the force call of DimeNetPlusPlusPotential.forward: that pass asks for the position gradient only, so the backward
+#                            functions skip the parameter gradients (weight-gradient products, W_sbf2 partials, column sums) it would compute and drop
+
+
+def _only_tangents(what, *adjoints):
+    if any(a is not None for a in adjoints):
+        raise NotImplementedError(f"DimeNet++ second sweep: an adjoint of {what} was asked for (a loss on parameter gradients); only losses on energies and forces "
+                                  "are built")
+
+
+def _silu_reverse2(pre, g, a):
+    """a = the adjoint of g * silu'(pre) -> (a * silu'(pre), a * g * silu''(pre))."""
+    a_g, a_pre = torch.empty_like(pre), torch.empty_like(pre)
+    _lib.check(_lib.load().nq_dnt_silu(_lib.ptr(pre), _lib.ptr(g), _lib.ptr(a), pre.numel(), _lib.ptr(a_g), _lib.ptr(a_pre), _st()))
+    return a_g, a_pre
+
+
 class _LinFn(torch.autograd.Function):
-    """torch.nn.Linear with or without bias, SiLU optionally fused into the GEMM epilogue."""
+    """torch.nn.Linear with or without bias, SiLU optionally fused into the GEMM epilogue.  -> (y, pre): ``pre`` (None without SiLU) is an output only so that the
+    second sweep can hand its adjoint back to this node; nothing else reads it."""
 
     @staticmethod
     def forward(ctx, x, W, b, silu):
@@ -139,32 +163,83 @@ class _LinFn(torch.autograd.Function):
         _lib.check(lib.nq_linear_forward(_lib.ptr(x), _lib.ptr(W), _lib.ptr(b), _lib.ptr(pre), _lib.ptr(post), M, N, K, _st()))
         ctx.save_for_backward(x, W, pre if silu else x.new_zeros(0))
         ctx.silu, ctx.has_bias = silu, b is not None
-        return post if silu else pre
+        ctx.set_materialize_grads(False)
+        return (post, pre) if silu else (pre, None)
 
     @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
+    def backward(ctx, g, g_pre):
+        if g is None and g_pre is None:
+            return None, None, None, None
         x, W, pre = ctx.saved_tensors
-        g = _f32(g)
+        return (*_LinBwd.apply(g, g_pre, x, W, pre, ctx.silu, ctx.has_bias, ctx.needs_input_grad[0], ctx.needs_input_grad[1] and not _FORCE_PASS[0]), None)
+
+
+class _LinBwd(torch.autograd.Function):
+    """(g, g_pre) -> (gx, gW, gb) with gp = g silu'(pre) + g_pre.  Second sweep, a_gx given: a_gp = a_gx W^T (the forward launcher), a_W = gp^T a_gx
+    (nq_linear_weight_grad), then a_g = a_gp silu'(pre) and a_pre = a_gp g silu''(pre), which returns to ``_LinFn`` as the adjoint of its second output."""
+
+    @staticmethod
+    def forward(ctx, g, g_pre, x, W, pre, silu, has_bias, need_x, need_W):
+        lib = _lib.load()
         M, K = x.shape
         N = W.shape[0]
-        if ctx.silu and M > 0:
+        g = None if g is None else _f32(g)
+        gp = g
+        if silu and M > 0 and g is not None:
             gp = torch.empty_like(g)
             _lib.check(lib.nq_qh_act(_lib.ptr(pre), _lib.ptr(g), 0, 1.0, g.numel(), _lib.ptr(gp), _st()))
-            g = gp
+        if g_pre is not None:
+            gp = _f32(g_pre) if gp is None else gp + _f32(g_pre)
         gx = gW = gb = None
-        if ctx.needs_input_grad[0]:
+        if need_x:
             gx = torch.empty_like(x)
-            _lib.check(lib.nq_linear_input_grad(_lib.ptr(g), _lib.ptr(W), _lib.ptr(gx), M, N, K, 0, _st()))
-        if ctx.needs_input_grad[1]:
+            _lib.check(lib.nq_linear_input_grad(_lib.ptr(gp), _lib.ptr(W), _lib.ptr(gx), M, N, K, 0, _st()))
+        if need_W:
             gW = torch.empty_like(W)
             scr = _new(int(lib.nq_weight_grad_scratch_floats(M, N, K)) + 64, like=x)
-            if ctx.has_bias:
+            if has_bias:
                 gb = _new(N, like=x)
-                _lib.check(lib.nq_linear_weight_grad_bias(_lib.ptr(g), _lib.ptr(x), _lib.ptr(gW), _lib.ptr(gb), M, N, K, _lib.ptr(scr), _st()))
+                _lib.check(lib.nq_linear_weight_grad_bias(_lib.ptr(gp), _lib.ptr(x), _lib.ptr(gW), _lib.ptr(gb), M, N, K, _lib.ptr(scr), _st()))
             else:
-                _lib.check(lib.nq_linear_weight_grad(_lib.ptr(g), _lib.ptr(x), _lib.ptr(gW), M, N, K, _lib.ptr(scr), _st()))
-        return gx, gW, gb, None
+                _lib.check(lib.nq_linear_weight_grad(_lib.ptr(gp), _lib.ptr(x), _lib.ptr(gW), M, N, K, _lib.ptr(scr), _st()))
+        ctx.save_for_backward(g if g is not None else x.new_zeros(0), gp, W, pre)
+        ctx.silu, ctx.has = silu, (g is not None, g_pre is not None)
+        ctx.set_materialize_grads(False)
+        return gx, gW, gb
+
+    @staticmethod
+    def backward(ctx, a_gx, a_gW, a_gb):
+        _only_tangents("a weight gradient", a_gW, a_gb)
+        out = [None] * 9
+        if a_gx is None:
+            return tuple(out)
+        lib = _lib.load()
+        g, gp, W, pre = ctx.saved_tensors
+        a_gx = _f32(a_gx)
+        M, K = a_gx.shape
+        N = W.shape[0]
+        if M == 0:
+            return tuple(out)
+        a_gp = _new(M, N, like=a_gx)
+        _lib.check(lib.nq_linear_forward(_lib.ptr(a_gx), _lib.ptr(W), None, _lib.ptr(a_gp), None, M, N, K, _st()))
+        if ctx.needs_input_grad[3]:
+            a_W = torch.empty_like(W)
+            scr = _new(int(lib.nq_weight_grad_scratch_floats(M, N, K)) + 64, like=a_gx)
+            _lib.check(lib.nq_linear_weight_grad(_lib.ptr(gp), _lib.ptr(a_gx), _lib.ptr(a_W), M, N, K, _lib.ptr(scr), _st()))
+            out[3] = a_W
+        has_g, has_pre = ctx.has
+        if has_pre:
+            out[1] = a_gp
+        if has_g:
+            if ctx.silu:
+                out[0], out[4] = _silu_reverse2(pre, g, a_gp)
+            else:
+                out[0] = a_gp
+        return tuple(out)
+
+
+def _linear(x, W, b, silu=False):
+    return _LinFn.apply(x, W, b, silu)[0]
 
 
 class _GeomFn(torch.autograd.Function):
@@ -179,15 +254,35 @@ class _GeomFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gd, gu):
         plan = ctx.plan
-        gpos = _new(plan.N, 3, like=plan.pos)
         if gd is None and gu is None:
-            return gpos.zero_(), None
+            return _new(plan.N, 3, like=plan.pos).zero_(), None
+        return _GeomBwd.apply(gd, gu, plan), None
+
+
+class _GeomBwd(torch.autograd.Function):
+    """(gd, gu) -> gpos.  Second sweep: the adjoint of gpos is a displacement of the atoms; (a_gd, a_gu) = the tangent (td, tu) of (d, u) along it."""
+
+    @staticmethod
+    def forward(ctx, gd, gu, plan):
         gd = None if gd is None else _f32(gd)
         gu = None if gu is None else _f32(gu)
-        gvec = _new(plan.E, 3, like=plan.pos)
+        gpos, gvec = _new(plan.N, 3, like=plan.pos), _new(plan.E, 3, like=plan.pos)
         _lib.check(_lib.load().nq_dn_geom_backward(_lib.ptr(plan.d), _lib.ptr(plan.u), _lib.ptr(gd), _lib.ptr(gu), _lib.ptr(plan.row_ptr), _lib.ptr(plan.src_order),
                                                    _lib.ptr(plan.src_ptr), plan.N, plan.E, _lib.ptr(gvec), _lib.ptr(gpos), _st()))
-        return gpos, None
+        ctx.plan, ctx.has = plan, (gd is not None, gu is not None)
+        ctx.set_materialize_grads(False)
+        return gpos
+
+    @staticmethod
+    def backward(ctx, a_gpos):
+        if a_gpos is None:
+            return None, None, None
+        plan = ctx.plan
+        a_gpos = _f32(a_gpos)
+        td, tu = _new(plan.E, like=plan.pos), _new(plan.E, 3, like=plan.pos)
+        _lib.check(_lib.load().nq_dnt_geom(_lib.ptr(plan.d), _lib.ptr(plan.u), _lib.ptr(a_gpos), _lib.ptr(plan.src), _lib.ptr(plan.dst), plan.E, _lib.ptr(td),
+                                           _lib.ptr(tu), _st()))
+        return (td if ctx.has[0] else None), (tu if ctx.has[1] else None), None
 
 
 class _BasisFn(torch.autograd.Function):
@@ -208,15 +303,41 @@ class _BasisFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rbf, g_rad):
         d, freq = ctx.saved_tensors
-        roots, norms, S, R, cutoff, p = ctx.meta
+        return (*_BasisBwd.apply(g_rbf, g_rad, d, freq, ctx.meta, ctx.needs_input_grad[1] and not _FORCE_PASS[0]), None, None, None, None, None, None)
+
+
+class _BasisBwd(torch.autograd.Function):
+    """(g_rbf, g_rad) -> (gd, gfreq).  Second sweep, t = the adjoint of gd: a_g_rbf = t drbf/dd, a_g_rad = t dRad/dd, a_freq[n] = sum_e t g_rbf d2rbf/(dd dfreq_n)."""
+
+    @staticmethod
+    def forward(ctx, g_rbf, g_rad, d, freq, meta, need_freq):
+        roots, norms, S, R, cutoff, p = meta
         E = d.shape[0]
         g_rbf = None if g_rbf is None else _f32(g_rbf)
         g_rad = None if g_rad is None else _f32(g_rad)
         gd, rows = _new(E, like=d), _new(E, R, like=d)
         _lib.check(_lib.load().nq_dn_basis_backward(_lib.ptr(d), _lib.ptr(freq), _lib.ptr(roots), _lib.ptr(norms), E, S, R, float(cutoff), p, _lib.ptr(g_rbf),
                                                     _lib.ptr(g_rad), _lib.ptr(gd), _lib.ptr(rows), _st()))
-        gfreq = _colsum(rows) if ctx.needs_input_grad[1] else None
-        return gd, gfreq, None, None, None, None, None, None
+        gfreq = _colsum(rows) if need_freq else None
+        ctx.save_for_backward(d, freq, g_rbf if g_rbf is not None else d.new_zeros(0))
+        ctx.meta, ctx.has = meta, (g_rbf is not None, g_rad is not None)
+        ctx.set_materialize_grads(False)
+        return gd, gfreq
+
+    @staticmethod
+    def backward(ctx, t, a_gfreq):
+        _only_tangents("the frequency gradient", a_gfreq)
+        if t is None:
+            return (None,) * 6
+        d, freq, g_rbf = ctx.saved_tensors
+        roots, norms, S, R, cutoff, p = ctx.meta
+        E = d.shape[0]
+        t = _f32(t)
+        rbf_t, rad_t, rows = _new(E, R, like=d), _new(E, S * R, like=d), _new(E, R, like=d)
+        _lib.check(_lib.load().nq_dnt_basis(_lib.ptr(d), _lib.ptr(freq), _lib.ptr(roots), _lib.ptr(norms), E, S, R, float(cutoff), p, _lib.ptr(t),
+                                            _lib.ptr(g_rbf) if ctx.has[0] else None, _lib.ptr(rbf_t), _lib.ptr(rad_t), _lib.ptr(rows), _st()))
+        a_freq = _colsum(rows) if ctx.needs_input_grad[3] and ctx.has[0] else None
+        return (rbf_t if ctx.has[0] else None), (rad_t if ctx.has[1] else None), None, a_freq, None, None
 
 
 class _TripletFn(torch.autograd.Function):
@@ -235,20 +356,60 @@ class _TripletFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         x, Q, u, W2 = ctx.saved_tensors
         plan, S = ctx.meta
+        return (*_TripletBwd.apply(g, x, Q, u, W2, plan, S, ctx.needs_input_grad[3] and not _FORCE_PASS[0]), None, None)
+
+
+class _TripletBwd(torch.autograd.Function):
+    """g -> (gx, gQ, gu, gW2).  Second sweep: (a_gx, a_gQ, a_gu) are the tangents (tx, tQ, tu) of (x, Q, u); a_g = the tangent of m along them
+    (nq_dnt_triplet_forward) and (a_x, a_Q, a_W2) = the reverse of <g, that tangent> (nq_dnt_triplet_backward).  u gets None."""
+
+    @staticmethod
+    def forward(ctx, g, x, Q, u, W2, plan, S, need_W2):
+        lib = _lib.load()
         I, Bs = W2.shape
         g = _f32(g)
         gx, gQ, gu = torch.empty_like(x), torch.empty_like(Q), torch.empty_like(u)
         gW2 = scr = None
-        if ctx.needs_input_grad[3]:
+        if need_W2:
             gW2 = torch.empty_like(W2)
             scr = _new(int(lib.nq_dn_triplet_scratch_floats(plan.E, I, Bs)) + 64, like=x)
         _lib.check(lib.nq_dn_triplet_backward(_lib.ptr(x), _lib.ptr(Q), _lib.ptr(u), _lib.ptr(W2), _lib.ptr(plan.row_ptr), _lib.ptr(plan.src), _lib.ptr(plan.dst),
                                               _lib.ptr(plan.src_order), _lib.ptr(plan.src_ptr), plan.E, I, S, Bs, _lib.ptr(g), _lib.ptr(gx), _lib.ptr(gQ),
                                               _lib.ptr(gu), _lib.ptr(gW2), _lib.ptr(scr), _st()))
-        return gx, gQ, gu, gW2, None, None
+        ctx.save_for_backward(g, x, Q, u, W2)
+        ctx.meta = (plan, S)
+        ctx.set_materialize_grads(False)
+        return gx, gQ, gu, gW2
+
+    @staticmethod
+    def backward(ctx, tx, tQ, tu, a_gW2):
+        _only_tangents("the W_sbf2 gradient", a_gW2)
+        out = [None] * 8
+        if tx is None and tQ is None and tu is None:
+            return tuple(out)
+        lib = _lib.load()
+        g, x, Q, u, W2 = ctx.saved_tensors
+        plan, S = ctx.meta
+        I, Bs = W2.shape
+        tx, tQ, tu = (None if t is None else _f32(t) for t in (tx, tQ, tu))
+        if ctx.needs_input_grad[0]:
+            mt = _new(plan.E, I, like=x)
+            _lib.check(lib.nq_dnt_triplet_forward(_lib.ptr(x), _lib.ptr(Q), _lib.ptr(u), _lib.ptr(W2), _lib.ptr(tx), _lib.ptr(tQ), _lib.ptr(tu), _lib.ptr(plan.row_ptr),
+                                                  _lib.ptr(plan.src), _lib.ptr(plan.dst), plan.E, I, S, Bs, _lib.ptr(mt), _st()))
+            out[0] = mt
+        if any(ctx.needs_input_grad[k] for k in (1, 2, 4)):
+            a_x, a_Q = torch.empty_like(x), torch.empty_like(Q)
+            a_W2 = scr = None
+            if ctx.needs_input_grad[4]:
+                a_W2 = torch.empty_like(W2)
+                scr = _new(int(lib.nq_dn_triplet_scratch_floats(plan.E, I, Bs)) + 64, like=x)
+            _lib.check(lib.nq_dnt_triplet_backward(_lib.ptr(x), _lib.ptr(Q), _lib.ptr(u), _lib.ptr(W2), _lib.ptr(tx), _lib.ptr(tQ), _lib.ptr(tu), _lib.ptr(plan.row_ptr),
+                                                   _lib.ptr(plan.src), _lib.ptr(plan.dst), _lib.ptr(plan.src_order), _lib.ptr(plan.src_ptr), plan.E, I, S, Bs,
+                                                   _lib.ptr(g), _lib.ptr(a_x), _lib.ptr(a_Q), _lib.ptr(a_W2), _lib.ptr(scr), _st()))
+            out[1], out[2], out[4] = a_x, a_Q, a_W2
+        return tuple(out)
 
 
 class _GateFn(torch.autograd.Function):
@@ -262,11 +423,31 @@ class _GateFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        x, gate = ctx.saved_tensors
+        return _GateBwd.apply(g, *ctx.saved_tensors)
+
+
+class _GateBwd(torch.autograd.Function):
+    """g -> (gx, gg) = (g gate, g x).  Second sweep (one small kernel, nq_dnt_gate): a_g = a_gx gate + a_gg x, a_x = a_gg g, a_gate = a_gx g."""
+
+    @staticmethod
+    def forward(ctx, g, x, gate):
         g = _f32(g)
         gx, gg = torch.empty_like(x), torch.empty_like(x)
         _lib.check(_lib.load().nq_dn_gate_backward(_lib.ptr(x), _lib.ptr(gate), _lib.ptr(g), x.numel(), _lib.ptr(gx), _lib.ptr(gg), _st()))
+        ctx.save_for_backward(g, x, gate)
+        ctx.set_materialize_grads(False)
         return gx, gg
+
+    @staticmethod
+    def backward(ctx, a_gx, a_gg):
+        if a_gx is None and a_gg is None:
+            return None, None, None
+        g, x, gate = ctx.saved_tensors
+        a_gx, a_gg = (None if t is None else _f32(t) for t in (a_gx, a_gg))
+        a_g, a_x, a_gate = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+        _lib.check(_lib.load().nq_dnt_gate(_lib.ptr(x), _lib.ptr(gate), _lib.ptr(g), _lib.ptr(a_gx), _lib.ptr(a_gg), x.numel(), _lib.ptr(a_g), _lib.ptr(a_x),
+                                           _lib.ptr(a_gate), _st()))
+        return a_g, a_x, a_gate
 
 
 class _GateSumFn(torch.autograd.Function):
@@ -285,16 +466,40 @@ class _GateSumFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, gate = ctx.saved_tensors
-        plan = ctx.plan
+        return (*_GateSumBwd.apply(g, x, gate, ctx.plan), None)
+
+
+class _GateSumBwd(torch.autograd.Function):
+    """g [N, H] -> (gx, gg) = (g[dst] gate, g[dst] x).  Second sweep, composed from the existing calls (the [N, H] results are small): a_g = gatesum(a_gx, gate) +
+    gatesum(a_gg, x); (a_x, a_gate) = nq_dn_gatesum_backward with (a_gx, a_gg) in the places of (x, gate)."""
+
+    @staticmethod
+    def forward(ctx, g, x, gate, plan):
         g = _f32(g)
         gx, gg = torch.empty_like(x), torch.empty_like(x)
         _lib.check(_lib.load().nq_dn_gatesum_backward(_lib.ptr(x), _lib.ptr(gate), _lib.ptr(g), _lib.ptr(plan.dst), plan.E, x.shape[1], _lib.ptr(gx), _lib.ptr(gg),
                                                       _st()))
-        return gx, gg, None
+        ctx.save_for_backward(g, x, gate)
+        ctx.plan = plan
+        return gx, gg
+
+    @staticmethod
+    def backward(ctx, a_gx, a_gg):
+        lib = _lib.load()
+        g, x, gate = ctx.saved_tensors
+        plan = ctx.plan
+        H = x.shape[1]
+        a_gx, a_gg = _f32(a_gx), _f32(a_gg)
+        p, q = _new(plan.N, H, like=x), _new(plan.N, H, like=x)
+        _lib.check(lib.nq_dn_gatesum_forward(_lib.ptr(a_gx), _lib.ptr(gate), _lib.ptr(plan.row_ptr), plan.N, H, _lib.ptr(p), _st()))
+        _lib.check(lib.nq_dn_gatesum_forward(_lib.ptr(a_gg), _lib.ptr(x), _lib.ptr(plan.row_ptr), plan.N, H, _lib.ptr(q), _st()))
+        a_x, a_gate = torch.empty_like(x), torch.empty_like(x)
+        _lib.check(lib.nq_dn_gatesum_backward(_lib.ptr(a_gx), _lib.ptr(a_gg), _lib.ptr(g), _lib.ptr(plan.dst), plan.E, H, _lib.ptr(a_x), _lib.ptr(a_gate), _st()))
+        return p + q, a_x, a_gate, None
 
 
 class _EmbedFn(torch.autograd.Function):
-    """silu(AB[dst][:H] + AB[src][H:] + Cr + bias): the embedding block's Linear(3H, H) after its products over N and E rows."""
+    """silu(AB[dst][:H] + AB[src][H:] + Cr + bias): the embedding block's Linear(3H, H) after its products over N and E rows.  -> (y, pre), ``pre`` as in ``_LinFn``."""
 
     @staticmethod
     def forward(ctx, AB, Cr, bias, plan):
@@ -305,18 +510,82 @@ class _EmbedFn(torch.autograd.Function):
                                                    _lib.ptr(y), _st()))
         ctx.save_for_backward(pre)
         ctx.plan = plan
-        return y
+        ctx.set_materialize_grads(False)
+        return y, pre
+
+    @staticmethod
+    def backward(ctx, g, g_pre):
+        if g is None and g_pre is None:
+            return None, None, None, None
+        (pre,) = ctx.saved_tensors
+        return (*_EmbedBwd.apply(g, g_pre, pre, ctx.plan, ctx.needs_input_grad[2] and not _FORCE_PASS[0]), None)
+
+
+class _EmbedBwd(torch.autograd.Function):
+    """(g, g_pre) -> (gAB, gpre, gbias), gpre = g silu'(pre) + g_pre.  Second sweep: a = the adjoint of gpre (the one output the positions reach, through Cr):
+    a_g = a silu'(pre), a_pre = a g silu''(pre)."""
+
+    @staticmethod
+    def forward(ctx, g, g_pre, pre, plan, need_bias):
+        lib = _lib.load()
+        H = pre.shape[1]
+        g = None if g is None else _f32(g)
+        gAB = _new(plan.N, 2 * H, like=pre)
+        if g_pre is None:
+            gpre = torch.empty_like(pre)
+            _lib.check(lib.nq_dn_embed_backward(_lib.ptr(pre), _lib.ptr(g), _lib.ptr(plan.row_ptr), _lib.ptr(plan.src_order), _lib.ptr(plan.src_ptr), plan.N, plan.E,
+                                                H, _lib.ptr(gpre), _lib.ptr(gAB), _st()))
+        else:
+            gpre = _f32(g_pre)
+            if g is not None and plan.E:
+                gp = torch.empty_like(pre)
+                _lib.check(lib.nq_qh_act(_lib.ptr(pre), _lib.ptr(g), 0, 1.0, g.numel(), _lib.ptr(gp), _st()))
+                gpre = gp + gpre
+            _lib.check(lib.nq_dnt_embed_scatter(_lib.ptr(gpre), _lib.ptr(plan.row_ptr), _lib.ptr(plan.src_order), _lib.ptr(plan.src_ptr), plan.N, plan.E, H,
+                                                _lib.ptr(gAB), _st()))
+        ctx.save_for_backward(pre, g if g is not None else pre.new_zeros(0))
+        ctx.has = (g is not None, g_pre is not None)
+        ctx.set_materialize_grads(False)
+        return gAB, gpre, (_colsum(gpre) if need_bias else None)
+
+    @staticmethod
+    def backward(ctx, a_gAB, a, a_gbias):
+        _only_tangents("the embedding's atom-side gradients", a_gAB, a_gbias)
+        if a is None:
+            return (None,) * 5
+        pre, g = ctx.saved_tensors
+        a = _f32(a)
+        a_g = a_pre = None
+        if ctx.has[0]:
+            a_g, a_pre = _silu_reverse2(pre, g, a)
+        return a_g, (a if ctx.has[1] else None), a_pre, None, None
+
+
+class _MolSumFn(torch.autograd.Function):
+    """out[b] = the sum of the rows of molecule b (gemnet_oc._SegSumFn's launches), differentiable any number of times: the adjoint of the sum is a gather
+    (``_MolGatherFn``) whose adjoint is the sum again."""
+
+    @staticmethod
+    def forward(ctx, rows, ptr, owner, n):
+        rows = _f32(rows)
+        ctx.meta = (ptr, owner)
+        return _segsum_raw(rows, None, ptr, n, rows.shape[1])
 
     @staticmethod
     def backward(ctx, g):
-        (pre,) = ctx.saved_tensors
-        plan = ctx.plan
-        H = pre.shape[1]
-        g = _f32(g)
-        gpre, gAB = torch.empty_like(pre), _new(plan.N, 2 * H, like=pre)
-        _lib.check(_lib.load().nq_dn_embed_backward(_lib.ptr(pre), _lib.ptr(g), _lib.ptr(plan.row_ptr), _lib.ptr(plan.src_order), _lib.ptr(plan.src_ptr), plan.N,
-                                                    plan.E, H, _lib.ptr(gpre), _lib.ptr(gAB), _st()))
-        return gAB, gpre, (_colsum(gpre) if ctx.needs_input_grad[2] else None), None
+        return _MolGatherFn.apply(g, *ctx.meta), None, None, None
+
+
+class _MolGatherFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, ptr, owner):
+        ctx.meta = (ptr, owner)
+        return _gather_raw(_f32(g), owner, None, owner.numel())
+
+    @staticmethod
+    def backward(ctx, a):
+        ptr, owner = ctx.meta
+        return _MolSumFn.apply(a, ptr, owner, ptr.numel() - 1), None, None
 
 
 # ---- the core's module tree (parameter holders with torch-geometric's initialisation; the arithmetic is in DimeNetPlusPlus.forward) ---------------------------
@@ -427,7 +696,7 @@ class DimeNetPlusPlus(nn.Module):
         return p.detach() if self._frozen else p
 
     def _dense(self, lin, x, silu=False):
-        return _LinFn.apply(x, self._w(lin.weight), None if lin.bias is None else self._w(lin.bias), silu)
+        return _linear(x, self._w(lin.weight), None if lin.bias is None else self._w(lin.bias), silu)
 
     def _residual(self, layer, h):
         return h + self._dense(layer.lin2, self._dense(layer.lin1, h, True), True)
@@ -447,7 +716,7 @@ class DimeNetPlusPlus(nn.Module):
         W1 = self._w(blk.lin_sbf1.weight)
         Bs = W1.shape[0]
         W1v = W1.view(Bs, S, R)
-        Q = _LinFn.apply(rad, torch.block_diag(*[W1v[:, l, :] for l in range(S)]), None, False)        # Q[e][l][b] = sum_n rad[e][l][n] W1[b][l R + n]
+        Q = _linear(rad, torch.block_diag(*[W1v[:, l, :] for l in range(S)]), None)               # Q[e][l][b] = sum_n rad[e][l][n] W1[b][l R + n]
         m = _TripletFn.apply(x_kj, Q, u, self._w(blk.lin_sbf2.weight), plan, S)
         h = x_ji + self._dense(blk.lin_up, m, True)
         for layer in blk.layers_before_skip:
@@ -465,9 +734,9 @@ class DimeNetPlusPlus(nn.Module):
         rbf, rad = _BasisFn.apply(d, self._w(self.rbf.freq), roots, norms, self.num_spherical, self.num_radial, self.cutoff, self.rbf.p)
         W = self._w(self.emb.lin.weight)
         hz = _EmbeddingFn.apply(self._w(self.emb.emb.weight), plan.z, plan.z_levels)
-        AB = _LinFn.apply(hz, torch.cat([W[:, :H], W[:, H:2 * H]], 0), None, False)
-        Cr = _LinFn.apply(self._dense(self.emb.lin_rbf, rbf, True), W[:, 2 * H:].contiguous(), None, False)
-        x = _EmbedFn.apply(AB, Cr, self._w(self.emb.lin.bias), plan)
+        AB = _linear(hz, torch.cat([W[:, :H], W[:, H:2 * H]], 0), None)
+        Cr = _linear(self._dense(self.emb.lin_rbf, rbf, True), W[:, 2 * H:].contiguous(), None)
+        x = _EmbedFn.apply(AB, Cr, self._w(self.emb.lin.bias), plan)[0]
         P = self._output(self.output_blocks[0], x, rbf, plan)
         if record is not None:
             record.update(rbf=rbf, rad=rad, block_out=[x])
@@ -476,7 +745,7 @@ class DimeNetPlusPlus(nn.Module):
             P = P + self._output(out, x, rbf, plan)
             if record is not None:
                 record["block_out"].append(x)
-        return _SegSumFn.apply(P, plan.mol_ptr, plan.atom_mol, plan.B)
+        return _MolSumFn.apply(P, plan.mol_ptr, plan.atom_mol, plan.B)
 
 
 class Swish(nn.Module):
@@ -517,10 +786,15 @@ class DimeNetPlusPlusPotential(nn.Module):
         _lib.check_prepared(plan, data)
         return plan
 
-    def forward(self, data, return_intermediates: bool = False):
-        """-> (energies [B], forces [N, 3]); the forces carry no autograd graph, the energies carry the graph of the parameters when gradients are enabled."""
+    def forward(self, data, return_intermediates: bool = False, create_graph: bool = False):
+        """-> (energies [B], forces [N, 3]); the energies carry the graph of the parameters when gradients are enabled.  The forces carry no autograd graph unless
+        ``create_graph`` is set (and gradients are enabled): then the force call is ``torch.autograd.grad(..., create_graph=True)`` and the forces, bitwise those of
+        the default path, carry the graph of the parameters (the second sweep of the wrappers above), so a loss on them trains.  That graph reaches the
+        parameters only: the second sweep forms no adjoint of the distances, the directions or the positions, so the position gradient of a force loss is not
+        provided (the internal position leaf is never handed out)."""
         plan = self._plan(data)
         with_graph = torch.is_grad_enabled()
+        second = bool(create_graph) and with_graph
         net = self.net
         net._frozen = not with_graph
         rec = {} if return_intermediates else None
@@ -533,12 +807,14 @@ class DimeNetPlusPlusPotential(nn.Module):
                     h = net._dense(self.regr_or_cls_nn[k], h, True)
                 pred = net._dense(self.regr_or_cls_nn[6], h).reshape(-1)
                 if plan.E:
-                    (gpos,) = torch.autograd.grad(pred.sum(), pos, retain_graph=with_graph)
+                    _FORCE_PASS[0] = True
+                    (gpos,) = torch.autograd.grad(pred.sum(), pos, retain_graph=with_graph, create_graph=second)
                 else:
                     gpos = torch.zeros_like(pos)
         finally:
             net._frozen = False
-        forces = -gpos.detach()
+            _FORCE_PASS[0] = False
+        forces = -gpos if second and gpos.requires_grad else -gpos.detach()
         if not with_graph:
             pred = pred.detach()
         if rec is not None:
@@ -550,7 +826,7 @@ class DimeNetPlusPlusPotential(nn.Module):
 
 
 class DimeNetPlusPlusLightning(_Task):
-    """dimenetplusplus.py:116-270.  ``step`` is the reference's; ``training_step`` refuses a force loss (second-order sweep not implemented)."""
+    """dimenetplusplus.py:116-270.  ``step`` is the reference's; ``training_step`` refuses a force loss (the second-order sweep is ``DimeNetPlusPlusForceLightning``)."""
 
     def __init__(self, net: nn.Module, loss, metric, energy_loss_coef: float, forces_loss_coef: float, monitor_loss: str = "val/loss", model_name: str = None,
                  lr_scheduler=None, scheduler_args=None, optimizer=None):
@@ -578,8 +854,8 @@ class DimeNetPlusPlusLightning(_Task):
     def training_step(self, batch, batch_idx):
         if self.loss_forces_coef != 0:
             raise NotImplementedError("DimeNet++ training with forces_loss_coef != 0 differentiates the forces with respect to the parameters: the second-order "
-                                      "sweep through the triplet kernels is not implemented; train with forces_loss_coef = 0 (validation, test and predict "
-                                      "work with any coefficient)")
+                                      "sweep is not part of this class; use DimeNetPlusPlusForceLightning (same constructor, same state_dict) or train with "
+                                      "forces_loss_coef = 0 (validation, test and predict work with any coefficient)")
         return super().training_step(batch, batch_idx)
 
     def configure_optimizers(self):
@@ -588,3 +864,15 @@ class DimeNetPlusPlusLightning(_Task):
         if self.hparams.lr_scheduler is not None:
             scheduler = self.hparams.lr_scheduler(optimizer=opt, **(self.scheduler_args or {}))
         return {"optimizer": opt, "monitor": self.monitor_loss, "lr_scheduler": scheduler}
+
+
+class DimeNetPlusPlusForceLightning(DimeNetPlusPlusLightning):
+    """The same task with the reference's ``create_graph=self.training`` (dimenetplusplus.py:99-109): in training the forces carry the graph of the parameters, so
+    ``training_step`` takes any ``forces_loss_coef`` (config/model/dimenetplusplus.yaml: 1 and 1).  Constructor, ``state_dict`` keys, validation, test and predict
+    are the parent's.  The gradient of the force loss reaches the parameters, not the positions."""
+
+    def forward(self, data):
+        return self.net(data, create_graph=self.net.training)
+
+    def training_step(self, batch, batch_idx):
+        return _Task.training_step(self, batch, batch_idx)
