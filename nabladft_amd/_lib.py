@@ -3,6 +3,8 @@ symbol is missing this module raises, it never routes around the HIP engine."""
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NABLAQ_LIB") or os.path.join(_HERE, "libnablaq.so")   # NABLAQ_LIB: development builds (scripts/ablate.sh)
 ABI_VERSION = 17
@@ -276,11 +278,22 @@ def ptr(t):
 def stream_ptr():
     """The current HIP stream of the current device as a C pointer.  Asked once per launch by every wrapper: the raw-handle query of torch (what its own
     compiled-kernel launchers use) instead of building a ``torch.cuda.Stream`` object each time."""
-    import torch
     raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
     if raw is None:
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
     return C.c_void_p(raw(torch.cuda.current_device()))
+
+
+def _st():
+    return stream_ptr()
+
+
+def _f32(t):
+    return t.to(torch.float32).contiguous()
+
+
+def _new(*shape, like):
+    return torch.empty(*shape, device=like.device, dtype=torch.float32)
 
 
 def profile_enable(on: bool):

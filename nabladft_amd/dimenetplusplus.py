@@ -8,7 +8,7 @@ torch-geometric (``torch_geometric.nn.models.DimeNetPlusPlus``, 2.4.0) is not pa
 What runs where
   * edge geometry and its adjoint, the float64 radial basis / radial table of the spherical basis, the triplet product (no [T, .] array, no triplet index
     list), x * gate, the output block's gated in-edge sum, the embedding block's gather + SiLU: csrc/dimenet.hip (``nq_dn_*``);
-  * every Linear (+ SiLU in the epilogue): the GEMM launchers; the atom embedding: escn._EmbeddingFn; the molecule sum: nq_gn_segment_sum / nq_gn_gather;
+  * every Linear (+ SiLU in the epilogue): dense.Linear2 on the GEMM launchers; the atom embedding: escn._EmbeddingFn; the molecule sum: gemnet_oc._SegSumFn;
   * forces: ONE ``torch.autograd.grad`` through the backward functions of these kernels.  Each of them is differentiable once more (the tangent kernels
     ``nq_dnt_*``), so with ``create_graph=True`` the forces carry the graph of the parameters and a loss on them trains: ``DimeNetPlusPlusForceLightning``.
     ``DimeNetPlusPlusLightning.training_step`` keeps refusing ``forces_loss_coef != 0``.  No CPU path.
@@ -21,11 +21,11 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, dense
+from ._lib import _f32, _new, _st
 from .escn import _EmbeddingFn, _inverse_lists
-from .gemnet_oc import _gather_raw, _new, _segsum_raw, _st
+from .gemnet_oc import _SegSumFn
 from .lightning import _Task
-from .qhnet import _f32
 
 NUM_ELEMENTS = 95
 INT_EMB_SIZES = (64, 128, 192, 256)        # one lane per channel of the triplet kernels, up to 4 registers per lane
@@ -129,117 +129,9 @@ def _colsum(rows_t):
 # forces needs d/d parameters <v, dE/dpos>, v = d loss / d forces.  The adjoint that reaches a ``_*Bwd`` node is the tangent of the kernel along the position
 # displacement; its ``backward`` returns that tangent pushed through the kernel (the adjoint of ``g``) and the reverse of the tangent with respect to the
 # parameter-dependent inputs.  d, u and the positions get None there: the position gradient of a force loss is not provided.  Under ``create_graph=False`` the
-# ``_*Bwd.apply`` calls run without recording anything: the same launches and the same bits as before.
-_FORCE_PASS = [False]      # set around the force call of DimeNetPlusPlusPotential.forward: that pass asks for the position gradient only, so the backward
-#                            functions skip the parameter gradients (weight-gradient products, W_sbf2 partials, column sums) it would compute and drop
-
-
-def _only_tangents(what, *adjoints):
-    if any(a is not None for a in adjoints):
-        raise NotImplementedError(f"DimeNet++ second sweep: an adjoint of {what} was asked for (a loss on parameter gradients); only losses on energies and forces "
-                                  "are built")
-
-
-def _silu_reverse2(pre, g, a):
-    """a = the adjoint of g * silu'(pre) -> (a * silu'(pre), a * g * silu''(pre))."""
-    a_g, a_pre = torch.empty_like(pre), torch.empty_like(pre)
-    _lib.check(_lib.load().nq_dnt_silu(_lib.ptr(pre), _lib.ptr(g), _lib.ptr(a), pre.numel(), _lib.ptr(a_g), _lib.ptr(a_pre), _st()))
-    return a_g, a_pre
-
-
-class _LinFn(torch.autograd.Function):
-    """torch.nn.Linear with or without bias, SiLU optionally fused into the GEMM epilogue.  -> (y, pre): ``pre`` (None without SiLU) is an output only so that the
-    second sweep can hand its adjoint back to this node; nothing else reads it."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, silu):
-        lib = _lib.load()
-        x, W = _f32(x), _f32(W)
-        b = None if b is None else _f32(b)
-        M, K = x.shape
-        N = W.shape[0]
-        pre = _new(M, N, like=x)
-        post = torch.empty_like(pre) if silu else None
-        _lib.check(lib.nq_linear_forward(_lib.ptr(x), _lib.ptr(W), _lib.ptr(b), _lib.ptr(pre), _lib.ptr(post), M, N, K, _st()))
-        ctx.save_for_backward(x, W, pre if silu else x.new_zeros(0))
-        ctx.silu, ctx.has_bias = silu, b is not None
-        ctx.set_materialize_grads(False)
-        return (post, pre) if silu else (pre, None)
-
-    @staticmethod
-    def backward(ctx, g, g_pre):
-        if g is None and g_pre is None:
-            return None, None, None, None
-        x, W, pre = ctx.saved_tensors
-        return (*_LinBwd.apply(g, g_pre, x, W, pre, ctx.silu, ctx.has_bias, ctx.needs_input_grad[0], ctx.needs_input_grad[1] and not _FORCE_PASS[0]), None)
-
-
-class _LinBwd(torch.autograd.Function):
-    """(g, g_pre) -> (gx, gW, gb) with gp = g silu'(pre) + g_pre.  Second sweep, a_gx given: a_gp = a_gx W^T (the forward launcher), a_W = gp^T a_gx
-    (nq_linear_weight_grad), then a_g = a_gp silu'(pre) and a_pre = a_gp g silu''(pre), which returns to ``_LinFn`` as the adjoint of its second output."""
-
-    @staticmethod
-    def forward(ctx, g, g_pre, x, W, pre, silu, has_bias, need_x, need_W):
-        lib = _lib.load()
-        M, K = x.shape
-        N = W.shape[0]
-        g = None if g is None else _f32(g)
-        gp = g
-        if silu and M > 0 and g is not None:
-            gp = torch.empty_like(g)
-            _lib.check(lib.nq_qh_act(_lib.ptr(pre), _lib.ptr(g), 0, 1.0, g.numel(), _lib.ptr(gp), _st()))
-        if g_pre is not None:
-            gp = _f32(g_pre) if gp is None else gp + _f32(g_pre)
-        gx = gW = gb = None
-        if need_x:
-            gx = torch.empty_like(x)
-            _lib.check(lib.nq_linear_input_grad(_lib.ptr(gp), _lib.ptr(W), _lib.ptr(gx), M, N, K, 0, _st()))
-        if need_W:
-            gW = torch.empty_like(W)
-            scr = _new(int(lib.nq_weight_grad_scratch_floats(M, N, K)) + 64, like=x)
-            if has_bias:
-                gb = _new(N, like=x)
-                _lib.check(lib.nq_linear_weight_grad_bias(_lib.ptr(gp), _lib.ptr(x), _lib.ptr(gW), _lib.ptr(gb), M, N, K, _lib.ptr(scr), _st()))
-            else:
-                _lib.check(lib.nq_linear_weight_grad(_lib.ptr(gp), _lib.ptr(x), _lib.ptr(gW), M, N, K, _lib.ptr(scr), _st()))
-        ctx.save_for_backward(g if g is not None else x.new_zeros(0), gp, W, pre)
-        ctx.silu, ctx.has = silu, (g is not None, g_pre is not None)
-        ctx.set_materialize_grads(False)
-        return gx, gW, gb
-
-    @staticmethod
-    def backward(ctx, a_gx, a_gW, a_gb):
-        _only_tangents("a weight gradient", a_gW, a_gb)
-        out = [None] * 9
-        if a_gx is None:
-            return tuple(out)
-        lib = _lib.load()
-        g, gp, W, pre = ctx.saved_tensors
-        a_gx = _f32(a_gx)
-        M, K = a_gx.shape
-        N = W.shape[0]
-        if M == 0:
-            return tuple(out)
-        a_gp = _new(M, N, like=a_gx)
-        _lib.check(lib.nq_linear_forward(_lib.ptr(a_gx), _lib.ptr(W), None, _lib.ptr(a_gp), None, M, N, K, _st()))
-        if ctx.needs_input_grad[3]:
-            a_W = torch.empty_like(W)
-            scr = _new(int(lib.nq_weight_grad_scratch_floats(M, N, K)) + 64, like=a_gx)
-            _lib.check(lib.nq_linear_weight_grad(_lib.ptr(gp), _lib.ptr(a_gx), _lib.ptr(a_W), M, N, K, _lib.ptr(scr), _st()))
-            out[3] = a_W
-        has_g, has_pre = ctx.has
-        if has_pre:
-            out[1] = a_gp
-        if has_g:
-            if ctx.silu:
-                out[0], out[4] = _silu_reverse2(pre, g, a_gp)
-            else:
-                out[0] = a_gp
-        return tuple(out)
-
-
-def _linear(x, W, b, silu=False):
-    return _LinFn.apply(x, W, b, silu)[0]
+# ``_*Bwd.apply`` calls run without recording anything: the same launches and the same bits as before.  The Linear layers are
+# ``dense.Linear2``, built the same way; ``dense._FORCE_PASS`` is set around the force call of DimeNetPlusPlusPotential.forward: that pass asks for the position
+# gradient only, so the backward functions skip the parameter gradients (weight-gradient products, W_sbf2 partials, column sums) it would compute and drop.
 
 
 class _GeomFn(torch.autograd.Function):
@@ -303,7 +195,7 @@ class _BasisFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rbf, g_rad):
         d, freq = ctx.saved_tensors
-        return (*_BasisBwd.apply(g_rbf, g_rad, d, freq, ctx.meta, ctx.needs_input_grad[1] and not _FORCE_PASS[0]), None, None, None, None, None, None)
+        return (*_BasisBwd.apply(g_rbf, g_rad, d, freq, ctx.meta, ctx.needs_input_grad[1] and not dense._FORCE_PASS[0]), None, None, None, None, None, None)
 
 
 class _BasisBwd(torch.autograd.Function):
@@ -326,7 +218,7 @@ class _BasisBwd(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, t, a_gfreq):
-        _only_tangents("the frequency gradient", a_gfreq)
+        dense.only_tangents("the frequency gradient", a_gfreq)
         if t is None:
             return (None,) * 6
         d, freq, g_rbf = ctx.saved_tensors
@@ -358,7 +250,7 @@ class _TripletFn(torch.autograd.Function):
     def backward(ctx, g):
         x, Q, u, W2 = ctx.saved_tensors
         plan, S = ctx.meta
-        return (*_TripletBwd.apply(g, x, Q, u, W2, plan, S, ctx.needs_input_grad[3] and not _FORCE_PASS[0]), None, None)
+        return (*_TripletBwd.apply(g, x, Q, u, W2, plan, S, ctx.needs_input_grad[3] and not dense._FORCE_PASS[0]), None, None)
 
 
 class _TripletBwd(torch.autograd.Function):
@@ -385,7 +277,7 @@ class _TripletBwd(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, tx, tQ, tu, a_gW2):
-        _only_tangents("the W_sbf2 gradient", a_gW2)
+        dense.only_tangents("the W_sbf2 gradient", a_gW2)
         out = [None] * 8
         if tx is None and tQ is None and tu is None:
             return tuple(out)
@@ -499,7 +391,7 @@ class _GateSumBwd(torch.autograd.Function):
 
 
 class _EmbedFn(torch.autograd.Function):
-    """silu(AB[dst][:H] + AB[src][H:] + Cr + bias): the embedding block's Linear(3H, H) after its products over N and E rows.  -> (y, pre), ``pre`` as in ``_LinFn``."""
+    """silu(AB[dst][:H] + AB[src][H:] + Cr + bias): the embedding block's Linear(3H, H) after its products over N and E rows.  -> (y, pre), ``pre`` as in ``dense.Linear2``."""
 
     @staticmethod
     def forward(ctx, AB, Cr, bias, plan):
@@ -518,7 +410,7 @@ class _EmbedFn(torch.autograd.Function):
         if g is None and g_pre is None:
             return None, None, None, None
         (pre,) = ctx.saved_tensors
-        return (*_EmbedBwd.apply(g, g_pre, pre, ctx.plan, ctx.needs_input_grad[2] and not _FORCE_PASS[0]), None)
+        return (*_EmbedBwd.apply(g, g_pre, pre, ctx.plan, ctx.needs_input_grad[2] and not dense._FORCE_PASS[0]), None)
 
 
 class _EmbedBwd(torch.autograd.Function):
@@ -538,9 +430,7 @@ class _EmbedBwd(torch.autograd.Function):
         else:
             gpre = _f32(g_pre)
             if g is not None and plan.E:
-                gp = torch.empty_like(pre)
-                _lib.check(lib.nq_qh_act(_lib.ptr(pre), _lib.ptr(g), 0, 1.0, g.numel(), _lib.ptr(gp), _st()))
-                gpre = gp + gpre
+                gpre = dense.silu_grad(pre, g) + gpre
             _lib.check(lib.nq_dnt_embed_scatter(_lib.ptr(gpre), _lib.ptr(plan.row_ptr), _lib.ptr(plan.src_order), _lib.ptr(plan.src_ptr), plan.N, plan.E, H,
                                                 _lib.ptr(gAB), _st()))
         ctx.save_for_backward(pre, g if g is not None else pre.new_zeros(0))
@@ -550,42 +440,15 @@ class _EmbedBwd(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, a_gAB, a, a_gbias):
-        _only_tangents("the embedding's atom-side gradients", a_gAB, a_gbias)
+        dense.only_tangents("the embedding's atom-side gradients", a_gAB, a_gbias)
         if a is None:
             return (None,) * 5
         pre, g = ctx.saved_tensors
         a = _f32(a)
         a_g = a_pre = None
         if ctx.has[0]:
-            a_g, a_pre = _silu_reverse2(pre, g, a)
+            a_g, a_pre = dense.silu_grad2(pre, g, a)
         return a_g, (a if ctx.has[1] else None), a_pre, None, None
-
-
-class _MolSumFn(torch.autograd.Function):
-    """out[b] = the sum of the rows of molecule b (gemnet_oc._SegSumFn's launches), differentiable any number of times: the adjoint of the sum is a gather
-    (``_MolGatherFn``) whose adjoint is the sum again."""
-
-    @staticmethod
-    def forward(ctx, rows, ptr, owner, n):
-        rows = _f32(rows)
-        ctx.meta = (ptr, owner)
-        return _segsum_raw(rows, None, ptr, n, rows.shape[1])
-
-    @staticmethod
-    def backward(ctx, g):
-        return _MolGatherFn.apply(g, *ctx.meta), None, None, None
-
-
-class _MolGatherFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, g, ptr, owner):
-        ctx.meta = (ptr, owner)
-        return _gather_raw(_f32(g), owner, None, owner.numel())
-
-    @staticmethod
-    def backward(ctx, a):
-        ptr, owner = ctx.meta
-        return _MolSumFn.apply(a, ptr, owner, ptr.numel() - 1), None, None
 
 
 # ---- the core's module tree (parameter holders with torch-geometric's initialisation; the arithmetic is in DimeNetPlusPlus.forward) ---------------------------
@@ -696,7 +559,7 @@ class DimeNetPlusPlus(nn.Module):
         return p.detach() if self._frozen else p
 
     def _dense(self, lin, x, silu=False):
-        return _linear(x, self._w(lin.weight), None if lin.bias is None else self._w(lin.bias), silu)
+        return dense.linear2(x, self._w(lin.weight), None if lin.bias is None else self._w(lin.bias), silu)
 
     def _residual(self, layer, h):
         return h + self._dense(layer.lin2, self._dense(layer.lin1, h, True), True)
@@ -716,7 +579,7 @@ class DimeNetPlusPlus(nn.Module):
         W1 = self._w(blk.lin_sbf1.weight)
         Bs = W1.shape[0]
         W1v = W1.view(Bs, S, R)
-        Q = _linear(rad, torch.block_diag(*[W1v[:, l, :] for l in range(S)]), None)               # Q[e][l][b] = sum_n rad[e][l][n] W1[b][l R + n]
+        Q = dense.linear2(rad, torch.block_diag(*[W1v[:, l, :] for l in range(S)]), None)         # Q[e][l][b] = sum_n rad[e][l][n] W1[b][l R + n]
         m = _TripletFn.apply(x_kj, Q, u, self._w(blk.lin_sbf2.weight), plan, S)
         h = x_ji + self._dense(blk.lin_up, m, True)
         for layer in blk.layers_before_skip:
@@ -734,8 +597,8 @@ class DimeNetPlusPlus(nn.Module):
         rbf, rad = _BasisFn.apply(d, self._w(self.rbf.freq), roots, norms, self.num_spherical, self.num_radial, self.cutoff, self.rbf.p)
         W = self._w(self.emb.lin.weight)
         hz = _EmbeddingFn.apply(self._w(self.emb.emb.weight), plan.z, plan.z_levels)
-        AB = _linear(hz, torch.cat([W[:, :H], W[:, H:2 * H]], 0), None)
-        Cr = _linear(self._dense(self.emb.lin_rbf, rbf, True), W[:, 2 * H:].contiguous(), None)
+        AB = dense.linear2(hz, torch.cat([W[:, :H], W[:, H:2 * H]], 0), None)
+        Cr = dense.linear2(self._dense(self.emb.lin_rbf, rbf, True), W[:, 2 * H:].contiguous(), None)
         x = _EmbedFn.apply(AB, Cr, self._w(self.emb.lin.bias), plan)[0]
         P = self._output(self.output_blocks[0], x, rbf, plan)
         if record is not None:
@@ -745,7 +608,7 @@ class DimeNetPlusPlus(nn.Module):
             P = P + self._output(out, x, rbf, plan)
             if record is not None:
                 record["block_out"].append(x)
-        return _MolSumFn.apply(P, plan.mol_ptr, plan.atom_mol, plan.B)
+        return _SegSumFn.apply(P, plan.mol_ptr, plan.atom_mol, plan.B)
 
 
 class Swish(nn.Module):
@@ -807,13 +670,13 @@ class DimeNetPlusPlusPotential(nn.Module):
                     h = net._dense(self.regr_or_cls_nn[k], h, True)
                 pred = net._dense(self.regr_or_cls_nn[6], h).reshape(-1)
                 if plan.E:
-                    _FORCE_PASS[0] = True
+                    dense._FORCE_PASS[0] = True
                     (gpos,) = torch.autograd.grad(pred.sum(), pos, retain_graph=with_graph, create_graph=second)
                 else:
                     gpos = torch.zeros_like(pos)
         finally:
             net._frozen = False
-            _FORCE_PASS[0] = False
+            dense._FORCE_PASS[0] = False
         forces = -gpos if second and gpos.requires_grad else -gpos.detach()
         if not with_graph:
             pred = pred.detach()

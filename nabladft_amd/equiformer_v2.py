@@ -22,13 +22,13 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, dense
+from ._lib import _f32, _new, _st
 from .escn import (CoefficientOrder, GaussianSmearing, _BlocksInFn, _BlocksOutFn, _S2ActBlocksFn, s2_activation_fusable, _EmbeddingFn, _RotateBackFn, _RotateFn, _RowFn, _silu, eSCN, j_matrices,
                    s2_grids)
 from . import gemnet_oc as _gemnet
-from .gemnet_oc import _DenseFn, _MulFn, _SO2PairFn, _SegSumFn, _new, _st, fused_pairs_available, lin
+from .gemnet_oc import _DenseFn, _MulFn, _SO2PairFn, _SegSumFn, fused_pairs_available, lin
 from .phisnet import _SphLinearFn
-from .qhnet import _LinearBiasFn, _f32
 
 _AVG_NUM_NODES = 39.65745326960467          # equiformer_v2_oc20.py:47-48
 _AVG_DEGREE = 19.16009564536883
@@ -211,7 +211,7 @@ def _linear(mod, x, act=False):
     """torch.nn.Linear parameters on the MFMA GEMM (SiLU fused when ``act``)."""
     if mod.bias is None:
         return _DenseFn.apply(x, mod.weight, 1.0 if act else False)
-    return _LinearBiasFn.apply(x, mod.weight, mod.bias, act)
+    return dense.linear(x, mod.weight, mod.bias, act)
 
 
 # ---- helper modules whose buffers are part of the reference's state_dict ----------------------------------------------------------------------------------------
@@ -337,7 +337,7 @@ class RadialFunction(nn.Module):
         """Columns [start, start + length) of the last Linear's output: a contiguous row block of its weight (no copy of the output)."""
         fc = self.net[-1]
         length = fc.out_features - start if length is None else length
-        return _LinearBiasFn.apply(h, fc.weight.narrow(0, start, length), fc.bias.narrow(0, start, length), False)
+        return dense.linear(h, fc.weight.narrow(0, start, length), fc.bias.narrow(0, start, length), False)
 
     def forward(self, x):
         return self.last(self.hidden(x))

@@ -21,10 +21,11 @@ from typing import List
 import numpy as np
 import torch
 
-from . import _lib, cg
+from . import _lib, cg, dense
 from . import gemnet_oc as _gemnet
-from .gemnet_oc import _DenseFn, _MulFn, _SO2GatedPairFn, _SegSumFn, _gather_raw, _new, _segsum_raw, _st, fused_pairs_available, lin
-from .qhnet import _ActFn, _LinearBiasFn, _MatmulFn, _f32
+from ._lib import _f32, _new, _st
+from .gemnet_oc import _DenseFn, _MulFn, _SO2GatedPairFn, _SegSumFn, _gather_raw, _segsum_raw, fused_pairs_available, lin
+from .qhnet import _ActFn
 
 
 # ---- constants -------------------------------------------------------------------------------------------------------------------------------
@@ -374,7 +375,7 @@ class _Linear(torch.nn.Module):
     def forward(self, x, act=False):
         if self.bias is None:
             return _DenseFn.apply(x, self.weight, 1.0 if act else False)          # SiLU in the GEMM epilogue
-        return _LinearBiasFn.apply(x, self.weight, self.bias, act)
+        return dense.linear(x, self.weight, self.bias, act)
 
 
 class GaussianSmearing(torch.nn.Module):
@@ -687,7 +688,7 @@ class eSCN(torch.nn.Module):
         P = self.num_sphere_samples
         x_pt = _RowFn.apply(x, self.sphharm_weights[0], 0, P, nf, Cc, False, None, None, G.N).view(-1, Cc)      # einsum('abc,pb->apc') (escn.py:399-407)
         mean = torch.full((P, 1), 1.0 / P, device=x.device)
-        node_energy = _MatmulFn.apply(self.energy_block(x_pt).view(G.N, P), mean)                     # [N, 1]
+        node_energy = dense.Matmul.apply(self.energy_block(x_pt).view(G.N, P), mean)                  # [N, 1]
         energy = _SegSumFn.apply(node_energy, G.mol_ptr, G.atom_mol, G.B).squeeze(1) * 0.001          # escn.py:411-414
         # Force head (escn.py:437-457): a nearly constant scalar field times the unit vectors of the 128 sphere points -- the sum cancels to ~1e-3 of its terms,
         # so this ONE reduction is carried in float64 (a [N,128] x [128,3] product: no cost); the f32 sum's own rounding was the largest contribution to the

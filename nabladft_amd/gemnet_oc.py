@@ -22,14 +22,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _f32, _new, _st
+from .dense import Matmul
 from .painn import build_neighbor_list
-from .qhnet import _MatmulFn, _f32
 
 _INV_SQRT2 = 1.0 / math.sqrt(2.0)
-
-
-def _st():
-    return _lib.stream_ptr()
 
 
 def _set(n, ptr, src, dst, geom):
@@ -146,10 +143,6 @@ def build_graphs(pos, batch, z, cutoff, cutoff_qint, cutoff_aeaint, cutoff_aint,
 # ============================================================================================================================================
 GEMM_BYTES = [None]      # bench hook: compulsory HBM bytes of the same products (operands read once, result written once; weights 2 B in the bf16 mode)
 GEMM_FLOPS = [None]      # bench hook: set GEMM_FLOPS[0] = 0.0 to accumulate 2*M*N*K of every dense product of the forward pass (backward = 2x that)
-
-
-def _new(*shape, like):
-    return torch.empty(*shape, device=like.device, dtype=torch.float32)
 
 
 _SSILU = 1.0 / 0.6       # ScaledSiLU (layers/base_layers.py:61-71)
@@ -493,17 +486,30 @@ def _segsum_raw(rows, order, ptr, n, Cc):
 
 
 class _SegSumFn(torch.autograd.Function):
-    """out[n] = sum of the CONTIGUOUS rows [ptr[n], ptr[n+1]); ``owner[row]`` = n for the adjoint."""
+    """out[n] = sum of the CONTIGUOUS rows [ptr[n], ptr[n+1]); ``owner[row]`` = n for the adjoint.  Differentiable any number of times: the adjoint of the sum
+    is a gather (``_SegGatherFn``) whose adjoint is the sum again."""
 
     @staticmethod
     def forward(ctx, rows, ptr, owner, n):
         rows = _f32(rows)
-        ctx.owner = owner
+        ctx.meta = (ptr, owner)
         return _segsum_raw(rows, None, ptr, n, rows.shape[1])
 
     @staticmethod
     def backward(ctx, g):
-        return _gather_raw(_f32(g), ctx.owner, None, ctx.owner.numel()), None, None, None
+        return _SegGatherFn.apply(g, *ctx.meta), None, None, None
+
+
+class _SegGatherFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, ptr, owner):
+        ctx.meta = (ptr, owner)
+        return _gather_raw(_f32(g), owner, None, owner.numel())
+
+    @staticmethod
+    def backward(ctx, a):
+        ptr, owner = ctx.meta
+        return _SegSumFn.apply(a, ptr, owner, ptr.numel() - 1), None, None
 
 
 class _TripletFn(torch.autograd.Function):
@@ -871,7 +877,7 @@ class BasisEmbedding(torch.nn.Module):
     def forward(self, rad):
         if self.num_spherical is None:
             return _DenseFn.apply(rad, self.weight, False)                       # rad @ W^T
-        return _MatmulFn.apply(rad, self.weight.reshape(self.weight.shape[0], -1))
+        return Matmul.apply(rad, self.weight.reshape(self.weight.shape[0], -1))
 
 
 class EfficientInteractionBilinear(torch.nn.Module):

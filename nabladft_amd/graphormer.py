@@ -10,7 +10,7 @@ leaves unmasked values of padded rows there); ``forward_ragged`` returns ``(ener
 What runs where
   * pair featuriser (distances, unit vectors, Gaussian basis, its per-atom sum) forward and backward, the head-major bias layout, attention with the shared
     additive bias forward and backward, the rotational force head, exact GELU, the E -> 1 energy projection: csrc/graphormer.hip;
-  * every nn.Linear: the GEMM launchers (qhnet._LinearBiasFn); nn.LayerNorm: equiformer_v2._LayerNormFn; the atom embedding and the molecule sum:
+  * every nn.Linear: the GEMM launchers (dense.Linear); nn.LayerNorm: equiformer_v2._LayerNormFn; the atom embedding and the molecule sum:
     escn._EmbeddingFn / gemnet_oc._SegSumFn.
   * The attention bias is transposed once per forward into the head-major buffer all blocks x layers encoder applications and the force head read; its adjoint
     is accumulated IN PLACE by their backward kernels and transposed back once (``_BiasLayoutFn``).
@@ -24,12 +24,12 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
+from . import _lib, dense
+from ._lib import _f32, _new, _st
 from .equiformer_v2 import _LayerNormFn
 from .escn import _EmbeddingFn, _inverse_lists
-from .gemnet_oc import _SegSumFn, _new, _st
+from .gemnet_oc import _SegSumFn
 from .lightning import _HAVE_PL, _Task
-from .qhnet import _LinearBiasFn, _f32
 
 ATOM_TYPES = 64
 EDGE_TYPES = ATOM_TYPES * ATOM_TYPES
@@ -275,7 +275,7 @@ class _RowDotFn(torch.autograd.Function):
 
 
 def _linear(mod, x):
-    return _LinearBiasFn.apply(x, mod.weight, mod.bias, False)
+    return dense.linear(x, mod.weight, mod.bias, False)
 
 
 def _layer_norm(mod, x):
@@ -345,8 +345,8 @@ class NodeTaskHead(nn.Module):
         self.force_mask_p = FORCE_HEAD_DROPOUT            # tests set 0.0 to force an all-keep mask
 
     def forward(self, x, plan, bias, unit):
-        qkv = _LinearBiasFn.apply(x, torch.cat([self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]),
-                                  torch.cat([self.q_proj.bias, self.k_proj.bias, self.v_proj.bias]), False)
+        qkv = dense.linear(x, torch.cat([self.q_proj.weight, self.k_proj.weight, self.v_proj.weight]),
+                           torch.cat([self.q_proj.bias, self.k_proj.bias, self.v_proj.bias]), False)
         W3 = torch.cat([self.force_proj1.weight, self.force_proj2.weight, self.force_proj3.weight])
         b3 = torch.cat([self.force_proj1.bias, self.force_proj2.bias, self.force_proj3.bias])
         mask, scale = keep_mask(plan, self.num_heads, self.force_mask_p) if self.training and self.force_mask_p > 0.0 else (None, 1.0)

@@ -16,7 +16,8 @@ from typing import Dict, Optional, Union
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, dense
+from ._lib import _f32
 
 
 class _WorkspaceToken:
@@ -171,33 +172,20 @@ class _EnergyBackbone(torch.autograd.Function):
 
 
 class _LinearFn(torch.autograd.Function):
-    """y = x @ W^T (+ b) through the engine's fp32 MFMA GEMMs."""
+    """y = x @ W^T (+ b) through the engine's fp32 MFMA GEMMs; the bias gradient is torch's column sum."""
 
     @staticmethod
     def forward(ctx, x, W, b):
-        lib = _lib.load()
-        x, W = x.to(torch.float32).contiguous(), W.to(torch.float32).contiguous()
-        M, K = x.shape
-        N = W.shape[0]
-        y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _lib.check(lib.nq_linear_forward(_lib.ptr(x), _lib.ptr(W), _lib.ptr(None if b is None else b.to(torch.float32).contiguous()), _lib.ptr(y), None, M, N, K,
-                                         _lib.stream_ptr()))
+        x, W = _f32(x), _f32(W)
         ctx.save_for_backward(x, W)
         ctx.has_bias = b is not None
-        return y
+        return dense.forward(x, W, None if b is None else _f32(b))[0]
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         x, W = ctx.saved_tensors
-        g = g.to(torch.float32).contiguous()
-        M, K = x.shape
-        N = W.shape[0]
-        gx, gW = torch.empty_like(x), torch.empty_like(W)
-        _lib.check(lib.nq_linear_input_grad(_lib.ptr(g), _lib.ptr(W), _lib.ptr(gx), M, N, K, 0, _lib.stream_ptr()))
-        scr = torch.empty(int(lib.nq_weight_grad_scratch_floats(M, N, K)) + 64, device=x.device, dtype=torch.float32)
-        _lib.check(lib.nq_linear_weight_grad(_lib.ptr(g), _lib.ptr(x), _lib.ptr(gW), M, N, K, _lib.ptr(scr), _lib.stream_ptr()))
-        return gx, gW, (g.sum(0) if ctx.has_bias else None)
+        g = _f32(g)
+        return dense.input_grad(g, W), dense.weight_grad(g, x)[0], (g.sum(0) if ctx.has_bias else None)
 
 
 class _ScaledSiluFn(torch.autograd.Function):

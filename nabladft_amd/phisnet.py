@@ -17,10 +17,10 @@ import os
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, dense
 import ctypes as C
 
-from .so3 import PackedList, PairMixing, SelfMixing, _LinearFn, _pack, _require_gpu, _unpack
+from .so3 import PackedList, PairMixing, SelfMixing, _pack, _require_gpu, _unpack
 
 
 class PairIndex:
@@ -268,7 +268,7 @@ def _linear(x, lin: nn.Linear):
     if lin.in_features == 1:
         y = x * lin.weight.view(*(1,) * len(lead), -1)
     else:
-        y = _LinearFn.apply(x.reshape(-1, lin.in_features), lin.weight).view(*lead, lin.out_features)
+        y = dense.linear(x.reshape(-1, lin.in_features), lin.weight).view(*lead, lin.out_features)
     return y if lin.bias is None else y + lin.bias
 
 

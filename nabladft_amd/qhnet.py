@@ -31,11 +31,13 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, cg
+from . import _lib, cg, dense
+from ._lib import _f32
+from .dense import Matmul as _MatmulFn          # x W, W [in, out]: FullyConnectedNet's product under the name its host-side test replaces
 from .hamiltonian import BlockAssembler, full_pair_index, transpose_index
 from .painn import build_neighbor_list
 from .phisnet import _SphLinearFn
-from .so3 import ExponentialBernsteinRadialBasisFunctions, _LinearFn, _MixFn
+from .so3 import ExponentialBernsteinRadialBasisFunctions, _MixFn
 
 LMAX = 4
 NCOMP = (LMAX + 1) ** 2
@@ -107,76 +109,6 @@ class _Graphs:
 
 
 # ---- autograd functions over the C ABI ---------------------------------------------------------------------------------------------------------
-def _f32(t):
-    return t.to(torch.float32).contiguous()
-
-
-class _MatmulFn(torch.autograd.Function):
-    """y = x @ W, W [in, out] (e3nn's FullyConnectedNet layout) on the fp32 MFMA GEMMs."""
-
-    @staticmethod
-    def forward(ctx, x, W):
-        lib = _lib.load()
-        x, W = _f32(x), _f32(W)
-        M, K = x.shape
-        N = W.shape[1]
-        y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _lib.check(lib.nq_linear_input_grad(_lib.ptr(x), _lib.ptr(W), _lib.ptr(y), M, K, N, 0, _lib.stream_ptr()))
-        ctx.save_for_backward(x, W)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
-        x, W = ctx.saved_tensors
-        g = _f32(g)
-        M, K = x.shape
-        N = W.shape[1]
-        gx = torch.empty_like(x)
-        _lib.check(lib.nq_linear_forward(_lib.ptr(g), _lib.ptr(W), None, _lib.ptr(gx), None, M, K, N, _lib.stream_ptr()))
-        gW = torch.empty_like(W)
-        scr = torch.empty(int(lib.nq_weight_grad_scratch_floats(M, K, N)) + 64, device=x.device, dtype=torch.float32)
-        _lib.check(lib.nq_linear_weight_grad(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gW), M, K, N, _lib.ptr(scr), _lib.stream_ptr()))
-        return gx, gW
-
-
-class _LinearBiasFn(torch.autograd.Function):
-    """torch.nn.Linear (+ optional SiLU) through nq_linear_forward's fused bias / SiLU epilogue."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, silu):
-        lib = _lib.load()
-        x, W, b = _f32(x), _f32(W), _f32(b)
-        M, K = x.shape
-        N = W.shape[0]
-        pre = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        post = torch.empty_like(pre) if silu else None
-        _lib.check(lib.nq_linear_forward(_lib.ptr(x), _lib.ptr(W), _lib.ptr(b), _lib.ptr(pre), _lib.ptr(post), M, N, K, _lib.stream_ptr()))
-        ctx.save_for_backward(x, W, pre if silu else x.new_zeros(0))
-        ctx.silu = silu
-        return post if silu else pre
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
-        x, W, pre = ctx.saved_tensors
-        g = _f32(g)
-        M, K = x.shape
-        N = W.shape[0]
-        if ctx.silu:
-            gp = torch.empty_like(g)
-            _lib.check(lib.nq_qh_act(_lib.ptr(pre), _lib.ptr(g), 0, 1.0, g.numel(), _lib.ptr(gp), _lib.stream_ptr()))
-            g = gp
-        gx = torch.empty_like(x)
-        _lib.check(lib.nq_linear_input_grad(_lib.ptr(g), _lib.ptr(W), _lib.ptr(gx), M, N, K, 0, _lib.stream_ptr()))
-        gW = torch.empty_like(W)
-        gb = torch.empty(N, device=g.device, dtype=torch.float32)
-        scr = torch.empty(int(lib.nq_weight_grad_scratch_floats(M, N, K)) + 64, device=x.device, dtype=torch.float32)
-        # weight and bias gradient in one launch: the column sums of g are taken from the operand registers of the contraction (fixed order)
-        _lib.check(lib.nq_linear_weight_grad_bias(_lib.ptr(g), _lib.ptr(x), _lib.ptr(gW), _lib.ptr(gb), M, N, K, _lib.ptr(scr), _lib.stream_ptr()))
-        return gx, gW, gb, None
-
-
 class _ActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kind, cst):
@@ -343,17 +275,9 @@ class _PairMixGenFn(torch.autograd.Function):
                                              _lib.ptr(g), R, Cc, K, _lib.ptr(g1), _lib.ptr(g2), _lib.ptr(gw1), _lib.ptr(gw2), _lib.stream_ptr()))
         gx = torch.empty_like(x)
         _lib.check(lib.nq_qh_pair_reduce(_lib.ptr(g1), _lib.ptr(g2), None, _lib.ptr(csr.row_ptr), _lib.ptr(csr.rev), N, NCOMP * Cc, _lib.ptr(gx), _lib.stream_ptr()))
-        # the generators' own adjoints: w1 = h1 @ W1 (as _MatmulFn), w2 = h2 @ W2^T + b2 (as _LinearBiasFn)
-        gh1 = torch.empty_like(h1)
-        _lib.check(lib.nq_linear_forward(_lib.ptr(gw1), _lib.ptr(W1), None, _lib.ptr(gh1), None, R, K, ncol, _lib.stream_ptr()))
-        gW1 = torch.empty_like(W1)
-        scr = torch.empty(int(max(lib.nq_weight_grad_scratch_floats(R, K, ncol), lib.nq_weight_grad_scratch_floats(R, ncol, K))) + 64, device=x.device, dtype=torch.float32)
-        _lib.check(lib.nq_linear_weight_grad(_lib.ptr(h1), _lib.ptr(gw1), _lib.ptr(gW1), R, K, ncol, _lib.ptr(scr), _lib.stream_ptr()))
-        gh2 = torch.empty_like(h2)
-        _lib.check(lib.nq_linear_input_grad(_lib.ptr(gw2), _lib.ptr(W2), _lib.ptr(gh2), R, ncol, K, 0, _lib.stream_ptr()))
-        gW2 = torch.empty_like(W2)
-        gb2 = torch.empty(ncol, device=x.device, dtype=torch.float32)
-        _lib.check(lib.nq_linear_weight_grad_bias(_lib.ptr(gw2), _lib.ptr(h2), _lib.ptr(gW2), _lib.ptr(gb2), R, ncol, K, _lib.ptr(scr), _lib.stream_ptr()))
+        # the generators' own adjoints: w1 = h1 @ W1 (as dense.Matmul), w2 = h2 @ W2^T + b2 (as dense.Linear)
+        gh1, gW1 = dense.forward(gw1, W1)[0], dense.weight_grad(h1, gw1)[0]
+        gh2, (gW2, gb2) = dense.input_grad(gw2, W2), dense.weight_grad(gw2, h2, True)
         return gx, gh1, gW1, gh2, gW2, gb2, None
 
 
@@ -573,8 +497,8 @@ class FullyConnectedNet(nn.Module):
 
 def _mlp(seq: nn.Sequential, x):
     """nn.Sequential(Linear, SiLU, Linear) on the MFMA GEMMs."""
-    h = _LinearBiasFn.apply(x, seq[0].weight, seq[0].bias, True)
-    return _LinearBiasFn.apply(h, seq[2].weight, seq[2].bias, False)
+    h = dense.linear(x, seq[0].weight, seq[0].bias, True)
+    return dense.linear(h, seq[2].weight, seq[2].bias, False)
 
 
 class NormGate(nn.Module):
@@ -688,7 +612,7 @@ class PairNetLayer(nn.Module):
         xn = self.linear_node_pair_n(self.norm_gate_pre(node_attr))
         if PAIR_GENERATOR_FUSION and self.c % 16 == 0 and self.fc_node_pair.hs[1] == self.fc[0].out_features and self.fc[0].out_features in (32, 64, 128):
             h1, W1 = self.fc_node_pair.hidden_and_weight(g.full_edge_attr, self._pc)
-            h2 = _LinearBiasFn.apply(s0, self.fc[0].weight, self.fc[0].bias, True)
+            h2 = dense.linear(s0, self.fc[0].weight, self.fc[0].bias, True)
             node_pair = _PairMixGenFn.apply(xn, h1, W1, h2, self.fc[2].weight, self.fc[2].bias, g.full)
         else:
             w1 = self.fc_node_pair(g.full_edge_attr, self._pc)
@@ -878,11 +802,11 @@ class QHNet(nn.Module):
         """seq(cat([node_attr[dst], node_attr[src]])) (qhnet.py:226-232) with the first Linear applied per atom before the gather."""
         W0 = seq[0].weight
         c = self.hs
-        a = _LinearFn.apply(node_attr, W0[:, :c].contiguous())
-        b = _LinearFn.apply(node_attr, W0[:, c:].contiguous())
+        a = dense.linear(node_attr, W0[:, :c].contiguous())
+        b = dense.linear(node_attr, W0[:, c:].contiguous())
         pre = _PairGatherAddFn.apply(a, b + seq[0].bias, csr)
         h = _ActFn.apply(pre, 0, 1.0)
-        return _LinearBiasFn.apply(h, seq[2].weight, seq[2].bias, False)
+        return dense.linear(h, seq[2].weight, seq[2].bias, False)
 
     def build_final_matrix(self, data, diagonal_matrix, non_diagonal_matrix):
         return self._asm.build_final_matrix(data, diagonal_matrix, non_diagonal_matrix)

@@ -14,37 +14,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, cg
-
-
-class _LinearFn(torch.autograd.Function):
-    """y = x @ W^T through the engine's fp32 MFMA GEMMs (nq_linear_*)."""
-
-    @staticmethod
-    def forward(ctx, x, W):
-        lib = _lib.load()
-        x = x.to(torch.float32).contiguous()
-        W = W.to(torch.float32).contiguous()
-        M, K = x.shape
-        N = W.shape[0]
-        y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        _lib.check(lib.nq_linear_forward(_lib.ptr(x), _lib.ptr(W), None, _lib.ptr(y), None, M, N, K, _lib.stream_ptr()))
-        ctx.save_for_backward(x, W)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
-        x, W = ctx.saved_tensors
-        g = g.to(torch.float32).contiguous()
-        M, K = x.shape
-        N = W.shape[0]
-        gx = torch.empty_like(x)
-        _lib.check(lib.nq_linear_input_grad(_lib.ptr(g), _lib.ptr(W), _lib.ptr(gx), M, N, K, 0, _lib.stream_ptr()))
-        scr = torch.empty(int(lib.nq_weight_grad_scratch_floats(M, N, K)) + 64, device=x.device, dtype=torch.float32)
-        gW = torch.empty_like(W)
-        _lib.check(lib.nq_linear_weight_grad(_lib.ptr(g), _lib.ptr(x), _lib.ptr(gW), M, N, K, _lib.ptr(scr), _lib.stream_ptr()))
-        return gx, gW
+from . import _lib, cg, dense
 
 
 class _MixFn(torch.autograd.Function):
@@ -234,7 +204,7 @@ class PairMixing(nn.Module):
         rows = x1.shape[0]
         rbf2 = rbf.expand(*lead, 1, self.num_basis_functions).reshape(rows, self.num_basis_functions)
         W = torch.cat([self.coeff(*p).weight * s for p, s in zip(self._paths, self._sign)], dim=0)       # [n_paths * F, K], CG sign convention folded in
-        coeff = _LinearFn.apply(rbf2, W).view(rows, len(self._paths), F)
+        coeff = dense.linear(rbf2, W).view(rows, len(self._paths), F)
         y = _MixFn.apply(x1, x2, coeff, None, (self.order_in1, self.order_in2, self.order_out, self._pidx, True, 0, False))
         return _unpack(y, self.order_out, lead, F)
 

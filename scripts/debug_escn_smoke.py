@@ -3,7 +3,8 @@ import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from nabladft_amd.escn import eSCN, _RowFn, _MatmulFn
+from nabladft_amd.dense import Matmul
+from nabladft_amd.escn import eSCN, _RowFn
 from nabladft_amd.synth import gen_conformers
 from oracle import escn_ref as R
 from oracle.escn_params import make_state
@@ -47,7 +48,7 @@ print("forces            : hip", rel(F, F64), " oracle32", rel(F32, F64))
 # the last contraction alone, from the float64 f: float32 GEMM vs float32 torch
 f64 = p64["f"]
 sp = P["sphere_points"]
-Fg = _MatmulFn.apply(f64.float().to(dev), (sp.float() / Pn).contiguous().to(dev))
+Fg = Matmul.apply(f64.float().to(dev), (sp.float() / Pn).contiguous().to(dev))
 Ft = (f64.float().unsqueeze(-1) * sp.float().view(1, Pn, 3)).sum(1) / Pn
 print("last contraction from exact f: hip gemm", rel(Fg, F64), " torch32", rel(Ft, F64))
 for i, lay in enumerate(layers):

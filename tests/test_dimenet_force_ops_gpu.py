@@ -185,7 +185,7 @@ def _wrapper(name, fn_dev, fn_ref, inputs, tangent_of, tangents, gs, adjoint_of)
 
 @pytest.mark.parametrize("bias,silu", [(True, True), (True, False), (False, True), (False, False)])
 def test_linear_wrapper_double_backward(bias, silu):
-    from nabladft_amd.dimenetplusplus import _linear
+    from nabladft_amd.dense import linear2 as _linear
     E = O.graph()["E"]
     x, W, b, gy, a_gx = rnd(90, E, 6), rnd(91, 8, 6), rnd(92, 8), rnd(93, E, 8), rnd(94, E, 6)
     act = FR.silu if silu else (lambda z: z)
@@ -212,7 +212,8 @@ def test_gate_gated_sum_and_embedding_wrappers_double_backward(H):
 
 
 def test_geometry_basis_triplet_and_molecule_sum_wrappers_double_backward():
-    from nabladft_amd.dimenetplusplus import _BasisFn, _GeomFn, _MolSumFn, _TripletFn
+    from nabladft_amd.dimenetplusplus import _BasisFn, _GeomFn, _TripletFn
+    from nabladft_amd.gemnet_oc import _SegSumFn
     g = O.graph()
     E, N = g["E"], g["N"]
     plan = _plan(g)
@@ -232,7 +233,7 @@ def test_geometry_basis_triplet_and_molecule_sum_wrappers_double_backward():
     ptr = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=DEV)
     owner = torch.tensor(np.repeat(np.arange(5), sizes), dtype=torch.int32, device=DEV)
     own64 = owner.cpu().long()
-    _wrapper("molecule sum", lambda rows, s: _MolSumFn.apply(rows * s, ptr, owner, 5), lambda rows, s: torch.zeros(5, 50, dtype=torch.float64).index_add_(0, own64, rows * s),
+    _wrapper("molecule sum", lambda rows, s: _SegSumFn.apply(rows * s, ptr, owner, 5), lambda rows, s: torch.zeros(5, 50, dtype=torch.float64).index_add_(0, own64, rows * s),
              (rnd(120, N, 50), rnd(121, N, 50)), (0,), (rnd(122, N, 50),), rnd(123, 5, 50), (1,))
 
 
