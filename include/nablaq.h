@@ -604,6 +604,18 @@ int nq_linear_input_grad_bf16(const float* G, const void* WbT, float* C, int32_t
 /* gW[N][K] = G[rows][N]^T X[rows][K] on the bf16 MFMA (operands transposed into bf16 copies inside `scratch`, split over the rows, fixed-order reduction). */
 size_t nq_weight_grad_bf16_scratch_bytes(int64_t rows, int32_t N, int32_t K);
 int nq_linear_weight_grad_bf16(const float* G, const float* X, float* gW, int64_t rows, int32_t N, int32_t K, void* scratch, void* stream);
+/* bf16-in-memory flavours of the same kernels (gemnet_oc.set_gemm_precision("bf16_act"); ScaledSiLU / ResidualLayer of layers/base_layers.py:11-97): tensors
+ * that only another of these products or the SiLU reverse reads stay bf16 in HBM.  All roundings are the round-to-nearest-even conversion of the staging path,
+ * so every result is bitwise the fp32-in-memory kernel's result rounded (outputs) or the fp32 kernel's result on the widened operand (inputs).
+ * nq_linear_forward_bf16_out (layers/base_layers.py:11-97): as nq_linear_forward_bf16 with C_act given; A is fp32 [M][K], or bf16 [M][K] if a_bf16; the
+ *   pre-activation is written as bf16 [M][N]; `act` = alpha * resid + beta * silu(pre) (from the unrounded accumulator) is written as bf16 if act_bf16, else
+ *   fp32.  A and Wb 16-byte aligned; the outputs need only their natural alignment, N is arbitrary.
+ * nq_linear_weight_grad_bf16_x (layers/base_layers.py:11-97): nq_linear_weight_grad_bf16 with X given as bf16 [rows][K]; same scratch.
+ * nq_gn_ssilu_backward_bf16 (layers/base_layers.py:11-97): nq_gn_ssilu_backward with z given as bf16 [n]. */
+int nq_linear_forward_bf16_out(const void* A, int32_t a_bf16, const void* Wb, void* pre_bf16, void* act, int32_t act_bf16, const float* resid, float alpha,
+                               float beta, int32_t M, int32_t N, int32_t K, void* stream);
+int nq_linear_weight_grad_bf16_x(const float* G, const void* X_bf16, float* gW, int64_t rows, int32_t N, int32_t K, void* scratch, void* stream);
+int nq_gn_ssilu_backward_bf16(const void* z_bf16, const float* g, float scale, int64_t n, float* out, void* stream);
 /* C[M,K] (+)= G[M,N] W[N,K] */
 int nq_linear_input_grad(const float* G, const float* W, float* C, int32_t M, int32_t N, int32_t K, int32_t accumulate, void* stream);
 /* Input gradient with a fused epilogue on C[M,K] = G W: mode 1: C = beta * (G W) * silu'(aux) (adjoint of the activation below), mode 2: C = alpha * aux + G W

@@ -154,6 +154,9 @@ SYMBOLS = {
     "nq_linear_input_grad_bf16_epi": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _F, _F, _I32, _P]),
     "nq_weight_grad_bf16_scratch_bytes": (_SZ, [_I64, _I32, _I32]),
     "nq_linear_weight_grad_bf16": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P]),
+    "nq_linear_forward_bf16_out": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _F, _F, _I32, _I32, _I32, _P]),
+    "nq_linear_weight_grad_bf16_x": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P, _P]),
+    "nq_gn_ssilu_backward_bf16": (C.c_int, [_P, _P, _F, _I64, _P, _P]),
     "nq_gn_embed_grad": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "nq_es_graph_count": (C.c_int, [_P, _P, _P, _I32, _D, _I32, _P, _P, C.POINTER(C.c_int32), _P]),
     "nq_es_graph_fill": (C.c_int, [_P, _P, _P, _I32, _D, _I32, _P, _P, _P, _P, _P]),

@@ -5,6 +5,9 @@
 // 128x128x32 tiles, 4 wavefronts (2x2, each 64x64 = 2x2 MFMA tiles), register prefetch of the next k-tile under the MFMAs, two LDS buffers, one barrier
 // per k-tile.  LDS rows are K-contiguous with a 16-byte pad (80-byte stride): every lane fetches its 8 consecutive k of one row with a single ds_read_b128.
 // Epilogues as in gemm.hip: store / accumulate / ScaledSiLU + residual (gemnet_oc/layers/base_layers.py:11-97).
+// bf16-in-memory flavours ("bf16_act" mode of gemnet_oc.py): the A operand may already be bf16 in HBM, and the ScaledSiLU epilogue may store the
+// pre-activation (and the activation) as bf16, rounded with the same (__bf16) conversion the staging path uses -- so a tensor that only ever feeds another
+// of these products, or the SiLU reverse, never exists in fp32.
 #include "common.h"
 
 typedef __bf16 hb8 __attribute__((ext_vector_type(8)));
@@ -20,13 +23,41 @@ struct HbArgs {
   const float* A; const __bf16* B; float* C; float* C2; const float* resid;
   float ea, eb;
   int M, N, K, lda, ldb, ldc;
-  const __bf16* Ab;          // A_BF16: A already packed in bf16 (weight gradient: transposed activations)
+  const __bf16* Ab;          // A_BF16: A already in bf16, row-major [M][lda] (weight gradient: transposed activations; forward: a bf16 activation)
   int k_split; long part_stride;   // split over the contraction: blockIdx.z covers [z * k_split, (z + 1) * k_split), output slab z
+  __bf16* Cb; __bf16* C2b;   // OUT > 0: bf16 pre-activation; OUT == 2: bf16 activation (OUT == 1 writes the fp32 activation to C2)
 };
 enum { HB_STORE = 0, HB_ACC = 1, HB_SILU_RES = 2, HB_DSILU = 3, HB_RES = 4 };
 
-template <int EPI, bool A_BF16 = false>
-__global__ __launch_bounds__(256) void k_gemm_bf16_nt(HbArgs p) {
+// ScaledSiLU + residual epilogue of one 32x32 accumulator tile with a bf16 pre-activation and a bf16 (OUT == 2) or fp32 (OUT == 1) activation.  The C/D
+// layout gives a lane ONE column and 16 rows, so the bf16 stores are 2 bytes per lane (64 contiguous bytes per row and instruction), at any N and any
+// alignment.  Measured on the MI355X, 20 468 and 81 872 rows x 512 x 512, all at three workgroups per CU (profiles/gemnet_bf16_act.txt):
+//   2-byte stores as here                                             28.8 / 42.1 / 29.8 us and 131 / 221 / 152-160 us (first / second product / Dense)
+//   lane pairs swap one row through DPP, 4-byte stores (N even)       30.2 / 43.0 / 29.8 us and 135-141 / 252 / 163-166 us
+//   lane quads transpose a 4x4 block through DPP, 8-byte stores       39.9 / 51.6 / 38.7 us and 157-161 / 274 / 164-166 us
+// -- the exchanges and selects cost more issue slots than the wider stores save.  What did matter is occupancy: without the register cap below the same
+// three variants took 38.4 / 40.4 / 56.4 us for the first product (188-204 VGPRs: two workgroups per CU instead of three).
+template <int OUT>
+__device__ __forceinline__ void hb_tile_store_bf16(const HbArgs& p, const hf16& acc, int row0, int col) {
+  if (col >= p.N) return;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = row0 + (r & 3) + 8 * (r >> 2);
+    if (row >= p.M) continue;
+    const long off = (long)row * p.ldc + col;
+    const float v = acc[r];
+    const float a = p.resid ? p.ea * p.resid[off] + p.eb * nq_silu_fast(v) : p.eb * nq_silu_fast(v);
+    p.Cb[off] = (__bf16)v;
+    if (OUT == 2) p.C2b[off] = (__bf16)a;
+    else p.C2[off] = a;
+  }
+}
+
+// The bf16-output flavours are capped at 168 VGPRs (three workgroups of four wavefronts per CU, like the fp32-output ones); the attribute leaves the other
+// instantiations as they were (their ISA is the same with and without it)
+#define HB_OUT_WAVES 3
+template <int EPI, bool A_BF16 = false, int OUT = 0>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OUT != 0 ? HB_OUT_WAVES : 1))) void k_gemm_bf16_nt(HbArgs p) {
   __shared__ __attribute__((aligned(16))) __bf16 sA[2][HB_BM * HB_LD];
   __shared__ __attribute__((aligned(16))) __bf16 sB[2][HB_BN * HB_LD];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
@@ -103,6 +134,13 @@ __global__ __launch_bounds__(256) void k_gemm_bf16_nt(HbArgs p) {
     buf ^= 1;
   }
   // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+  if (OUT != 0) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) hb_tile_store_bf16<OUT>(p, acc[i][j], m0 + wm * 64 + i * 32 + 4 * lk, n0 + wn * 64 + j * 32 + lr);
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -141,15 +179,16 @@ __global__ void k_bf16_pack(const float* __restrict__ W, int N, int K, __bf16* _
   }
 }
 
-// x [M][C] fp32 -> xT [C][Mp] bf16, zero for m >= M (Mp = M rounded up to the k-tile).  64 (rows) x 32 (columns) tiles through LDS: reads are 128-byte row
+// x [M][C] fp32 (or already bf16: the conversions are then exact) -> xT [C][Mp] bf16, zero for m >= M (Mp = M rounded up to the k-tile).  64 (rows) x 32 (columns) tiles through LDS: reads are 128-byte row
 // segments, writes are 128-byte segments of 64 consecutive m
-__global__ __launch_bounds__(256) void k_transpose_bf16(const float* __restrict__ x, long M, int C, long Mp, __bf16* __restrict__ xT) {
+template <typename T>
+__global__ __launch_bounds__(256) void k_transpose_bf16(const T* __restrict__ x, long M, int C, long Mp, __bf16* __restrict__ xT) {
   __shared__ float tile[64][33];
   const long m0 = (long)blockIdx.x * 64;
   const int c0 = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int r = ty; r < 64; r += 8) {
     const long m = m0 + r; const int c = c0 + tx;
-    tile[r][tx] = (m < M && c < C) ? x[m * C + c] : 0.f;
+    tile[r][tx] = (m < M && c < C) ? (float)x[m * C + c] : 0.f;
   }
   __syncthreads();
   const int mx = (threadIdx.x & 31) * 2, cy = threadIdx.x >> 5;   // each thread writes two consecutive m (4 bytes)
@@ -200,6 +239,27 @@ static int hb_launch(hipStream_t st, const float* A, const void* B, float* C, fl
 
 extern "C" {
 
+int nq_linear_forward_bf16_out(const void* A, int32_t a_bf16, const void* Wb, void* pre_bf16, void* act, int32_t act_bf16, const float* resid, float alpha,
+                               float beta, int32_t M, int32_t N, int32_t K, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_bf16_nt_%s%s:[n=%d,k=%d]", a_bf16 ? "b" : "f", act_bf16 ? "bb" : "bf", N, K); else nm__[0] = 0;
+  NQ_PROF(st, nm__);
+  NQ_PROF_FLOPS(2.0 * M * N * K);
+  if (!A || !Wb || !pre_bf16 || !act) return nq_fail(NQ_ERR_ARG, "null argument");
+  if (M <= 0) return NQ_OK;
+  if (K % HB_BK != 0 || N <= 0) return nq_fail(NQ_ERR_ARG, "bf16 gemm: K = %d must be a multiple of %d", K, HB_BK);
+  if ((uintptr_t)A % 16 != 0 || (uintptr_t)Wb % 16 != 0) return nq_fail(NQ_ERR_ARG, "bf16 gemm: operands must be 16-byte aligned");
+  HbArgs p{a_bf16 ? nullptr : (const float*)A, (const __bf16*)Wb, nullptr, act_bf16 ? nullptr : (float*)act, resid, alpha, beta, M, N, K, K, K, N,
+           a_bf16 ? (const __bf16*)A : nullptr, K, 0, (__bf16*)pre_bf16, act_bf16 ? (__bf16*)act : nullptr};      // one z-slice over the whole contraction
+  dim3 grid(nq_cdiv(M, HB_BM), nq_cdiv(N, HB_BN), 1);
+  if (a_bf16 && act_bf16) hipLaunchKernelGGL((k_gemm_bf16_nt<HB_SILU_RES, true, 2>), grid, dim3(256), 0, st, p);
+  else if (a_bf16) hipLaunchKernelGGL((k_gemm_bf16_nt<HB_SILU_RES, true, 1>), grid, dim3(256), 0, st, p);
+  else if (act_bf16) hipLaunchKernelGGL((k_gemm_bf16_nt<HB_SILU_RES, false, 2>), grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((k_gemm_bf16_nt<HB_SILU_RES, false, 1>), grid, dim3(256), 0, st, p);
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+
 int nq_bf16_pack(const float* W, int32_t N, int32_t K, void* Wb, void* WbT, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "bf16_pack");
@@ -233,8 +293,7 @@ size_t nq_weight_grad_bf16_scratch_bytes(int64_t rows, int32_t N, int32_t K) {
   hb_wgrad_plan(rows, N, K, &Mp, &ns, &ks);
   return (size_t)(N + K) * Mp * 2 + (size_t)ns * N * K * 4 + 512;
 }
-int nq_linear_weight_grad_bf16(const float* G, const float* X, float* gW, int64_t rows, int32_t N, int32_t K, void* scratch, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+static int hb_weight_grad(const float* G, const void* X, bool x_bf16, float* gW, int64_t rows, int32_t N, int32_t K, void* scratch, hipStream_t st) {
   char nm__[48]; if (nq_profile_on) snprintf(nm__, sizeof nm__, "gemm_bf16_tn:[%dx%d]", N, K); else nm__[0] = 0;
   NQ_PROF(st, nm__);
   NQ_PROF_FLOPS(2.0 * rows * N * K);
@@ -244,8 +303,9 @@ int nq_linear_weight_grad_bf16(const float* G, const float* X, float* gW, int64_
   __bf16* GT = (__bf16*)scratch;
   __bf16* XT = GT + (size_t)N * Mp;
   float* part = (float*)(((uintptr_t)(XT + (size_t)K * Mp) + 255) & ~(uintptr_t)255);
-  hipLaunchKernelGGL(k_transpose_bf16, dim3((unsigned)((Mp + 63) / 64), nq_cdiv(N, 32)), dim3(256), 0, st, G, (long)rows, N, Mp, GT);
-  hipLaunchKernelGGL(k_transpose_bf16, dim3((unsigned)((Mp + 63) / 64), nq_cdiv(K, 32)), dim3(256), 0, st, X, (long)rows, K, Mp, XT);
+  hipLaunchKernelGGL(k_transpose_bf16<float>, dim3((unsigned)((Mp + 63) / 64), nq_cdiv(N, 32)), dim3(256), 0, st, G, (long)rows, N, Mp, GT);
+  if (x_bf16) hipLaunchKernelGGL(k_transpose_bf16<__bf16>, dim3((unsigned)((Mp + 63) / 64), nq_cdiv(K, 32)), dim3(256), 0, st, (const __bf16*)X, (long)rows, K, Mp, XT);
+  else hipLaunchKernelGGL(k_transpose_bf16<float>, dim3((unsigned)((Mp + 63) / 64), nq_cdiv(K, 32)), dim3(256), 0, st, (const float*)X, (long)rows, K, Mp, XT);
   NQ_LAUNCH_CHECK();
   HbArgs p{nullptr, XT, ns > 1 ? part : gW, nullptr, nullptr, 0.f, 0.f, N, K, (int)Mp, (int)Mp, (int)Mp, K, GT, ks, (long)N * K};
   dim3 grid(nq_cdiv(N, HB_BM), nq_cdiv(K, HB_BN), ns);
@@ -257,6 +317,12 @@ int nq_linear_weight_grad_bf16(const float* G, const float* X, float* gW, int64_
     NQ_LAUNCH_CHECK();
   }
   return NQ_OK;
+}
+int nq_linear_weight_grad_bf16(const float* G, const float* X, float* gW, int64_t rows, int32_t N, int32_t K, void* scratch, void* stream) {
+  return hb_weight_grad(G, X, false, gW, rows, N, K, scratch, (hipStream_t)stream);
+}
+int nq_linear_weight_grad_bf16_x(const float* G, const void* X_bf16, float* gW, int64_t rows, int32_t N, int32_t K, void* scratch, void* stream) {
+  return hb_weight_grad(G, X_bf16, true, gW, rows, N, K, scratch, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -591,6 +591,23 @@ __global__ void k_gn_ssilu_bwd(const float* __restrict__ z, const float* __restr
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) out[t] = scale * g[t] * nq_dsilu(z[t]);
 }
+// The same with the pre-activation z stored as bf16 (the "bf16_act" mode of gemnet_oc.py keeps it that way in HBM): four elements per thread, 8-byte loads of
+// z and 16-byte loads / stores of g / out where the pointers allow it (vec), the tail and the unaligned case one element at a time.
+__global__ void k_gn_ssilu_bwd_bf16(const __bf16* __restrict__ z, const float* __restrict__ g, float scale, long n, float* __restrict__ out, int vec) {
+  const long t = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (t >= n) return;
+  if (vec && t + 4 <= n) {
+    typedef __bf16 zb4 __attribute__((ext_vector_type(4)));
+    const zb4 zv = *reinterpret_cast<const zb4*>(z + t);
+    const float4 gv = *reinterpret_cast<const float4*>(g + t);
+    float4 o;
+    o.x = scale * gv.x * nq_dsilu((float)zv[0]); o.y = scale * gv.y * nq_dsilu((float)zv[1]);
+    o.z = scale * gv.z * nq_dsilu((float)zv[2]); o.w = scale * gv.w * nq_dsilu((float)zv[3]);
+    *reinterpret_cast<float4*>(out + t) = o;
+    return;
+  }
+  for (long i = t; i < n && i < t + 4; ++i) out[i] = scale * g[i] * nq_dsilu((float)z[i]);
+}
 // dW[t][c] = sum_{n : z[n] == t + 1} g[n][c]  (adjoint of Embedding(z - 1), embedding_block.py:39-53), fixed order
 __global__ void k_gn_embed_grad(const int* __restrict__ z, const float* __restrict__ g, int N, int T, int C, float* __restrict__ dW) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -844,6 +861,16 @@ int nq_gn_ssilu_backward(const float* z, const float* g, float scale, int64_t n,
   NQ_PROF(st, "gn_ssilu_bwd");
   if (n <= 0) return NQ_OK;
   hipLaunchKernelGGL(k_gn_ssilu_bwd, GN_GRID(n), z, g, scale / 0.6f, (long)n, out);
+  NQ_LAUNCH_CHECK();
+  return NQ_OK;
+}
+int nq_gn_ssilu_backward_bf16(const void* z_bf16, const float* g, float scale, int64_t n, float* out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  NQ_PROF(st, "gn_ssilu_bwd_bf16");
+  if (n <= 0) return NQ_OK;
+  if (!z_bf16 || !g || !out) return nq_fail(NQ_ERR_ARG, "null argument");
+  const int vec = (uintptr_t)z_bf16 % 8 == 0 && ((uintptr_t)g | (uintptr_t)out) % 16 == 0;
+  hipLaunchKernelGGL(k_gn_ssilu_bwd_bf16, GN_GRID((n + 3) / 4), (const __bf16*)z_bf16, g, scale / 0.6f, (long)n, out, vec);
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }

@@ -141,7 +141,8 @@ def build_graphs(pos, batch, z, cutoff, cutoff_qint, cutoff_aeaint, cutoff_aint,
 # ============================================================================================================================================
 # autograd wrappers of the C entry points (no CPU path)
 # ============================================================================================================================================
-GEMM_BYTES = [None]      # bench hook: compulsory HBM bytes of the same products (operands read once, result written once; weights 2 B in the bf16 mode)
+GEMM_BYTES = [None]      # bench hook: compulsory HBM bytes of the same products (operands read once, result written once; weights 2 B in the bf16 modes, and
+#                          2 B for every activation the "bf16_act" mode keeps in bf16)
 GEMM_FLOPS = [None]      # bench hook: set GEMM_FLOPS[0] = 0.0 to accumulate 2*M*N*K of every dense product of the forward pass (backward = 2x that)
 
 
@@ -160,10 +161,19 @@ def weights_epoch_advance() -> None:
 
 
 def set_gemm_precision(mode: str) -> None:
-    """"f32" (default: exact-f32 MFMA, the parity-tested path) or "bf16": the forward and input-gradient products of the Dense layers run on bf16 MFMA with
-    fp32 accumulation (operands rounded to bf16, weights packed once per parameter version); weight gradients, all sums over edges / triplets /
-    quadruplets and the optimizer stay fp32 -- the mode BASELINE.json names for config/model/gemnet-oc.yaml."""
-    if mode not in ("f32", "bf16"):
+    """"f32" (default: exact-f32 MFMA, the parity-tested path), "bf16" or "bf16_act".
+
+    "bf16": the forward and input-gradient products of the Dense layers run on bf16 MFMA with fp32 accumulation (operands rounded to bf16 while they are
+    staged, weights packed once per model forward); the weight gradients of 2048 rows and more too; all sums over edges / triplets / quadruplets and the
+    optimizer stay fp32.  Every activation is still fp32 in memory.
+
+    "bf16_act": "bf16", and in addition the tensors that never leave the Dense stack are bf16 IN MEMORY wherever the layer runs on the bf16 kernels (at least
+    256 rows, contraction a multiple of 32): the pre-activation an activated Dense saves for its backward pass, and pre1 / a1 / pre2 of a ResidualLayer (a1
+    is read by the second product as a bf16 operand; no fp32 copy of any of the three exists).  Outputs of the nodes, the residual stream, all sums and all
+    weight gradients stay fp32.  The forward pass is bit-identical to "bf16" (every consumer of a1 rounded it to bf16 anyway, and the activation is computed
+    from the unrounded accumulator); the backward pass sees pre-activations rounded to bf16 and, for the weight gradient that reads a1, bf16 operands at
+    every size the mode covers -- the mode BASELINE.json names for config/model/gemnet-oc.yaml ("bf16 with fp32 scatter-accumulate")."""
+    if mode not in ("f32", "bf16", "bf16_act"):
         raise ValueError(mode)
     _PRECISION[0] = mode
     _PACKED.clear()
@@ -185,7 +195,12 @@ def _packed(W):
 
 
 def _use_bf16(M, contract):
-    return _PRECISION[0] == "bf16" and contract % 32 == 0 and M >= 256
+    return _PRECISION[0] != "f32" and contract % 32 == 0 and M >= 256
+
+
+def _use_bf16_act(M, *contracts):
+    """"bf16_act" only: a tensor is bf16 in memory if every kernel that reads or writes it has a bf16 flavour, i.e. every product around it qualifies."""
+    return _PRECISION[0] == "bf16_act" and all(_use_bf16(M, c) for c in contracts)
 
 
 def _gemm_act(x, W, resid, alpha, beta):
@@ -206,9 +221,26 @@ def _gemm_act(x, W, resid, alpha, beta):
     return pre, out
 
 
+def _gemm_act_bf16(x, W, resid, alpha, beta, act_bf16):
+    """_gemm_act of the "bf16_act" mode: pre is bf16, out is bf16 (act_bf16) or fp32; x is fp32 or bf16.  The caller has checked _use_bf16_act."""
+    M, K = x.shape
+    N = W.shape[0]
+    x_bf16 = x.dtype == torch.bfloat16
+    pre = torch.empty(M, N, device=x.device, dtype=torch.bfloat16)
+    out = torch.empty(M, N, device=x.device, dtype=torch.bfloat16 if act_bf16 else torch.float32)
+    _lib.check(_lib.load().nq_linear_forward_bf16_out(_lib.ptr(x), int(x_bf16), _lib.ptr(_packed(W)[0]), _lib.ptr(pre), _lib.ptr(out), int(act_bf16),
+                                                      None if resid is None else _lib.ptr(resid), float(alpha), float(beta), M, N, K, _st()))
+    if GEMM_FLOPS[0] is not None:
+        GEMM_FLOPS[0] += 2.0 * M * N * K
+    if GEMM_BYTES[0] is not None:
+        GEMM_BYTES[0] += (2.0 if x_bf16 else 4.0) * M * K + (2.0 + (2.0 if act_bf16 else 4.0)) * M * N + 2.0 * N * K      # x read, pre and out written, W read
+    return pre, out
+
+
 def _ssilu_bwd(pre, g, scale):
     out = torch.empty_like(g)
-    _lib.check(_lib.load().nq_gn_ssilu_backward(_lib.ptr(pre), _lib.ptr(g), float(scale), g.numel(), _lib.ptr(out), _st()))
+    fn = _lib.load().nq_gn_ssilu_backward_bf16 if pre.dtype == torch.bfloat16 else _lib.load().nq_gn_ssilu_backward
+    _lib.check(fn(_lib.ptr(pre), _lib.ptr(g), float(scale), g.numel(), _lib.ptr(out), _st()))
     return out
 
 
@@ -228,7 +260,7 @@ def _dgrad_epi(g, W, aux, alpha, beta, mode):
     """mode 1: beta * (g W) * silu'(aux); mode 2: alpha * aux + g W -- in the GEMM epilogue."""
     M, N = g.shape
     K = W.shape[1]
-    if M > 0 and _use_bf16(M, N):
+    if (M > 0 and _use_bf16(M, N)) or aux.dtype == torch.bfloat16:     # a bf16 aux (saved by a "bf16_act" forward) has no fused flavour in any mode
         # measured: on the short bf16 kernel the 64 scattered aux loads per lane of the fused epilogue cost more (73 us vs 37 us per 20 k x 512 x 512 product)
         # than the separate streaming pass they replace -- keep the passes separate there
         raw = _dgrad(g, W)
@@ -244,7 +276,11 @@ def _wgrad(g, x):
     M, N = g.shape
     K = x.shape[1]
     gW = _new(N, K, like=g)
-    if _PRECISION[0] == "bf16" and M >= 2048:
+    if x.dtype == torch.bfloat16:            # "bf16_act": a bf16 activation is never widened in memory, at any size
+        scr = torch.empty(int(lib.nq_weight_grad_bf16_scratch_bytes(M, N, K)), device=g.device, dtype=torch.uint8)
+        _lib.check(lib.nq_linear_weight_grad_bf16_x(_lib.ptr(g), _lib.ptr(x), _lib.ptr(gW), M, N, K, _lib.ptr(scr), _st()))
+        return gW
+    if _PRECISION[0] != "f32" and M >= 2048:
         scr = torch.empty(int(lib.nq_weight_grad_bf16_scratch_bytes(M, N, K)), device=g.device, dtype=torch.uint8)
         _lib.check(lib.nq_linear_weight_grad_bf16(_lib.ptr(g), _lib.ptr(x), _lib.ptr(gW), M, N, K, _lib.ptr(scr), _st()))
         return gW
@@ -262,7 +298,10 @@ class _DenseFn(torch.autograd.Function):
         x, W = _f32(x), _f32(W)
         ctx.act = _SSILU if act is True else float(act)
         if ctx.act:
-            pre, y = _gemm_act(x, W, None, 0.0, ctx.act)
+            if _use_bf16_act(x.shape[0], x.shape[1]):
+                pre, y = _gemm_act_bf16(x, W, None, 0.0, ctx.act, False)        # pre only feeds the SiLU reverse: bf16; y has arbitrary consumers: fp32
+            else:
+                pre, y = _gemm_act(x, W, None, 0.0, ctx.act)
             ctx.save_for_backward(x, W, pre)
             return y
         M, K = x.shape
@@ -310,7 +349,7 @@ def _fwd_f32(x, W, aux=None, alpha=0.0):
 
 def fused_pairs_available():
     """The two-term products below exist for the f32-accurate engines; the bf16 mode keeps the composed form (its operands are packed per launch)."""
-    return _PRECISION[0] != "bf16"
+    return _PRECISION[0] == "f32"
 
 
 class _SO2PairFn(torch.autograd.Function):
@@ -381,8 +420,12 @@ class _ResidualFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W1, W2):
         x, W1, W2 = _f32(x), _f32(W1), _f32(W2)
-        pre1, a1 = _gemm_act(x, W1, None, 0.0, _SSILU)
-        pre2, out = _gemm_act(a1, W2, x, _INV_SQRT2, _INV_SQRT2 * _SSILU)
+        if _use_bf16_act(x.shape[0], W1.shape[1], W2.shape[1]):
+            pre1, a1 = _gemm_act_bf16(x, W1, None, 0.0, _SSILU, True)                              # pre1, a1, pre2 never leave this node: bf16
+            pre2, out = _gemm_act_bf16(a1, W2, x, _INV_SQRT2, _INV_SQRT2 * _SSILU, False)
+        else:
+            pre1, a1 = _gemm_act(x, W1, None, 0.0, _SSILU)
+            pre2, out = _gemm_act(a1, W2, x, _INV_SQRT2, _INV_SQRT2 * _SSILU)
         ctx.save_for_backward(x, W1, W2, pre1, a1, pre2)
         return out
 

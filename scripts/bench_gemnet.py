@@ -3,7 +3,8 @@ neighbour caps 30 / 20 / 8, quadruplet + atom-edge + edge-atom + atom-atom inter
 loss = L1(E) + 100 * L2(F), gradient-norm clip 10.0, config/gemnet-oc.yaml: batch_size 8) training-step timing on one MI355X in fp32: graphs -> forward -> loss -> backward -> AdamW, on synthetic drug-like
 conformers already resident in HBM.  ``run()`` is what ``bench.py --model gemnet`` calls.
 
-    python scripts/bench_gemnet.py [--molecules 16] [--steps 10] [--warmup 3] [--kernels] [--cpu-baseline]
+    python scripts/bench_gemnet.py [--molecules 16] [--steps 10] [--warmup 3] [--kernels] [--cpu-baseline] [--precision f32|bf16|bf16_act]
+    python scripts/bench_gemnet.py --alternate bf16,bf16_act --rounds 3 --kernels      # A/B in one process: the modes take turns, spread next to the difference
 """
 import argparse
 import json
@@ -90,11 +91,13 @@ def run(molecules=16, steps=10, warmup=3, kernels=True, device=None, seed=1, wor
     for i in range(warmup):
         step(i)
     sync()
+    torch.cuda.reset_peak_memory_stats(dev)
     t0 = time.perf_counter()
     for i in range(steps):
         loss = step(i)
     sync()
     dt = time.perf_counter() - t0
+    peak_mib = torch.cuda.max_memory_allocated(dev) / 2.0 ** 20
     G = net.get_graphs_and_indices(batches[0])
     out = {"workload": "GemNet-OC (config/model/gemnet-oc.yaml: 4 blocks, atom 256 / edge 512, 128 rbf, 7 spherical, 12 A cutoffs, caps 30/20/8, all four extra "
                        "interactions, direct coupled forces) train step: graphs, forward, L1(E) + 100 L2(F), backward, clip 10.0, AdamW(amsgrad); synthetic ~42-atom conformers",
@@ -102,7 +105,7 @@ def run(molecules=16, steps=10, warmup=3, kernels=True, device=None, seed=1, wor
            "load_balance": {"cost_model": "gemnet_oc", "this_run_predicted_spread": getattr(batches[0], "cost_spread", 0.0),
                             "predicted_spread_8_ranks_10_to_90_atoms_by_conformers_per_rank": nqdist.spread_table("gemnet_oc")}, "atoms": G.N,
            "edges": {"a2a": G.Ea2a, "main": G.Em, "a2ee2a": G.Ea, "qint": G.Eq, "qint_x_main_rows": G.Tin}, "parameters": net.num_params, "_dt": dt,
-           "final_loss": float(loss.detach()), "dtype": precision, "data": "synthetic",
+           "final_loss": float(loss.detach()), "dtype": precision, "peak_memory_MiB": peak_mib, "data": "synthetic",
            "parity": "pinned to the reference GemNetOC classes run on CPU (tests/golden/gemnet_*.npz); torch_scatter / torch_sparse / torch_cluster restated"}
     if kernels:
         gemnet_oc.GEMM_FLOPS[0] = 0.0
@@ -122,20 +125,21 @@ def run(molecules=16, steps=10, warmup=3, kernels=True, device=None, seed=1, wor
         ks = sorted(((k, v[0] / steps, v[1] // steps) for k, v in prof.items()), key=lambda x: -x[1])
         out["device_ms_per_step_nq_kernels"] = tot
         out["kernel_ms_per_step"] = {k: [round(ms, 4), int(n)] for k, ms, n in ks[:24]}
+        out["dense_kernel_ms_per_step"] = {k: [round(ms, 4), int(n)] for k, ms, n in ks if k.startswith(("gemm_bf16_", "gn_ssilu_bwd"))}      # all of them, not the top 24
         gemm_ms = sum(v[0] for k, v in prof.items() if v[2] > 0 or k.startswith("bf16")) / steps      # dense products (+ the per-forward bf16 weight re-pack)
         out["gemm_classes_TFLOPs"] = {k: round(v[2] / max(v[0], 1e-9) / 1e9, 1) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0]) if v[2] > 0}
         out["gemm_bf16_ms_per_step"] = sum(ms for k, ms, _ in ks if "bf16" in k)
         fl = sum(v[2] for v in prof.values()) / steps                      # exact: every dense launcher records its 2 M N K (nq_profile_read2)
         by = 3.0 * fwd_bytes                                                # each of the three products reads two operands and writes one of the same sizes
         ach = fl / (max(gemm_ms, 1e-9) * 1e-3) / 1e12
-        if precision == "bf16":
-            # the Dense products run on bf16 MFMA (2.5 PFLOP/s dense) with fp32 activations in HBM: at these shapes (K = 256 ... 512) the compulsory bytes take
+        if precision != "f32":
+            # the Dense products run on bf16 MFMA (2.5 PFLOP/s dense) with fp32 activations in HBM ("bf16_act": the Dense-only ones in bf16): at these shapes (K = 256 ... 512) the compulsory bytes take
             # longer at 8 TB/s than the flops at the bf16 peak, so HBM is the roof that binds; both times are reported
             t_mfma, t_hbm = fl / (MFMA_BF16_PEAK_TFLOPS * 1e12) * 1e3, by / (HBM_PEAK_GBS * 1e9) * 1e3
             bound = "hbm" if t_hbm >= t_mfma else "mfma"
             achieved = by / (max(gemm_ms, 1e-9) * 1e-3) / 1e9 if bound == "hbm" else ach
             peak = HBM_PEAK_GBS if bound == "hbm" else MFMA_BF16_PEAK_TFLOPS
-            out["roofline"] = {"kernel": "k_gemm_bf16 (Dense layers: bf16 MFMA, fp32 accumulate; fp32 activations in HBM)", "bound": bound, "achieved": achieved, "peak": peak,
+            out["roofline"] = {"kernel": "k_gemm_bf16 (Dense layers: bf16 MFMA, fp32 accumulate; " + ("Dense-only activations bf16 in HBM)" if precision == "bf16_act" else "fp32 activations in HBM)"), "bound": bound, "achieved": achieved, "peak": peak,
                                "unit": "GB/s" if bound == "hbm" else "TFLOP/s", "frac": achieved / peak, "traffic": None, "gemm_ms_per_step": gemm_ms,
                                "flops_per_step": fl, "algorithmic_bytes_per_step": by, "mfma_bf16_bound_ms": t_mfma, "hbm_bound_ms": t_hbm,
                                "achieved_TFLOPs": ach, "frac_of_bf16_mfma_peak": ach / MFMA_BF16_PEAK_TFLOPS}
@@ -186,6 +190,28 @@ def cpu_baseline(seconds_budget=25.0, conformers=1):   # (this oracle needs ~6 s
                       f"built by Python loops, as part of the step), median of {n} steps after one warm-up step, torch {torch.__version__} CPU fp32, no optimizer step"}
 
 
+def alternate(modes, rounds, molecules, steps, warmup, kernels):
+    """A/B of GEMM precisions in one process: the modes take turns `rounds` times; per mode the step times of all rounds, their median and spread, peak memory,
+    and (with kernels) the bf16 product and SiLU-reverse rows of the last round."""
+    runs = {m: [] for m in modes}
+    for _ in range(rounds):
+        for m in modes:
+            runs[m].append(run(molecules, steps, warmup, kernels, precision=m))
+    out = {"molecules_per_step": molecules, "steps": steps, "rounds": rounds, "modes": {}}
+    for m, rs in runs.items():
+        ms = sorted(r["ms_per_step"] for r in rs)
+        ent = {"ms_per_step_rounds": [round(r["ms_per_step"], 3) for r in rs], "ms_per_step_median": ms[len(ms) // 2], "ms_per_step_spread": ms[-1] - ms[0],
+               "peak_memory_MiB": max(r["peak_memory_MiB"] for r in rs)}
+        if kernels:
+            ent["device_ms_per_step_nq_kernels_rounds"] = [round(r["device_ms_per_step_nq_kernels"], 3) for r in rs]
+            ent["dense_kernel_ms_per_step"] = rs[-1]["dense_kernel_ms_per_step"]
+        out["modes"][m] = ent
+    a, b = modes[0], modes[-1]
+    out["difference_ms_per_step"] = {"of": f"{b} - {a} (medians)", "value": out["modes"][b]["ms_per_step_median"] - out["modes"][a]["ms_per_step_median"],
+                                     "spread": max(out["modes"][a]["ms_per_step_spread"], out["modes"][b]["ms_per_step_spread"])}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--molecules", type=int, default=16)
@@ -193,8 +219,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--cpu-baseline", action="store_true")
-    ap.add_argument("--precision", choices=["f32", "bf16"], default="f32")
+    ap.add_argument("--precision", choices=["f32", "bf16", "bf16_act"], default="f32")
+    ap.add_argument("--alternate", default=None, help="comma-separated precisions that take turns in this process, e.g. bf16,bf16_act")
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
+    if a.alternate:
+        print(json.dumps(alternate(a.alternate.split(","), a.rounds, a.molecules, a.steps, a.warmup, a.kernels)))
+        return
     out = run(a.molecules, a.steps, a.warmup, a.kernels, precision=a.precision)
     if a.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
