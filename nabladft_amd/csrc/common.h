@@ -236,10 +236,11 @@ int nq_molgw_schedule(hipStream_t, const NqGraphView&, const int* dst, const flo
 int nq_molgw_geometry(hipStream_t, const NqGraphView&, const float* RW, const float* TD, const float* TR, const int* sched_ints, float* recs);
 int nq_gwr_mol(hipStream_t, const NqGraphView&, int F, int R, int max_mol_atoms, const float* XH, const float* V, const float* TXH, const float* TV,
                const float* GX, const float* GV, const float* GTX, const float* GTV, const int* sched_ints, const float* recs, float* part, float* gWr,
-               float* gbr, bool accumulate = false, bool layer0 = false);
+               float* gbr, bool accumulate, bool layer0, hipStream_t reduce_st, hipEvent_t part_ready);   // reduce_st != the first stream: k_gwr_mol_reduce runs there, behind part_ready
 int nq_msg_rev(hipStream_t, const MsgRevArgs&, bool dual);
 int nq_geom_tan(hipStream_t, const NqGraphView&, const int* dst, const float* pos_dot, float* TD, float* TR);
-int nq_geom_rev(hipStream_t, const NqGraphView&, const float4* GEDGE, int nwaves, float* forces);
+int nq_force_planes(int F, int N, bool fused);   // GEDGE planes the force-adjoint message kernel of such a launch writes (one per channel slice)
+int nq_geom_rev(hipStream_t, const NqGraphView&, const float4* GEDGE, int nwaves, float* forces, bool serial);
 
 // the whole update block of one layer's forward sweep as one kernel (updfuse.hip; hidden_channels = 128): weight fragments once per forward call, then one launch
 bool nq_gemm_exact_f32_requested();   // the exact-f32 engine was asked for (NQ_GEMM_F32=1 / nq_set_gemm_variant(32)): kernels that only exist on the bf16 matrix pipe step aside

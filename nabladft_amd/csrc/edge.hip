@@ -1160,7 +1160,35 @@ __device__ __forceinline__ void edge_gw(const NqGraphView& g, const float4* __re
   z = a.x * r2 + (a.w - dot * r2) * inv;
 }
 
-__global__ void k_geom_rev(NqGraphView g, const float4* __restrict__ GEDGE, int nwaves, float* __restrict__ forces) {
+// One GEOM_REV_LANES-lane group per atom: the lanes evaluate gw(sp) - gw(rev[sp]) of up to GEOM_REV_LANES slots of the row at once (two dependent gathers each,
+// all in flight together); longer rows go in chunks.  The differences are then added in CSR order into ONE accumulator that every lane of the group carries
+// (a lane-by-lane walk), which is the association of k_geom_rev_serial: the forces are bit-identical to it.
+#define GEOM_REV_LANES 32
+#define GEOM_REV_THREADS 256
+__global__ __launch_bounds__(GEOM_REV_THREADS) void k_geom_rev(NqGraphView g, const float4* __restrict__ GEDGE, int nwaves, float* __restrict__ forces) {
+  const int lane = threadIdx.x & (GEOM_REV_LANES - 1);
+  const int n = blockIdx.x * (GEOM_REV_THREADS / GEOM_REV_LANES) + threadIdx.x / GEOM_REV_LANES;
+  if (n >= g.N) return;   // whole groups leave together
+  const int s0 = g.row_ptr[n], s1 = g.row_ptr[n + 1];
+  float fx = 0.f, fy = 0.f, fz = 0.f;
+  for (int c0 = s0; c0 < s1; c0 += GEOM_REV_LANES) {
+    const int cnt = min(GEOM_REV_LANES, s1 - c0);   // uniform over the group
+    float dx = 0.f, dy = 0.f, dz = 0.f;
+    if (lane < cnt) {
+      const int sp = c0 + lane;
+      float ax, ay, az, bx, by, bz;
+      edge_gw(g, GEDGE, nwaves, sp, ax, ay, az);
+      edge_gw(g, GEDGE, nwaves, g.rev[sp], bx, by, bz);
+      dx = ax - bx; dy = ay - by; dz = az - bz;
+    }
+    for (int i = 0; i < cnt; ++i) {   // source lanes i < cnt of the own group: active in this iteration
+      fx += __shfl(dx, i, GEOM_REV_LANES); fy += __shfl(dy, i, GEOM_REV_LANES); fz += __shfl(dz, i, GEOM_REV_LANES);
+    }
+  }
+  if (lane == 0) { forces[3 * (long)n] = -fx; forces[3 * (long)n + 1] = -fy; forces[3 * (long)n + 2] = -fz; }
+}
+// the reference flavour (NQ_GEOM_REV_SERIAL=1): one thread per atom, a serial loop over the row
+__global__ void k_geom_rev_serial(NqGraphView g, const float4* __restrict__ GEDGE, int nwaves, float* __restrict__ forces) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= g.N) return;
   float fx = 0.f, fy = 0.f, fz = 0.f;
@@ -1234,9 +1262,10 @@ int nq_geom_tan(hipStream_t st, const NqGraphView& g, const int* dst, const floa
   return NQ_OK;
 }
 
-int nq_geom_rev(hipStream_t st, const NqGraphView& g, const float4* GEDGE, int nwaves, float* forces) {
+int nq_geom_rev(hipStream_t st, const NqGraphView& g, const float4* GEDGE, int nwaves, float* forces, bool serial) {
   NQ_PROF(st, "geom_rev");
-  hipLaunchKernelGGL(k_geom_rev, dim3(nq_cdiv(g.N, 128)), dim3(128), 0, st, g, GEDGE, nwaves, forces);
+  if (serial) hipLaunchKernelGGL(k_geom_rev_serial, dim3(nq_cdiv(g.N, 128)), dim3(128), 0, st, g, GEDGE, nwaves, forces);
+  else hipLaunchKernelGGL(k_geom_rev, dim3(nq_cdiv(g.N, GEOM_REV_THREADS / GEOM_REV_LANES)), dim3(GEOM_REV_THREADS), 0, st, g, GEDGE, nwaves, forces);
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }
@@ -1347,6 +1376,9 @@ int nq_msgf_fwd(hipStream_t st, const MsgArgs& q, const FilterArgs& fa, bool tan
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }
+
+// force adjoint (kind 2): the fused kernels add into one GEDGE plane per channel slice, the unfused k_msg_rev into one per 64 channels
+int nq_force_planes(int F, int N, bool fused) { return fused ? F / (64 * fused_ch(2, F, N)) : F / 64; }
 
 int nq_msgf_rev(hipStream_t st, const MsgRevArgs& q, const FilterArgs& fa, bool dual, bool pair_rows, bool layer0) {
   layer0 = layer0 && (!dual || (!pair_rows && q.lite));   // the pair-row and the full dual flavours have no layer-0 form: they run the general kernel

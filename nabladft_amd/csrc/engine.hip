@@ -194,6 +194,13 @@ struct StepPlan {
   // zeros, and its V2 input-gradient product contracts the first 2F columns of G_Y only (the last F are zeros).  Not for the seeded (direct-force) sweep, whose
   // head seeds a vector adjoint.  NQ_NO_TOPLAYER=1: the general code (A/B runs, tests).
   bool top_layer;
+  // Helper launches on the side stream (where the side stream is on at all: side_stream_init), one switch per group for A/B runs and tests:
+  //   side_fwd     forward call: the pair schedule, the six WrT transposes / update-weight pre-splits and the layer-0 zero fills    NQ_NO_SIDE_FWD=1
+  //   side_geom    backward call: the pair geometry records and the layer-0 tangent zero fills                                     NQ_NO_SIDE_GEOM=1
+  //   side_reduce  backward call: k_gwr_mol_reduce of every layer                                                                  NQ_NO_SIDE_REDUCE=1
+  bool side_fwd, side_geom, side_reduce;
+  // NQ_GEOM_REV_SERIAL=1: the one-thread-per-atom k_geom_rev (the reference flavour of the lane-group kernel; A/B runs, tests)
+  bool geom_rev_serial;
 };
 static StepPlan plan_step(const nq_painn_cfg* c, const nq_graph* g, bool want_forces) {
   auto env_on = [](const char* name) { const char* v = getenv(name); return v && v[0] == '1'; };
@@ -213,6 +220,8 @@ static StepPlan plan_step(const nq_painn_cfg* c, const nq_graph* g, bool want_fo
   p.fused_update = nq_updfuse_frag_floats(c->hidden_channels) > 0 && !env_on("NQ_NO_FUSED_UPDATE") && !nq_gemm_exact_f32_requested();
   p.layer0 = !env_on("NQ_NO_LAYER0");
   p.top_layer = !env_on("NQ_NO_TOPLAYER");
+  p.side_fwd = !env_on("NQ_NO_SIDE_FWD"); p.side_geom = !env_on("NQ_NO_SIDE_GEOM"); p.side_reduce = !env_on("NQ_NO_SIDE_REDUCE");
+  p.geom_rev_serial = env_on("NQ_GEOM_REV_SERIAL");
   return p;
 }
 // the layout of a workspace sized or inspected outside a step (nq_painn_workspace_bytes, nq_painn_ws_lookup): the plan such a step would make now
@@ -275,6 +284,71 @@ static int check_common(const nq_painn_cfg* cfg, const nq_graph* g, const void* 
   if (ws_bytes < W->total_floats * sizeof(float))
     return nq_fail(NQ_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", ws_bytes, W->total_floats * sizeof(float));
   return NQ_OK;
+}
+
+// ---- side stream for the weight gradients and the helper launches ----------------------------------------------------------------------------
+// Nothing downstream of the reverse sweep waits for dL/dW (split-K TN GEMMs, the k0-sorted rbf_proj gradient, bias column sums): only the
+// optimiser does.  They are issued on a second HIP stream and run under the critical path (input-gradient GEMMs, node kernels, message sweeps),
+// which leaves matrix-core and bandwidth gaps: the dual message kernel waits on gathers for half of its cycles.  Ordering is by events: a side
+// launch waits for its producer on the main stream; the main stream waits before it overwrites a buffer the side stream may still read.
+// The side stream and its event pool belong to one (device, main stream) pair (a process that drives two GPUs, or two streams from two threads, gets
+// one pair each); an early error return between fork() and join() still joins (destructor), so a stream capture is never left forked.
+// The same stream carries the small launches nothing in the chain waits for (plan_step: side_fwd, side_geom, side_reduce): the pair schedule, the transposed /
+// pre-split weights and the layer-0 zero fills of the forward call, the pair geometry records of the backward call, k_gwr_mol_reduce.  Their consumers on
+// the main stream wait on the event of what they read (mark / main_waits), never on a whole-stream join.
+struct SideStream {
+  hipStream_t main = nullptr, side = nullptr;
+  bool on = false;
+  std::vector<hipEvent_t>* pool = nullptr;
+  size_t used = 0;
+  bool forked = false, joined = false;
+  hipEvent_t last_read[8] = {};
+  SideStream() = default;
+  SideStream(const SideStream&) = delete;
+  SideStream& operator=(const SideStream&) = delete;
+  ~SideStream() { if (on && forked && !joined) join(); }
+  hipEvent_t next() {
+    if (used == pool->size()) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr; pool->push_back(e); }
+    return (*pool)[used++];
+  }
+  hipStream_t fork() {                       // the side stream sees everything issued on main so far
+    if (!on) return main;
+    hipEvent_t e = next();
+    (void)hipEventRecord(e, main); (void)hipStreamWaitEvent(side, e, 0);
+    forked = true; joined = false;
+    return side;
+  }
+  void read_by_side(int buf) { if (on) { hipEvent_t e = next(); (void)hipEventRecord(e, side); last_read[buf] = e; } }
+  void before_main_writes(int buf) { if (on && last_read[buf]) { (void)hipStreamWaitEvent(main, last_read[buf], 0); last_read[buf] = nullptr; } }
+  hipEvent_t mark() { if (!on) return nullptr; hipEvent_t e = next(); (void)hipEventRecord(e, side); return e; }   // everything issued on the side stream so far
+  void main_waits(hipEvent_t e) { if (on && e) (void)hipStreamWaitEvent(main, e, 0); }
+  void join() { if (on) { hipEvent_t e = next(); (void)hipEventRecord(e, side); (void)hipStreamWaitEvent(main, e, 0); joined = true; } }
+};
+enum { SB_GY = 0, SB_GQ, SB_GU, SB_GXH, SB_GH, SB_GPHI, SB_GBR, SB_GWPART };
+struct SidePool { hipStream_t side = nullptr; std::vector<hipEvent_t> events; };
+static std::mutex g_side_mu;
+static std::map<std::pair<int, hipStream_t>, SidePool*> g_side_pools;
+static void side_stream_init(SideStream& s, hipStream_t main, int n_atoms) {
+  s.main = main;
+  // Measured (profiles/r02_side_stream_ab.txt): at 2048 conformers / step 60.5 ms with the side stream vs 60.1 ms without; at 32 conformers (1.3 k atoms, the step is
+  // a chain of ~330 small dependent kernels) 4.40 vs 4.71 ms, at 256 conformers 11.57 vs 11.78 ms: the weight gradients leave the critical path.  Re-measured on
+  // the round-6 kernels (profiles/r06_helper_kernels_ab.txt, item 6): now a small gain at every size (2048 conformers 45.45 -> 45.1-45.2 ms, 512: 13.74 -> 13.14),
+  // but two streams sharing the chip make every per-kernel duration (HIP events and rocprofv3 alike) depend on what ran beside it, and the record's roofline
+  // is a per-kernel figure: above 16 k atoms the side stream is on unless the launch profiler is recording (the instrumented HIP-event pass stays single-stream;
+  // a rocprofv3 pass is taken with NQ_SIDE_STREAM=0); NQ_SIDE_STREAM=0 / 1 forces it.  Re-measured on this tree: profiles/reverse_passes_ab.txt.
+  const char* env = getenv("NQ_SIDE_STREAM");
+  const bool want = env && (env[0] == '0' || env[0] == '1') ? env[0] == '1' : (n_atoms <= 16384 || !nq_profile_on);
+  if (!want) return;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return;
+  std::lock_guard<std::mutex> lock(g_side_mu);
+  SidePool*& pool = g_side_pools[std::make_pair(dev, main)];
+  if (!pool) {
+    SidePool* p = new SidePool();
+    if (hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) != hipSuccess) { delete p; return; }
+    pool = p;
+  }
+  s.side = pool->side; s.pool = &pool->events; s.on = true;
 }
 
 // ================================================================================================
@@ -414,7 +488,8 @@ int nq_painn_ws_lookup(const nq_painn_cfg* cfg, int32_t N, int32_t E, int32_t B,
   else if (!strcmp(name, "e_atom")) { base = tangent ? W.te_atom : W.e_atom; rows = n; w = 1; dual = false; tangent = 0; }
   else if (!strcmp(name, "t_d")) { base = W.TD; rows = e; w = 1; dual = false; }
   else if (!strcmp(name, "t_r")) { base = W.TR; rows = e; w = 3; dual = false; }
-  else if (!strcmp(name, "gedge")) { base = W.GEDGE; rows = (F / 64) * e; w = 4; dual = false; }
+  else if (!strcmp(name, "gedge")) { base = W.GEDGE; rows = (F / 64) * e; w = 4; dual = false; }   // (the force sweep zeroes and fills nq_force_planes() of the F/64 planes)
+  else if (!strcmp(name, "gx")) { base = W.GX; rows = n; w = F; dual = false; }   // after a whole step (tests): the adjoint of x_in0, the operand of the embedding gradient
   else return nq_fail(NQ_ERR_ARG, "unknown workspace buffer '%s'", name);
 #undef LAYER_OK
   if (tangent && !dual) return nq_fail(NQ_ERR_ARG, "buffer '%s' has no tangent half", name);
@@ -443,10 +518,20 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
   // wavefronts the claim atomics are a visible part of each kernel (1.3 k atoms: dual sweep 57 -> 112 us), so small batches keep the static striding
   auto row_ctr = [&](int kind, int l) { return N >= 4096 ? rowctr0 + ((size_t)kind * L + l) * NQ_ROWCTR_INTS : (int*)nullptr; };
 
+  // Helper launches beside the sweeps: forked once after the window records, joined before the call returns (both exits), so the caller or a stream capture
+  // never sees a forked stream and the workspace is complete on `stream` as include/nablaq.h says.  Off: every launch below is on the main stream in the old order.
+  SideStream ss;
+  if (plan.side_fwd && W.fused && plan.gw_mode != GW_MIXED) side_stream_init(ss, st, N);   // mixed batches: everything stays on the main stream, as in the backward call
+  // layer-0 flavours: no kernel of this call reads the zeros of vec_in0 and of the layer-0 input tangents (the backward call's general flavours and the traces do)
+  const bool fills_aside = ss.on && plan.layer0;
+  hipEvent_t wrt_ready[64] = {};   // per layer: WrT (and the pre-split update weights) written by the side stream
+
   // embedding; zero vec_in0 and the tangent halves of layer-0 inputs (d x0 / d pos = 0)
   NQ_TRY(nq_embed(st, g.z, params + P.emb, N, F, ws + W.X[0]));
-  NQ_HIP(hipMemsetAsync(ws + W.X[0] + NF, 0, NF * sizeof(float), st));
-  NQ_HIP(hipMemsetAsync(ws + W.V[0], 0, 6 * NF * sizeof(float), st));
+  if (!fills_aside) {
+    NQ_HIP(hipMemsetAsync(ws + W.X[0] + NF, 0, NF * sizeof(float), st));
+    NQ_HIP(hipMemsetAsync(ws + W.V[0], 0, 6 * NF * sizeof(float), st));
+  }
   float* rho = ws + W.RHO2; float* drho = rho + (size_t)E * R;
   const bool lite_store = plan.lite;   // the force sweep below stores its per-layer adjoints for the second-order sweep (WsLayer::LG*)
   if (W.fused) {
@@ -454,7 +539,19 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
     nq_make_filter_args(&fa0, nullptr, nullptr, rbf_offsets, ws + W.RW, R, cfg->cutoff, cfg->envelope_exponent, cfg->rbf_coeff, cfg->filter_mode);
     NQ_TRY(nq_rbf_window(st, g.geom, E, fa0, ws + W.RW));
     int* const sched = reinterpret_cast<int*>(ws + W.SCHED);
-    if (plan.gw_mode != GW_PAIR_ROWS) NQ_TRY(nq_molgw_schedule(st, g, graph->dst, ws + W.RW, R, plan.gw_cap, sched, ws + W.GWREC));
+    hipStream_t sd = ss.fork();          // sd == st when the side stream is off
+    if (ss.on) {   // inputs: parameters only; each layer's message / fused-update launch waits on its own event
+      for (int l = 0; l < L; ++l) {
+        NQ_TRY(nq_transpose(sd, params + P.msg[l].Wr, 3 * F, R, ws + W.lay[l].WRT));
+        if (plan.fused_update) NQ_TRY(nq_updfuse_presplit(sd, params + P.upd[l].U, params + P.upd[l].V1, params + P.upd[l].V2, F, ws + W.lay[l].UFRAG));
+        wrt_ready[l] = ss.mark();
+      }
+      if (fills_aside) {
+        NQ_HIP(hipMemsetAsync(ws + W.X[0] + NF, 0, NF * sizeof(float), sd));
+        NQ_HIP(hipMemsetAsync(ws + W.V[0], 0, 6 * NF * sizeof(float), sd));
+      }
+    }
+    if (plan.gw_mode != GW_PAIR_ROWS) NQ_TRY(nq_molgw_schedule(sd, g, graph->dst, ws + W.RW, R, plan.gw_cap, sched, ws + W.GWREC));   // first reader: the backward call
     if (plan.gw_mode == GW_PAIR_ROWS) NQ_TRY(nq_k0_sort(st, ws + W.RW, E, R, reinterpret_cast<int*>(ws + W.ORDER), reinterpret_cast<int*>(ws + W.scratch), graph->dst, g.col));   // lower slots only
     else if (plan.gw_mode == GW_MIXED)   // lower slots of the molecules above the cap only; their number stays on the device (last spare int of the schedule block)
       NQ_TRY(nq_k0_sort(st, ws + W.RW, E, R, reinterpret_cast<int*>(ws + W.ORDER), reinterpret_cast<int*>(ws + W.scratch), graph->dst, g.col, g.mol_ptr, g.atom_mol,
@@ -472,7 +569,8 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
     m.XM = ws + y.XM; m.VM = ws + y.VM;
     if (W.fused) {
       FilterArgs fa;
-      NQ_TRY(nq_transpose(st, params + mp.Wr, 3 * F, R, ws + y.WRT));
+      if (ss.on) ss.main_waits(wrt_ready[l]);
+      else NQ_TRY(nq_transpose(st, params + mp.Wr, 3 * F, R, ws + y.WRT));
       nq_make_filter_args(&fa, ws + y.WRT, params + mp.br, rbf_offsets, ws + W.RW, R, cfg->cutoff, cfg->envelope_exponent, cfg->rbf_coeff, cfg->filter_mode);
       fa.row_ctr = row_ctr(0, l);
       NQ_TRY(nq_msgf_fwd(st, m, fa, false, plan.layer0 && l == 0));
@@ -485,7 +583,7 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
     u.N = N; u.F = F; u.XM = ws + y.XM; u.VM = ws + y.VM; u.U = ws + y.UU; u.Y = ws + y.Y; u.S = ws + y.S; u.CAT = ws + y.CAT;
     u.X1 = ws + W.X[l + 1]; u.V1 = ws + W.V[l + 1];
     if (plan.fused_update) {
-      NQ_TRY(nq_updfuse_presplit(st, params + up.U, params + up.V1, params + up.V2, F, ws + y.UFRAG));
+      if (!ss.on) NQ_TRY(nq_updfuse_presplit(st, params + up.U, params + up.V1, params + up.V2, F, ws + y.UFRAG));
       NQ_TRY(nq_upd_fused(st, u, ws + y.UFRAG, params + up.c1, params + up.c2, ws + y.ZQ, ws + y.Q));
       continue;
     }
@@ -500,7 +598,7 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
   r.N = N; r.H = H; r.ZO = ws + W.ZO; r.w2 = params + P.w2; r.o2 = params + P.o2; r.e_atom = ws + W.e_atom;
   NQ_TRY(nq_readout(st, r, 0));
   NQ_TRY(nq_mol_sum(st, ws + W.e_atom, g.mol_ptr, g.B, energy));
-  if (!forces) return NQ_OK;
+  if (!forces) { ss.join(); return NQ_OK; }
 
   // ---- force adjoint sweep: seeds dE_tot/de_i = 1 --------------------------------------------
   NQ_TRY(nq_atom_seeds(st, nullptr, g.atom_mol, N, ws + W.ge, nullptr));
@@ -511,7 +609,7 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
   NQ_TRY(nq_gemm_nn(st, ws + W.GZO, params + P.O1, gx_cur, N, H, F, H, F, F, 0, "O1"));
   float* gv_cur = lite_store ? ws + W.lay[L - 1].LGVA : ws + W.GVa; float* gv_oth = ws + W.GVb;
   if (lite_store || !plan.top_layer) NQ_HIP(hipMemsetAsync(gv_cur, 0, 3 * NF * sizeof(float), st));   // (top_layer: read by nobody in this sweep; the stored-adjoint layout keeps its zeros)
-  const int nwaves = F / 64;
+  const int nwaves = nq_force_planes(F, N, W.fused);   // the planes the message kernels below write (one per channel slice), not the F/64 the layout holds
   NQ_HIP(hipMemsetAsync(ws + W.GEDGE, 0, (size_t)nwaves * E * 4 * sizeof(float), st));
   for (int l = L - 1; l >= 0; --l) {
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
@@ -561,7 +659,8 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
       NQ_TRY(nq_gemm_nn(st, GH, params + mp.W1, gx_cur, N, F, F, F, F, F, 1, "W1"));
     }
   }
-  NQ_TRY(nq_geom_rev(st, g, reinterpret_cast<const float4*>(ws + W.GEDGE), nwaves, forces));
+  NQ_TRY(nq_geom_rev(st, g, reinterpret_cast<const float4*>(ws + W.GEDGE), nwaves, forces, plan.geom_rev_serial));
+  ss.join();
   return NQ_OK;
 }
 
@@ -569,66 +668,6 @@ int nq_painn_forward(const nq_painn_cfg* cfg, const float* params, const float* 
 // seeded = true: first-order reverse for the direct-force model (painn.py:130-133): no tangent sweep; the tangent halves of every
 // stacked buffer are zeroed so that the dual-reverse kernels reduce to the plain reverse, and the adjoints of the final node state
 // (from the PaiNNOutput head, evaluated by the caller) are added to the seeds.
-// ---- side stream for the weight gradients ---------------------------------------------------------------------------------------------------
-// Nothing downstream of the reverse sweep waits for dL/dW (split-K TN GEMMs, the k0-sorted rbf_proj gradient, bias column sums): only the
-// optimiser does.  They are issued on a second HIP stream and run under the critical path (input-gradient GEMMs, node kernels, message sweeps),
-// which leaves matrix-core and bandwidth gaps: the dual message kernel waits on gathers for half of its cycles.  Ordering is by events: a side
-// launch waits for its producer on the main stream; the main stream waits before it overwrites a buffer the side stream may still read.
-// The side stream and its event pool belong to one (device, main stream) pair (a process that drives two GPUs, or two streams from two threads, gets
-// one pair each); an early error return between fork() and join() still joins (destructor), so a stream capture is never left forked.
-struct SideStream {
-  hipStream_t main = nullptr, side = nullptr;
-  bool on = false;
-  std::vector<hipEvent_t>* pool = nullptr;
-  size_t used = 0;
-  bool forked = false, joined = false;
-  hipEvent_t last_read[8] = {};
-  SideStream() = default;
-  SideStream(const SideStream&) = delete;
-  SideStream& operator=(const SideStream&) = delete;
-  ~SideStream() { if (on && forked && !joined) join(); }
-  hipEvent_t next() {
-    if (used == pool->size()) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr; pool->push_back(e); }
-    return (*pool)[used++];
-  }
-  hipStream_t fork() {                       // the side stream sees everything issued on main so far
-    if (!on) return main;
-    hipEvent_t e = next();
-    (void)hipEventRecord(e, main); (void)hipStreamWaitEvent(side, e, 0);
-    forked = true; joined = false;
-    return side;
-  }
-  void read_by_side(int buf) { if (on) { hipEvent_t e = next(); (void)hipEventRecord(e, side); last_read[buf] = e; } }
-  void before_main_writes(int buf) { if (on && last_read[buf]) { (void)hipStreamWaitEvent(main, last_read[buf], 0); last_read[buf] = nullptr; } }
-  void join() { if (on) { hipEvent_t e = next(); (void)hipEventRecord(e, side); (void)hipStreamWaitEvent(main, e, 0); joined = true; } }
-};
-enum { SB_GY = 0, SB_GQ, SB_GU, SB_GXH, SB_GH, SB_GPHI, SB_GBR };
-struct SidePool { hipStream_t side = nullptr; std::vector<hipEvent_t> events; };
-static std::mutex g_side_mu;
-static std::map<std::pair<int, hipStream_t>, SidePool*> g_side_pools;
-static void side_stream_init(SideStream& s, hipStream_t main, int n_atoms) {
-  s.main = main;
-  // Measured (profiles/r02_side_stream_ab.txt): at 2048 conformers / step 60.5 ms with the side stream vs 60.1 ms without; at 32 conformers (1.3 k atoms, the step is
-  // a chain of ~330 small dependent kernels) 4.40 vs 4.71 ms, at 256 conformers 11.57 vs 11.78 ms: the weight gradients leave the critical path.  Re-measured on
-  // the round-6 kernels (profiles/r06_helper_kernels_ab.txt, item 6): now a small gain at every size (2048 conformers 45.45 -> 45.1-45.2 ms, 512: 13.74 -> 13.14),
-  // but two streams sharing the chip make every per-kernel duration (HIP events and rocprofv3 alike) depend on what ran beside it, and the record's roofline
-  // is a per-kernel figure: above 16 k atoms the side stream is on unless the launch profiler is recording (the instrumented HIP-event pass stays single-stream;
-  // a rocprofv3 pass is taken with NQ_SIDE_STREAM=0); NQ_SIDE_STREAM=0 / 1 forces it.  Re-measured on this tree: profiles/reverse_passes_ab.txt.
-  const char* env = getenv("NQ_SIDE_STREAM");
-  const bool want = env && (env[0] == '0' || env[0] == '1') ? env[0] == '1' : (n_atoms <= 16384 || !nq_profile_on);
-  if (!want) return;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return;
-  std::lock_guard<std::mutex> lock(g_side_mu);
-  SidePool*& pool = g_side_pools[std::make_pair(dev, main)];
-  if (!pool) {
-    SidePool* p = new SidePool();
-    if (hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) != hipSuccess) { delete p; return; }
-    pool = p;
-  }
-  s.side = pool->side; s.pool = &pool->events; s.on = true;
-}
-
 static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, const float* rbf_offsets, const nq_graph* graph, void* workspace,
                                size_t workspace_bytes, const float* grad_energy, const float* grad_forces, float* grad_params, void* stream,
                                bool seeded, const float* seed_x, const float* seed_vec, void* const* layer_events = nullptr) {
@@ -655,6 +694,13 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
   ReadoutArgs r{};
   r.N = N; r.H = H; r.ZO = ws + W.ZO; r.TZO = ws + W.ZO + NH; r.w2 = params + P.w2; r.o2 = params + P.o2;
   r.e_atom = ws + W.e_atom; r.te_atom = ws + W.te_atom;
+  const bool molgw = plan.gw_mode != GW_PAIR_ROWS, mixed = plan.gw_mode == GW_MIXED;
+  const int* const sched = reinterpret_cast<const int*>(ws + W.SCHED);
+  SideStream ss;
+  if (!mixed) side_stream_init(ss, st, N);   // mixed batches: the pair-row contraction of the large molecules and the per-molecule kernel add into one
+                                             // gradient and share the scratch with the split-K products -- everything stays on the main stream (a rare path)
+  hipEvent_t geom_ready = nullptr;   // side stream: the pair geometry records and the layer-0 tangent zeros (first readers: the dual reverse sweep)
+  bool geom_aside = false;
   if (seeded) {
     // zero every tangent half (the forward sweep filled the primal halves only)
     auto zero = [&](size_t off, size_t n) { return hipMemsetAsync(ws + off, 0, n * sizeof(float), st); };
@@ -671,11 +717,24 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
   if (grad_forces) NQ_TRY(nq_negate(st, grad_forces, ws + W.pos_dot, 3L * N));
   else NQ_HIP(hipMemsetAsync(ws + W.pos_dot, 0, 3 * (size_t)N * sizeof(float), st));
   NQ_TRY(nq_geom_tan(st, g, graph->dst, ws + W.pos_dot, ws + W.TD, ws + W.TR));
+  if (ss.on && plan.side_geom && W.fused) {   // nothing in the tangent sweep reads these (layer-0 flavours: plan.layer0); they run under its first products
+    geom_aside = true;
+    hipStream_t sg = ss.fork();
+    if (plan.layer0) {   // t_x_in0 = 0: both layer-0 products are zero rows
+      const WsLayer& y0 = W.lay[0];
+      NQ_HIP(hipMemsetAsync(ws + y0.Z1 + NF, 0, NF * sizeof(float), sg));
+      NQ_HIP(hipMemsetAsync(ws + y0.Hh + NF, 0, NF * sizeof(float), sg));
+      NQ_HIP(hipMemsetAsync(ws + y0.XH + 3 * NF, 0, 3 * NF * sizeof(float), sg));
+    }
+    if (molgw) NQ_TRY(nq_molgw_geometry(sg, g, ws + W.RW, ws + W.TD, ws + W.TR, sched, ws + W.GWREC));
+    geom_ready = ss.mark();
+  }
   for (int l = 0; l < L; ++l) {
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
     float* TZ1 = ws + y.Z1 + NF; float* TH = ws + y.Hh + NF; float* TXH = ws + y.XH + 3 * NF;
     // tangent pre-activation and tangent activation TH = TZ1 * silu'(Z1) in one pass
-    if (plan.layer0 && l == 0) {   // t_x_in0 = 0: both products are zero rows (the dual sweep and the traces read these buffers)
+    if (plan.layer0 && l == 0 && geom_aside) {   // zeroed on the side stream above
+    } else if (plan.layer0 && l == 0) {   // t_x_in0 = 0: both products are zero rows (the general flavours of the dual sweep and the traces read these buffers)
       NQ_HIP(hipMemsetAsync(TZ1, 0, NF * sizeof(float), st));
       NQ_HIP(hipMemsetAsync(TH, 0, NF * sizeof(float), st));
       NQ_HIP(hipMemsetAsync(TXH, 0, 3 * NF * sizeof(float), st));
@@ -725,9 +784,6 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
   // recomputed -- every input-gradient product runs over the primal-adjoint rows only, the elementwise and message kernels skip their GT* stores.
   // (The force sweep's V2 / W2 products keep both forms of their result: the adjoint of the SiLU layer's output, for the silu'' term here, and of its pre-activation.)
   const bool lite = plan.lite && !seeded;
-  SideStream ss;
-  if (plan.gw_mode != GW_MIXED) side_stream_init(ss, st, N);   // mixed batches: the pair-row contraction of the large molecules and the per-molecule kernel add into one
-                                                           // gradient and share the scratch with the split-K products -- everything stays on the main stream (a rare path)
   hipStream_t sd = ss.fork();          // sd == st when the side stream is off
   NQ_TRY(nq_colsum(sd, ws + W.TMPW, N, H, H, gp + P.w2, scr));
   NQ_TRY(nq_colsum(sd, ws + W.ge, N, 1, 1, gp + P.o2, scr));
@@ -741,10 +797,11 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
     if (seed_vec) NQ_HIP(hipMemcpyAsync(gv_cur, seed_vec, 3 * NF * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   float* gphi = ws + W.GPHI2; float* gpsi = gphi + (size_t)E * 3 * F;
-  const bool molgw = plan.gw_mode != GW_PAIR_ROWS, mixed = plan.gw_mode == GW_MIXED;
-  const int* const sched = reinterpret_cast<const int*>(ws + W.SCHED);
   const int* const n_big_pairs = sched + nq_molgw_sched_ints(E, g.B) - 1;
-  if (molgw) NQ_TRY(nq_molgw_geometry(st, g, ws + W.RW, ws + W.TD, ws + W.TR, sched, ws + W.GWREC));
+  if (molgw && !geom_aside) NQ_TRY(nq_molgw_geometry(st, g, ws + W.RW, ws + W.TD, ws + W.TR, sched, ws + W.GWREC));
+  // The records' first reader is the first k_gwr_mol (layer L-1, after that layer's message kernel); the tangent zeros are read by the general dual flavours of
+  // layer 0 (pair rows, NQ_NO_LITE), which in a one-layer model run ahead of it: one wait here covers both (the side work ended a whole tangent sweep ago).
+  if (geom_aside) ss.main_waits(geom_ready);
   if (mixed) NQ_HIP(hipMemsetAsync(ws + W.GBR, 0, 3 * NF * sizeof(float), st));   // only the rows of the large molecules are written below; the column sum runs over all atoms
   for (int l = L - 1; l >= 0; --l) {
     const WsLayer& y = W.lay[l]; const MsgP& mp = P.msg[l]; const UpdP& up = P.upd[l];
@@ -803,10 +860,17 @@ static int painn_backward_impl(const nq_painn_cfg* cfg, const float* params, con
         NQ_TRY(nq_gwr_sorted(st, gphi, gpsi, ws + W.RW, reinterpret_cast<const int*>(ws + W.ORDER), E / 2, F, R, gp + mp.Wr, scr, 3, n_big_pairs));
         NQ_TRY(nq_colsum(st, ws + W.GBR, N, 3 * F, 3 * F, gp + mp.br, scr));
       }
-      // rbf_proj weight and bias gradient from the same node rows, staged per molecule in LDS (main stream: it reads the adjoints this layer's input-gradient
-      // products overwrite next; the fork below orders the side stream and the layer event behind it); mixed: added to what the pair-row kernels left
-      if (molgw)
-        NQ_TRY(nq_gwr_mol(st, g, F, R, plan.gw_cap, m.XH, m.V, m.TXH, m.TV, m.GX, m.GV, m.GTX, m.GTV, sched, ws + W.GWREC, ws + W.GWPART, gp + mp.Wr, gp + mp.br, mixed, l0));
+      // rbf_proj weight and bias gradient from the same node rows, staged per molecule in LDS (k_gwr_mol on the main stream: it reads the adjoints this layer's
+      // input-gradient products overwrite next; the fork below orders the side stream and the layer event behind it); mixed: added to what the pair-row kernels left.
+      // k_gwr_mol_reduce reads the partial rows only and writes gradient slices the optimiser alone reads: side stream (behind this layer's U gradient, ahead
+      // of its W2 gradient; the layer event below is recorded behind it); the next layer's k_gwr_mol waits for it before it overwrites the partial rows
+      if (molgw) {
+        const bool red_aside = ss.on && plan.side_reduce;
+        ss.before_main_writes(SB_GWPART);
+        NQ_TRY(nq_gwr_mol(st, g, F, R, plan.gw_cap, m.XH, m.V, m.TXH, m.TV, m.GX, m.GV, m.GTX, m.GTV, sched, ws + W.GWREC, ws + W.GWPART, gp + mp.Wr, gp + mp.br, mixed, l0,
+                          red_aside ? ss.side : st, red_aside ? ss.next() : nullptr));
+        if (red_aside) ss.read_by_side(SB_GWPART);
+      }
     } else {
       NQ_TRY(nq_msg_rev(st, m, true));
     }

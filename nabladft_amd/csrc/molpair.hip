@@ -676,8 +676,9 @@ int nq_molgw_geometry(hipStream_t st, const NqGraphView& g, const float* RW, con
 
 int nq_gwr_mol(hipStream_t st, const NqGraphView& g, int F, int R, int max_mol_atoms, const float* XH, const float* V, const float* TXH, const float* TV,
                const float* GX, const float* GV, const float* GTX, const float* GTV, const int* sched_ints, const float* recs, float* part, float* gWr,
-               float* gbr, bool accumulate, bool layer0) {
+               float* gbr, bool accumulate, bool layer0, hipStream_t reduce_st, hipEvent_t part_ready) {
   NQ_PROF(st, layer0 ? "gwr_mol_l0" : "gwr_mol");
+  if (reduce_st != st && !part_ready) return nq_fail(NQ_ERR_ARG, "nq_gwr_mol: a reduce stream of its own needs an event");
   const MolGwBufs b = molgw_bufs(const_cast<int*>(sched_ints), g.E, g.B);
   GwrMolArgs q;
   q.g = g; q.F = F; q.nslices = F / GM_CH; q.groups = molgw_groups(g.B, q.nslices);
@@ -695,7 +696,9 @@ int nq_gwr_mol(hipStream_t st, const NqGraphView& g, int F, int R, int max_mol_a
     hipLaunchKernelGGL(k_gwr_mol<false>, dim3(q.groups * q.nslices), dim3(GM_THREADS), lds, st, q, PA, PG);
   }
   NQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_gwr_mol_reduce, dim3(nq_cdiv((long)(R + 1) * 3 * F, 256 / GMR_Q)), dim3(256), 0, st, part, b.wlo, q.groups, q.nslices, R, F, gWr, gbr, accumulate ? 1 : 0);
+  // the reduce reads the partial rows only and writes gradient slices: the caller may give it a stream of its own, ordered behind the kernel above by part_ready
+  if (reduce_st != st) { NQ_HIP(hipEventRecord(part_ready, st)); NQ_HIP(hipStreamWaitEvent(reduce_st, part_ready, 0)); }
+  hipLaunchKernelGGL(k_gwr_mol_reduce, dim3(nq_cdiv((long)(R + 1) * 3 * F, 256 / GMR_Q)), dim3(256), 0, reduce_st, part, b.wlo, q.groups, q.nslices, R, F, gWr, gbr, accumulate ? 1 : 0);
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }

@@ -216,13 +216,24 @@ __global__ void k_embed(const int* __restrict__ z, const float* __restrict__ emb
 
 // embedding gradient, deterministic: one workgroup per chunk of atoms, thread f owns column f of an LDS
 // accumulator [T][F]; partial slabs are then reduced in fixed order by k_reduce_partials.
+#define EMB_BATCH 8
 __global__ void k_embed_grad_partial(const int* __restrict__ z, const float* __restrict__ GX, int N, int F, int T, int chunk,
                                      float* __restrict__ part) {
   extern __shared__ float acc[];
   const int f = threadIdx.x;
   for (int t = 0; t < T; ++t) acc[t * F + f] = 0.f;
   const int n0 = blockIdx.x * chunk, n1 = min(N, n0 + chunk);
-  for (int n = n0; n < n1; ++n) acc[(z[n] - 1) * F + f] += GX[(long)n * F + f];
+  // the per-atom LDS update chain is serial (same chunk, same in-chunk order, one accumulator per element type); the loads it waits for are not:
+  // EMB_BATCH atoms' z / GX are fetched together ahead of their adds
+  int n = n0;
+  for (; n + EMB_BATCH <= n1; n += EMB_BATCH) {
+    int t[EMB_BATCH]; float v[EMB_BATCH];
+#pragma unroll
+    for (int i = 0; i < EMB_BATCH; ++i) { t[i] = z[n + i] - 1; v[i] = GX[(long)(n + i) * F + f]; }
+#pragma unroll
+    for (int i = 0; i < EMB_BATCH; ++i) acc[t[i] * F + f] += v[i];
+  }
+  for (; n < n1; ++n) acc[(z[n] - 1) * F + f] += GX[(long)n * F + f];
   for (int t = 0; t < T; ++t) part[((long)blockIdx.x * T + t) * F + f] = acc[t * F + f];
 }
 
