@@ -186,12 +186,13 @@ int nq_hblock_tables(const int32_t* z, const int32_t* atom_mol, const int32_t* m
                      const int32_t* mask_count, int32_t S, int32_t* orb_atom, int32_t* orb_slot, int32_t* look, int64_t look_count,
                      int32_t* err_flag, void* stream);
 /* out_packed[total]: block (dst rows, src columns) = diag[atom] or nondiag[pair(dst, src)] on the atoms' orbital slots; symmetrize != 0
- * adds the transposed element (H + H^T). */
+ * adds the transposed element (H + H^T).  diag is [N][S][S] and nondiag [P][S][S] with the N and P the tables were built for; this call
+ * is given neither, so the caller answers for both sizes (BlockAssembler.assemble checks them); nondiag may be NULL only where P = 0. */
 int nq_hblock_assemble(const float* diag, const float* nondiag, const int32_t* mol_ptr, const int64_t* pair_base, const int64_t* pack_ptr,
                        const int64_t* mol_orb_ptr, const int32_t* orb_atom, const int32_t* orb_slot, const int32_t* look, int32_t B, int32_t S,
                        int32_t symmetrize, int64_t total, float* out_packed, int32_t* err_flag, void* stream);
 /* Reverse of nq_hblock_assemble: grad_diag [N][S][S], grad_nondiag [P][S][S] (unused slots get 0).  inv_table [Zt][S]: slot -> local
- * orbital of that atom type or -1. */
+ * orbital of that atom type or -1.  With P > 0 a NULL e_dst, e_src or grad_nondiag is refused (NQ_ERR_ARG). */
 int nq_hblock_assemble_backward(const float* grad_packed, const int32_t* z, const int32_t* atom_mol, const int64_t* orb_ptr, const int64_t* pack_ptr,
                                 const int64_t* mol_orb_ptr, const int32_t* inv_table, const int64_t* e_dst, const int64_t* e_src, int32_t N,
                                 int64_t P, int32_t S, int32_t symmetrize, float* grad_diag, float* grad_nondiag, void* stream);
@@ -204,7 +205,9 @@ int nq_hblock_packed_dense(float* packed, float* dense, const int64_t* pack_ptr,
  * sum_L sum_M cg_table[l_i][l_j][L][m_i][m_j][M] * f[row][L*L+M][idx(type_i, type_j, n_i, n_j, L)], f = f_ii[atom] or f_ij[pair(i, j)]
  * ([rows][ncomp][Fo]); cg_table [3][3][5][5][5][9] = sqrt(2L+1) * the model's Clebsch-Gordan tensors; shell tables [T][32]; idx_ii
  * [T][S][S][5], idx_ij [T][T][S][S][5] (-1 = absent).  orb_local: local orbital index inside its atom (nq_hblock_tables with identity masks).
- * unit_diagonal: overlap matrices (diagonal = 1, neural_network.py:964-965).  Backward: inv_ii [T][5][Fo], inv_ij [T][T][5][Fo] = n_i*S+n_j or -1. */
+ * unit_diagonal: overlap matrices (diagonal = 1, neural_network.py:964-965).  Backward: inv_ii [T][5][Fo], inv_ij [T][T][5][Fo] = n_i*S+n_j or -1.
+ * f_ii and f_ij share ncomp and Fo: Fo exceeds every index held in idx_ii / idx_ij and ncomp reaches (L+1)^2 of the highest L they carry (the caller
+ * pads the narrower tensor; IrrepsAssembler.assemble checks all of it).  Backward refuses a NULL e_i, e_j or grad_f_ij where P > 0 (NQ_ERR_ARG). */
 int nq_irreps_assemble(const float* f_ii, const float* f_ij, const int32_t* z, const int32_t* mol_ptr, const int64_t* pair_base, const int64_t* pack_ptr,
                        const int64_t* mol_orb_ptr, const int64_t* orb_ptr, const int32_t* orb_atom, const int32_t* orb_local, const int32_t* look,
                        int32_t B, int32_t ncomp, int32_t Fo, const int32_t* tz, const int32_t* sh_n, const int32_t* sh_l, const int32_t* sh_m,

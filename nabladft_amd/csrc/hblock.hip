@@ -185,6 +185,8 @@ int nq_hblock_assemble_backward(const float* grad_packed, const int32_t* z, cons
                                 const int64_t* mol_orb_ptr, const int32_t* inv_table, const int64_t* e_dst, const int64_t* e_src, int32_t N,
                                 int64_t P, int32_t S, int32_t symmetrize, float* grad_diag, float* grad_nondiag, void* stream) {
   if (!grad_packed || !z || !atom_mol || !orb_ptr || !pack_ptr || !mol_orb_ptr || !inv_table || !grad_diag) return nq_fail(NQ_ERR_ARG, "null argument");
+  if (N < 0 || P < 0) return nq_fail(NQ_ERR_ARG, "N = %d, P = %lld", N, (long long)P);
+  if (P > 0 && (!e_dst || !e_src || !grad_nondiag)) return nq_fail(NQ_ERR_ARG, "P = %lld pairs without a pair list or grad_nondiag", (long long)P);
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "hblock_assemble_rev");
   HbRevArgs a{grad_packed, z, atom_mol, (const long long*)orb_ptr, (const long long*)pack_ptr, (const long long*)mol_orb_ptr, inv_table,
@@ -367,6 +369,8 @@ int nq_irreps_assemble_backward(const float* grad_packed, const int32_t* z, cons
   if (!grad_packed || !z || !atom_mol || !pack_ptr || !mol_orb_ptr || !orb_ptr || !inv_ii || !inv_ij || !tz || !sh_n || !sh_l || !sh_m || !sh_off ||
       !cg_table || !grad_f_ii)
     return nq_fail(NQ_ERR_ARG, "null argument");
+  if (N < 0 || P < 0 || ncomp < 0 || Fo < 0) return nq_fail(NQ_ERR_ARG, "N = %lld, P = %lld, ncomp = %d, Fo = %d", (long long)N, (long long)P, ncomp, Fo);
+  if (P > 0 && (!e_i || !e_j || !grad_f_ij)) return nq_fail(NQ_ERR_ARG, "P = %lld pairs without a pair list or grad_f_ij", (long long)P);
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "irreps_assemble_rev");
   IrRevArgs a{grad_packed, z, atom_mol, (const long long*)e_i, (const long long*)e_j, (const long long*)pack_ptr, (const long long*)mol_orb_ptr,

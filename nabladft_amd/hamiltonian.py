@@ -158,7 +158,14 @@ class BlockAssembler:
         return p
 
     def assemble(self, plan: _Plan, diagonal_matrix: torch.Tensor, non_diagonal_matrix: torch.Tensor, symmetrize: bool = True) -> torch.Tensor:
-        """Packed result [plan.total] (differentiable w.r.t. both block tensors)."""
+        """Packed result [plan.total] (differentiable w.r.t. both block tensors).  diagonal_matrix is [plan.N, S, S] and non_diagonal_matrix
+        [plan.P, S, S] (one row per column of the plan's pair list): the kernels index both by the plan's tables alone, so any other shape would be
+        read past its end and is refused here (ValueError), before any launch."""
+        want_d, want_n = (plan.N, self.S, self.S), (plan.P, self.S, self.S)
+        if tuple(diagonal_matrix.shape) != want_d:
+            raise ValueError(f"diagonal_matrix is {tuple(diagonal_matrix.shape)}, the plan needs {want_d}")
+        if tuple(non_diagonal_matrix.shape) != want_n:
+            raise ValueError(f"non_diagonal_matrix is {tuple(non_diagonal_matrix.shape)}, the plan needs {want_n}")
         out = _Assemble.apply(self, plan, symmetrize, diagonal_matrix, non_diagonal_matrix)
         return out
 
@@ -340,6 +347,10 @@ class IrrepsAssembler:
                     c = torch.as_tensor(clebsch_gordan(li, lj, L)).detach().to(torch.float32).cpu() * (2 * L + 1) ** 0.5
                     cgt[li, lj, L, :2 * li + 1, :2 * lj + 1, :2 * L + 1] = c
         self._host = dict(tz=tz, sh_n=sh_n, sh_l=sh_l, sh_m=sh_m, sh_off=sh_off, idx_ii=idx_ii, idx_ij=idx_ij, cgt=cgt)
+        # what the kernels read of a feature row [ncomp, Fo]: column idx of component L^2 + M for every stored (.., L) -> idx
+        self.max_index = max(int(idx_ii.max()), int(idx_ij.max()))
+        held = ((idx_ii >= 0).reshape(-1, self.NL).any(0) | (idx_ij >= 0).reshape(-1, self.NL).any(0)).nonzero()
+        self.max_L = int(held.max()) if held.numel() else -1
         self._count = count
         self._identity = torch.arange(self.MAXORB, dtype=torch.int32).repeat(zt, 1)
         self._dev, self._inv = {}, {}
@@ -379,6 +390,23 @@ class IrrepsAssembler:
         return self._plan_helper.plan(z, ptr, torch.stack([idx_i, idx_j]))
 
     def assemble(self, plan, f_ii, f_ij, symmetrize=True, unit_diagonal=False):
+        """Packed result [plan.total] (differentiable w.r.t. both feature tensors).  f_ii [plan.N, ncomp, Fo] and f_ij [plan.P, ncomp, Fo] share ONE
+        padded shape per row: the kernels stride both with the same ncomp and Fo, so the caller pads the narrower tensor (phisnet.py: ``_pack``).  Fo must
+        exceed every index of irreps_ii / irreps_ij and ncomp must reach (L + 1)^2 for the highest L they carry; anything else would be read past its end,
+        so it is refused here (ValueError), before any launch."""
+        if f_ii.dim() != 3 or f_ij.dim() != 3:
+            raise ValueError(f"f_ii / f_ij must be [rows, ncomp, Fo], got {tuple(f_ii.shape)} and {tuple(f_ij.shape)}")
+        if f_ii.shape[0] != plan.N:
+            raise ValueError(f"f_ii has {f_ii.shape[0]} rows, the plan has {plan.N} atoms")
+        if f_ij.shape[0] != plan.P:
+            raise ValueError(f"f_ij has {f_ij.shape[0]} rows, the plan has {plan.P} ordered pairs")
+        if tuple(f_ij.shape[1:]) != tuple(f_ii.shape[1:]):
+            raise ValueError(f"f_ii rows are {tuple(f_ii.shape[1:])} and f_ij rows {tuple(f_ij.shape[1:])}: both must share one padded [ncomp, Fo]")
+        ncomp, Fo = int(f_ii.shape[1]), int(f_ii.shape[2])
+        if Fo <= self.max_index:
+            raise ValueError(f"Fo = {Fo} features per component, the index dictionaries reach index {self.max_index}")
+        if ncomp < (self.max_L + 1) ** 2:
+            raise ValueError(f"ncomp = {ncomp} components, the index dictionaries carry L = {self.max_L} which needs {(self.max_L + 1) ** 2}")
         return _IrAssemble.apply(self, plan, symmetrize, unit_diagonal, f_ii, f_ij)
 
     def check(self, plan):

@@ -675,7 +675,9 @@ class NeuralNetwork(nn.Module):
         return out(g)
 
     def _pack(self, fs, n_out):
-        x = fs.packed if isinstance(fs, PackedList) and fs.packed is not None else torch.cat([f[0] for f in fs], dim=-2)   # [rows, (Lout+1)^2, n_out]
+        """One [rows, (Lout+1)^2, max(n_ii, n_ij)] tensor: IrrepsAssembler.assemble strides f_ii and f_ij with one shared width and refuses anything else,
+        so the narrower head is zero-padded up to the wider one."""
+        x =fs.packed if isinstance(fs, PackedList) and fs.packed is not None else torch.cat([f[0] for f in fs], dim=-2)   # [rows, (Lout+1)^2, n_out]
         pad = max(self._n_out) - n_out
         return torch.nn.functional.pad(x, (0, pad)) if pad else x
 
