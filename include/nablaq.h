@@ -682,6 +682,47 @@ int nq_lbfgs_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, 
 int nq_lbfgs_step(void* state, int32_t N, int32_t B, int32_t memory, int32_t n_small, const void* forces, int32_t forces_f64, const uint8_t* fixed_mask,
                   float* pos32, double fmax, double maxstep, double damping, double alpha, int32_t evaluate_only, void* stream);
 
+/* ---- Batched molecular dynamics, state on the device (csrc/md.hip; entry points added, ABI 17 unchanged) ------------------------------------------------------------------------
+ * Replaces: PYGAseInterface.init_md / run_md (nablaDFT/optimization/pyg_ase_interface.py:207-263, 284-294: ase VelocityVerlet :239, ase Langevin :241-246),
+ * _init_velocities (:265-282: MaxwellBoltzmannDistribution, Stationary, ZeroRotation), the FixAtoms constraint (:159-162) and the MDLogger / Trajectory
+ * observers (:251-263) as device rings.  ase is not in the reference tree: the equations are restated (nabladft_amd/md.py) and unpinned against ase.
+ * Units: Hartree, Angstrom, amu, fs, K.  nq_md_constants writes {KAPPA, KB}: (Hartree/Angstrom)/amu -> Angstrom/fs^2 and Hartree/K from CODATA 2014.
+ * All state is float64.  flags: 1 = log ring, 2 = frame ring, 4 = frames carry velocities too; a requested ring with capacity 0 is NQ_ERR_ARG.
+ * `state` is ONE caller-owned device buffer of nq_md_state_bytes(...) bytes, 16-byte aligned (0 = bad dimensions, see nq_last_error).  nq_md_state_layout
+ * fills offsets_host[12] with the byte offsets of: header int32[32] = {steps taken, status (-2: a call came with other dimensions than nq_md_init and did
+ * nothing), pending (a first half-step waits for its second half-kick), log rows in the ring, frames in the ring, overflow flag (a sample found its ring full
+ * and was dropped), N, B, n_small, log capacity, frame capacity, flags, last sampled step, internal}; mol_ptr int32[B+1]; order int32[B]; mol_key int64[B];
+ * mass f64[N]; fixed uint8[N]; r f64[N][3]; v f64[N][3]; rv f64[N][3] (rnd_vel of a pending step with injected noise); log f64[cap][B][8] = {step, E_tot,
+ * E_pot, E_kin (Hartree), T (K, dof = 3 (n - n_fixed)), |P| (amu Angstrom/fs), |L| about the centre of mass (amu Angstrom^2/fs), 0}; frames f64[cap][N][3];
+ * velocity frames f64[cap][N][3].  The host drains a ring by copying its rows and writing 0 to header word 3 / 4 on the same stream.
+ * nq_md_init: mol_ptr_host, mol_key_host (nullable: the molecule's index), masses_host (amu, every one > 0 or NQ_ERR_ARG) and fixed_host (nullable uint8[N])
+ * are HOST arrays; every molecule needs 1..512 atoms (NQ_ERR_MOL_TOO_LARGE above); copies `pos` (float32, or float64 when pos_f64) into r and pos32 (the
+ * model's input tensor) and `vel` (device f64[N][3], nullable: zero) into v, writes *n_small_host, synchronises `stream` once.
+ * nq_md_init_velocities: v = zeta sqrt(KAPPA KB T_init / m), then (flags) v -= sum(m v) / sum(m) and v -= omega x (x - x_com) with I omega = L solved in the
+ * eigenbasis of the inertia tensor (eigenvalues <= 1e-10 trace(I) are skipped: atoms, diatomics, linear molecules); fixed atoms keep v = 0.
+ * nq_md_step: ONE kernel launch = one MD step, given the forces (float32, or float64 when forces_f64) and optionally the energies [B] of the CURRENT
+ * positions: (a) the second half-kick of the pending step, (b) when step % interval == 0 a log row and a frame of the now consistent (x, v, F), (c) this
+ * step's noise, first half-kick and drift, pos32 = (float) r.  mode 0: velocity Verlet; mode 1: Langevin with friction fr (1/fs) at kT (Hartree), fix_com.
+ * finish_only != 0: (a) and (b) only, the last call of a run; it advances nothing.  xi / eta (device f64[N][3], nullable, both or none): the normals of (c)
+ * instead of the generator's.  Generator: Philox4x32-10 keyed by `seed`, counter (mol_key, step, atom inside the molecule, draw), Box-Muller in float64; the
+ * second half-kick generates the step's numbers again.  dt <= 0, kT < 0, fr < 0: NQ_ERR_ARG.  Like nq_lbfgs_step the call repeats the dimensions; on a mismatch
+ * with the header the kernel touches nothing but header word 1 (-2) and the call still returns NQ_OK.
+ * nq_md_normals: out f64[N][3] = exactly the normals the kernels draw at (seed, step): draw 0 = xi, 1 = eta (Langevin step), 2 = zeta (velocity
+ * initialisation, step 0), 3 = the unused partner of zeta; mol_ptr int32[B+1] and mol_key int64[B] (nullable: index) are DEVICE arrays.
+ * Results are bitwise reproducible and do not depend on which other molecules share the batch. */
+int nq_md_constants(double* kappa_kb_host);
+size_t nq_md_state_bytes(int32_t N, int32_t B, int32_t log_cap, int32_t frame_cap, int32_t flags);
+int nq_md_state_layout(int32_t N, int32_t B, int32_t log_cap, int32_t frame_cap, int32_t flags, size_t* offsets_host);
+int nq_md_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, const int64_t* mol_key_host, const double* masses_host, const uint8_t* fixed_host,
+               int32_t N, int32_t B, int32_t log_cap, int32_t frame_cap, int32_t flags, const void* pos, int32_t pos_f64, const double* vel, float* pos32,
+               int32_t* n_small_host, void* stream);
+int nq_md_init_velocities(void* state, int32_t N, int32_t B, int32_t n_small, int32_t log_cap, int32_t frame_cap, int32_t flags, double T_init, int64_t seed,
+                          int32_t remove_translation, int32_t remove_rotation, void* stream);
+int nq_md_step(void* state, int32_t N, int32_t B, int32_t n_small, int32_t log_cap, int32_t frame_cap, int32_t flags, const void* forces, int32_t forces_f64,
+               const void* energies, int32_t energies_f64, float* pos32, int32_t mode, double dt, double kT, double fr, int32_t interval, int64_t seed,
+               const double* xi, const double* eta, int32_t finish_only, void* stream);
+int nq_md_normals(int64_t seed, int32_t step, int32_t draw, const int32_t* mol_ptr, const int64_t* mol_key, int32_t N, int32_t B, double* out, void* stream);
+
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,
  * row-major behind pair_ptr int64[B+1] (P = pair_ptr[B]).  "head-major" = per molecule [H][n][n] starting at H * pair_ptr[b]: the layout of the attention bias,

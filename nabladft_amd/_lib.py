@@ -209,6 +209,13 @@ SYMBOLS = {
     "nq_lbfgs_state_layout": (C.c_int, [_I32, _I32, _I32, C.POINTER(_SZ)]),
     "nq_lbfgs_init": (C.c_int, [_P, _SZ, _P, _I32, _I32, _I32, _P, _I32, _P, C.POINTER(C.c_int32), _P]),
     "nq_lbfgs_step": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _D, _D, _D, _D, _I32, _P]),
+    "nq_md_constants": (C.c_int, [C.POINTER(C.c_double)]),
+    "nq_md_state_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "nq_md_state_layout": (C.c_int, [_I32, _I32, _I32, _I32, _I32, C.POINTER(_SZ)]),
+    "nq_md_init": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, C.POINTER(C.c_int32), _P]),
+    "nq_md_init_velocities": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _D, _I64, _I32, _I32, _P]),
+    "nq_md_step": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _I32, _D, _D, _D, _I32, _I64, _P, _P, _I32, _P]),
+    "nq_md_normals": (C.c_int, [_I64, _I32, _I32, _P, _P, _I32, _I32, _P, _P]),
     "nq_g3d_max_mol_atoms": (C.c_int32, []),
     "nq_g3d_pair_forward": (C.c_int, [_P] * 9 + [_I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "nq_g3d_pair_scratch_floats": (_SZ, [_I32, _I64, _I32]),

@@ -340,4 +340,12 @@ class BatchwiseOptimizeTask:
             out.close()
 
 
-__all__ = ["ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "LBFGSState"]
+def __getattr__(name):
+    # nablaDFT.optimization also exports PYGAseInterface (pyg_ase_interface.py:119-335); it lives in md.py, which imports this module
+    if name in ("PYGAseInterface", "BatchedMD"):
+        from . import md
+        return getattr(md, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+__all__ = ["ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "LBFGSState", "PYGAseInterface", "BatchedMD"]
