@@ -723,6 +723,40 @@ int nq_md_step(void* state, int32_t N, int32_t B, int32_t n_small, int32_t log_c
                const double* xi, const double* eta, int32_t finish_only, void* stream);
 int nq_md_normals(int64_t seed, int32_t step, int32_t draw, const int32_t* mol_ptr, const int64_t* mol_key, int32_t N, int32_t B, double* out, void* stream);
 
+/* ---- Batched normal modes: finite-difference Hessians and a Jacobi eigensolver (csrc/vib.hip; entry points added, ABI 17 unchanged) ------------------------
+ * Replaces: PYGAseInterface.compute_normal_modes (nablaDFT/optimization/pyg_ase_interface.py:317-334: ase.vibrations.Vibrations(atoms).run(), .summary(),
+ * .write_jmol()).  ase is not in the reference tree: the arithmetic is restated (nabladft_amd/vibrations.py) and unpinned against ase.
+ * Units: Hartree, Angstrom, amu; every array below is float64 unless said otherwise.  D = 3 x (free atoms of the batch), P = sum over molecules of m_b^2 with
+ * m_b = 3 x (free atoms of molecule b) <= 576 (NQ_ERR_MOL_TOO_LARGE above); the caller computes both from mol_ptr and the fixed mask, nq_vib_init checks them.
+ * The displacement list is molecule-major over (molecule, free degree of freedom); displacement j owns two images of its molecule, "-" then "+".
+ * `state` is ONE caller-owned device buffer of nq_vib_state_bytes(N, B, D, P) bytes, 16-byte aligned (0 = bad dimensions, see nq_last_error).
+ * nq_vib_state_layout fills offsets_host[18] with the byte offsets of: header int32[16] = {N, B, D, P low word, P high word, status (-2: a call came with other
+ * dimensions than nq_vib_init and did nothing, -3: a chunk's image tensor has another size than the plan), n_lds}; mol_ptr int32[B+1]; dof_ptr int32[B+1];
+ * hess_ptr int64[B+1] (start of each molecule's packed m_b x m_b matrices); order int32[B] (molecules whose matrix fits the LDS first); free_atom int32[D/3];
+ * disp_mol int32[D]; disp_off int64[D+1] (atoms of all images before displacement j); im [D] = mass^-1/2 per degree of freedom; r [N][3] (the geometry);
+ * h [D] (realised steps); asymmetry [B]; sweeps int32[B]; status int32[B] (0 converged, 1 sweep cap reached, 2 wrong launch plan); omega2 [D]; work [P];
+ * hessian [P]; modes [P] (row k of a molecule's block = mode k, ascending omega2).
+ * nq_vib_init: mol_ptr_host, masses_host (amu, every free atom's > 0) and fixed_host (nullable uint8[N]) are HOST arrays; copies `pos` (float32, or float64
+ * when pos_f64) into r, writes plan_host[3] = {n_lds, largest m in LDS, largest m}, synchronises `stream` once.
+ * nq_vib_displace: chunk [c0, c1) of the displacement list -> image_pos float32 [image_atoms][3], image_atoms = disp_off[c1] - disp_off[c0]: every image is
+ * (float) r of its molecule with one coordinate (float)(r -+ delta); h[j] = (double) x32+ - (double) x32-, the step the quotient divides by.
+ * nq_vib_accumulate: the model's forces on those images (float32, or float64 when forces_f64) -> rows (F- - F+)[free] / h[j] of `work`.
+ * nq_vib_finish: hessian = (G + G^T) / 2, asymmetry = max |G - G^T| per molecule, work = im_i hessian_ij im_j (the mass-weighted matrix, exactly symmetric).
+ * nq_vib_eigh: eigen-decomposition of every molecule's matrix in `work` (which it overwrites) by the parallel cyclic Jacobi method, one 256-thread workgroup
+ * per molecule (round-robin ordering; the matrix in LDS when m <= 141, else in place in global memory); stops at off(A) <= m 2^-52 |A|_F or after 30 sweeps.
+ * Writes omega2 ascending, modes (eigenvector k in row k, multiplied by im when scale_modes, orthonormal otherwise), sweeps and status.  n_lds, max_m_lds and
+ * max_m are what nq_vib_init returned.  No atomics: results are bitwise reproducible and do not depend on which other molecules share the batch. */
+size_t nq_vib_state_bytes(int32_t N, int32_t B, int32_t D, int64_t P);
+int nq_vib_state_layout(int32_t N, int32_t B, int32_t D, int64_t P, size_t* offsets_host);
+int nq_vib_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, const double* masses_host, const uint8_t* fixed_host, int32_t N, int32_t B,
+                int32_t D, int64_t P, const void* pos, int32_t pos_f64, int32_t* plan_host, void* stream);
+int nq_vib_displace(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t c0, int32_t c1, double delta, float* image_pos, int64_t image_atoms,
+                    void* stream);
+int nq_vib_accumulate(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t c0, int32_t c1, const void* forces, int32_t forces_f64,
+                      int64_t image_atoms, void* stream);
+int nq_vib_finish(void* state, int32_t N, int32_t B, int32_t D, int64_t P, void* stream);
+int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t n_lds, int32_t max_m_lds, int32_t max_m, int32_t scale_modes, void* stream);
+
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,
  * row-major behind pair_ptr int64[B+1] (P = pair_ptr[B]).  "head-major" = per molecule [H][n][n] starting at H * pair_ptr[b]: the layout of the attention bias,

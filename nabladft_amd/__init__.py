@@ -20,6 +20,8 @@ Public surface mirrors the reference plugin classes for this path:
                                     task.py:9-73): the `optimize` job, L-BFGS state on the device (optimization.py)
   nabladft_amd.PYGAseInterface / BatchedMD <-> nablaDFT.optimization.PYGAseInterface (pyg_ase_interface.py:119-335): single point, batched NVE / Langevin
                                     MD with the state on the device (md.py; the ase integrators restated, unpinned), relaxation through the device L-BFGS
+  nabladft_amd.BatchedVibrations <-> ase.vibrations.Vibrations behind PYGAseInterface.compute_normal_modes (pyg_ase_interface.py:317-334): batched
+                                    finite-difference Hessians and a Jacobi eigensolver on the device (vibrations.py; restated, unpinned)
   nabladft_amd.spk.*            <-> the schnetpack classes config/model/{painn,schnet}.yaml instantiate (parity unpinned)
   nabladft_amd.read_energy_database / ArenaLoader <-> PyGNablaDFT.process + DataLoader collate (dataset/pyg_datasets.py:101-109)
 """
@@ -37,7 +39,9 @@ from . import optimization  # noqa: F401
 from .optimization import ASEBatchwiseLBFGS, BatchwiseOptimizeTask, PyGBatchwiseCalculator  # noqa: F401
 from . import md  # noqa: F401
 from .md import BatchedMD, PYGAseInterface  # noqa: F401
+from . import vibrations  # noqa: F401
+from .vibrations import BatchedVibrations  # noqa: F401
 from .data import ArenaLoader, ConformerArena, HamiltonianBatch, HamiltonianDatabase, HamiltonianDataset, hamiltonian_batch, read_energy_database  # noqa: F401
 
 __all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "DimeNetPlusPlusForceLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
-           "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "PYGAseInterface"]
+           "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "BatchedVibrations", "PYGAseInterface"]

@@ -27,7 +27,7 @@ device log / frame rings, and does the next first half-kick and drift.  Random n
 (mol_key, step, atom inside the molecule, draw), Box-Muller in float64): a trajectory rerun alone reproduces the one it had inside a batch, bit for bit.
 
 Limits (each raises, nothing degrades silently): Hartree / Angstrom only; molecules of at most 512 atoms; ase's binary ``.traj`` is not written (frames go to
-``<name>.npz`` and the last frame to ``<name>.extxyz``); ``compute_normal_modes`` is not built; ``optimize`` runs the device L-BFGS of optimization.py, not ase's
+``<name>.npz`` and the last frame to ``<name>.extxyz``); ``compute_normal_modes`` is vibrations.py and has its own limits; ``optimize`` runs the device L-BFGS of optimization.py, not ase's
 ``QuasiNewton`` (BFGS + line search), and ``optimizer_class`` is accepted and ignored; no periodic cells, no thermostat but Langevin, no barostat, one time
 step and one temperature per batch.
 """
@@ -370,7 +370,7 @@ class PYGAseInterface:
     "a"), ``<name>.npz`` (``positions`` [frames, N, 3], ``ptr``, ``z``, ``steps``) and ``<name>.extxyz`` (last frame); ase's binary ``.traj`` is not written.
     Steps are counted from the first ``init_md`` on; Time[ps] is the step number times the current ``time_step``.  A step both runs would sample (the last of
     one run, the first of the next) is written once, by the earlier run.
-    ``compute_normal_modes`` (:317-334) raises NotImplementedError: finite-difference Hessians are the follow-up."""
+    ``compute_normal_modes`` (:317-334) runs ``vibrations.BatchedVibrations`` (on a device that is not a GPU it raises NotImplementedError: no CPU path)."""
 
     def __init__(self, molecule_path: str, working_dir: str, config, model, energy_key: str = "energy", force_key: str = "forces",
                  energy_unit: Union[str, float] = "Hartree", position_unit: Union[str, float] = "Angstrom", device: Union[str, torch.device] = "cpu",
@@ -473,7 +473,15 @@ class PYGAseInterface:
         return converged
 
     def compute_normal_modes(self, write_jmol: bool = True):
-        raise NotImplementedError("compute_normal_modes is not built (ase.vibrations: finite-difference Hessians are the follow-up)")
+        """Normal modes at ``self.positions`` with the interface's fixed atoms (vibrations.py: batched finite-difference Hessians and the device eigensolver
+        instead of ase.vibrations).  Writes ``normal_modes.npz``, ``normal_modes.txt`` (ase's summary layout, one block per molecule) and, when ``write_jmol``,
+        ``normal_modes.xyz`` (one frame per mode) into ``working_dir``; the driver stays in ``self.vibrations``."""
+        if self.device.type != "cuda":
+            raise NotImplementedError("compute_normal_modes runs on MI355X only (no CPU path): construct the interface with device='cuda'")
+        from .vibrations import BatchedVibrations, write_normal_modes
+        vib = self.vibrations = BatchedVibrations(self.calculator, fixed_atoms_mask=self.fixed_mask)
+        vib.run(self._batch())
+        write_normal_modes(self.working_dir, vib, self.z, self.ptr, self.positions, write_jmol)
 
 
 __all__ = ["BatchedMD", "MDState", "PYGAseInterface", "KAPPA", "KB", "masses_for", "read_xyz", "write_xyz"]

@@ -345,7 +345,10 @@ def __getattr__(name):
     if name in ("PYGAseInterface", "BatchedMD"):
         from . import md
         return getattr(md, name)
+    if name == "BatchedVibrations":
+        from . import vibrations
+        return vibrations.BatchedVibrations
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "LBFGSState", "PYGAseInterface", "BatchedMD"]
+__all__ = ["ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "LBFGSState", "PYGAseInterface", "BatchedMD", "BatchedVibrations"]
