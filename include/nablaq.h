@@ -156,7 +156,9 @@ int nq_painn_ws_lookup(const nq_painn_cfg* cfg, int32_t N, int32_t E, int32_t B,
 typedef struct nq_schnet_cfg {
   int32_t n_atom_basis;    /* F in {64,128,256} (n_filters = n_atom_basis) */
   int32_t n_interactions;  /* L */
-  int32_t n_rbf;           /* GaussianRBF(n_rbf, cutoff) */
+  int32_t n_rbf;           /* GaussianRBF(n_rbf, cutoff): 2 <= n_rbf <= 268 (the k0 sort of the first-layer weight gradient has 256 bins:
+                            * n_rbf - min(n_rbf, 13) + 1 <= 256) and max(n_rbf, 13) * F * 4 B <= 156 KB (W1^T in LDS: 156 at F = 256); anything
+                            * else is refused with NQ_ERR_ARG before any device work */
   int32_t max_z;           /* rows of representation.embedding.weight (row 0 = padding) */
   double cutoff;           /* CosineCutoff(cutoff) = GaussianRBF cutoff, Angstrom */
   float rbf_coeff;         /* -0.5 / width^2, width = offsets[1] - offsets[0] */
@@ -173,6 +175,16 @@ int nq_schnet_forward(const nq_schnet_cfg* cfg, const float* params, const float
                       size_t workspace_bytes, float* energy, float* forces, void* stream);
 int nq_schnet_backward(const nq_schnet_cfg* cfg, const float* params, const float* rbf_offsets, const nq_graph* graph, void* workspace,
                        size_t workspace_bytes, const float* grad_energy, const float* grad_forces, float* grad_params, void* stream);
+/* Test/inspection hook like nq_painn_ws_lookup: offset (in floats) and element count of a named buffer of the SchNet workspace; host-only arithmetic.
+ * Buffer names are those of oracle/spk_schnet_ref.py:SchNetSweeps; P = E/2 undirected pairs; tangent = 1 selects the tangent half where one exists.
+ *   per layer, with a tangent half: "x" (layers 0..L), "y", "m", "t1", "u" [N][F]; "a1", "h2" [P][F];  "zo" [N][F/2] (with tangent half);
+ *   "e_atom", "te_atom" [N];  "rw" [P][32] window records, "order" [P] / "pair_of" [E] / "pair_slot" [P] (int32 payloads), "geomp" [P][4];
+ *   "td" [E] (per slot), "tdp" [P], "gd_total" [P] (dE/dd summed over the layers and both directed edges, after a forward call with forces);
+ *   the adjoint buffers SHARED by all layers "gx", "gu", "gm", "gy" [2][N][F] and "gh2", "ga1" [2][P][F]: after nq_schnet_backward they hold the
+ *   layer processed last, layer 0 ("gu" = (gt1, gtt1), "ga1" = (gz1, gtz1 * td) -- the in-place results; "gx" = the adjoints of x[0]).
+ * NQ_ERR_ARG with a message for an unknown name, a layer out of range, or a tangent half asked of a buffer that has none. */
+int nq_schnet_ws_lookup(const nq_schnet_cfg* cfg, int32_t N, int32_t E, int32_t B, const char* name, int32_t layer, int32_t tangent,
+                        size_t* offset_floats, size_t* count);
 
 /* ---- Hamiltonian block assembly (QHNet.build_final_matrix, qhnet/qhnet.py:293-321; + H + H^T, qhnet.py:237; HamiltonianLoss,
  *      qhnet/loss.py:9-16).  Packed result layout: molecule after molecule, M_b x M_b row-major, M_b = orbitals of molecule b;

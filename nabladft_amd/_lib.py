@@ -73,6 +73,7 @@ SYMBOLS = {
     "nq_schnet_workspace_bytes": (_SZ, [C.POINTER(SchnetCfg), _I32, _I32, _I32]),
     "nq_schnet_forward": (C.c_int, [C.POINTER(SchnetCfg), _P, _P, C.POINTER(Graph), _P, _SZ, _P, _P, _P]),
     "nq_schnet_backward": (C.c_int, [C.POINTER(SchnetCfg), _P, _P, C.POINTER(Graph), _P, _SZ, _P, _P, _P, _P]),
+    "nq_schnet_ws_lookup": (C.c_int, [C.POINTER(SchnetCfg), _I32, _I32, _I32, C.c_char_p, _I32, _I32, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "nq_hblock_tables": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _I32, _P, _P, _P, _I64, _P, _P]),
     "nq_hblock_assemble": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I64, _P, _P, _P]),
     "nq_hblock_assemble_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _I32, _I32, _P, _P, _P]),

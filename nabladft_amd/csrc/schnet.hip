@@ -14,6 +14,7 @@
 //   * all reverse-mode scatters over the source atom are evaluated as gathers over the atom's own CSR row -- no atomics, bitwise
 //     reproducible.
 // PARITY UNPINNED (schnetpack is not part of the reference tree): checked against this repo's restatement only.
+#include <string.h>
 #include "common.h"
 #include "lanes.h"
 #include "../../include/nablaq.h"
@@ -499,6 +500,8 @@ static int sn_check(const nq_schnet_cfg* c, const nq_graph* g, const void* ws, s
   if (!(F == 64 || F == 128 || F == 256)) return nq_fail(NQ_ERR_ARG, "n_atom_basis must be 64, 128 or 256");
   if (c->n_interactions < 1 || c->n_interactions > NQ_MAX_LAYERS) return nq_fail(NQ_ERR_ARG, "n_interactions out of range");
   if (c->n_rbf < 2 || (size_t)(c->n_rbf < FWIN ? FWIN : c->n_rbf) * F * sizeof(float) > 156 * 1024) return nq_fail(NQ_ERR_ARG, "n_rbf * n_atom_basis does not fit LDS");
+  if (c->n_rbf - (c->n_rbf < FWIN ? c->n_rbf : FWIN) + 1 > 256)     // the k0 sort of the first-layer weight gradient (edge.hip:nq_k0_sort)
+    return nq_fail(NQ_ERR_ARG, "n_rbf = %d: the k0 sort supports at most 256 window starts (n_rbf <= 268)", c->n_rbf);
   if (c->max_z < 2) return nq_fail(NQ_ERR_ARG, "max_z");
   if (g->N <= 0 || g->E <= 0 || g->B <= 0) return nq_fail(NQ_ERR_ARG, "empty graph");
   if ((g->E & 1) || !g->lowptr || !g->dst) return nq_fail(NQ_ERR_ARG, "SchNet needs the symmetric edge list with lowptr (nq_graph_count / nq_graph_fill)");
@@ -519,6 +522,48 @@ size_t nq_schnet_workspace_bytes(const nq_schnet_cfg* cfg, int32_t N, int32_t E,
   if (!cfg || cfg->n_interactions < 1 || cfg->n_interactions > NQ_MAX_LAYERS || N < 0 || E < 0) return 0;
   SnWs W; sn_ws_layout(cfg, N, E, B, &W);
   return W.total * sizeof(float);
+}
+
+int nq_schnet_ws_lookup(const nq_schnet_cfg* cfg, int32_t N, int32_t E, int32_t B, const char* name, int32_t l, int32_t tangent,
+                        size_t* off, size_t* count) {
+  if (!cfg || !name || !off || !count) return nq_fail(NQ_ERR_ARG, "null argument");
+  if (cfg->n_interactions < 1 || cfg->n_interactions > NQ_MAX_LAYERS || N < 0 || E < 0) return nq_fail(NQ_ERR_ARG, "n_interactions, N or E out of range");
+  SnWs W; sn_ws_layout(cfg, N, E, B, &W);
+  const size_t F = cfg->n_atom_basis, H = F / 2, n = N, e = E, p = e / 2;
+  const int L = cfg->n_interactions;
+  size_t base = 0, rows = 0, w = 0;
+  bool dual = false;
+#define LAYER_OK(maxl) if (l < 0 || l > (maxl)) return nq_fail(NQ_ERR_ARG, "layer %d out of range", l)
+  if (!strcmp(name, "x")) { LAYER_OK(L); base = W.X[l]; rows = n; w = F; dual = true; }
+  else if (!strcmp(name, "y")) { LAYER_OK(L - 1); base = W.lay[l].Y; rows = n; w = F; dual = true; }
+  else if (!strcmp(name, "m")) { LAYER_OK(L - 1); base = W.lay[l].M; rows = n; w = F; dual = true; }
+  else if (!strcmp(name, "t1")) { LAYER_OK(L - 1); base = W.lay[l].T1; rows = n; w = F; dual = true; }
+  else if (!strcmp(name, "u")) { LAYER_OK(L - 1); base = W.lay[l].U; rows = n; w = F; dual = true; }
+  else if (!strcmp(name, "a1")) { LAYER_OK(L - 1); base = W.lay[l].A1; rows = p; w = F; dual = true; }
+  else if (!strcmp(name, "h2")) { LAYER_OK(L - 1); base = W.lay[l].H2; rows = p; w = F; dual = true; }
+  else if (!strcmp(name, "zo")) { base = W.ZO; rows = n; w = H; dual = true; }
+  else if (!strcmp(name, "e_atom")) { base = W.e_atom; rows = n; w = 1; }
+  else if (!strcmp(name, "te_atom")) { base = W.te_atom; rows = n; w = 1; }
+  else if (!strcmp(name, "rw")) { base = W.RW; rows = p; w = RW_STRIDE; }
+  else if (!strcmp(name, "order")) { base = W.ORDER; rows = p; w = 1; }                 // int32 payload
+  else if (!strcmp(name, "pair_of")) { base = W.PAIR_OF; rows = e; w = 1; }             // int32 payload
+  else if (!strcmp(name, "pair_slot")) { base = W.PAIR_SLOT; rows = p; w = 1; }         // int32 payload
+  else if (!strcmp(name, "geomp")) { base = W.GEOMP; rows = p; w = 4; }
+  else if (!strcmp(name, "td")) { base = W.TD; rows = e; w = 1; }
+  else if (!strcmp(name, "tdp")) { base = W.TDP; rows = p; w = 1; }
+  else if (!strcmp(name, "gd_total")) { base = W.GDT; rows = p; w = 1; }
+  else if (!strcmp(name, "gx")) { base = W.GX; rows = n; w = F; dual = true; }
+  else if (!strcmp(name, "gu")) { base = W.GU; rows = n; w = F; dual = true; }
+  else if (!strcmp(name, "gm")) { base = W.GM; rows = n; w = F; dual = true; }
+  else if (!strcmp(name, "gy")) { base = W.GY; rows = n; w = F; dual = true; }
+  else if (!strcmp(name, "gh2")) { base = W.GH2; rows = p; w = F; dual = true; }
+  else if (!strcmp(name, "ga1")) { base = W.GA1; rows = p; w = F; dual = true; }
+  else return nq_fail(NQ_ERR_ARG, "unknown workspace buffer '%s'", name);
+#undef LAYER_OK
+  if (tangent && !dual) return nq_fail(NQ_ERR_ARG, "buffer '%s' has no tangent half", name);
+  *off = base + (tangent ? rows * w : 0);
+  *count = rows * w;
+  return NQ_OK;
 }
 
 int nq_schnet_forward(const nq_schnet_cfg* cfg, const float* params, const float* rbf_offsets, const nq_graph* graph, void* workspace,

@@ -13,7 +13,7 @@ installed here; layer definitions, parameter names (``representation.interaction
 ``output_modules.0.outnet.{0,1}``) and the train/eval behaviour of post-processors follow SURVEY.md Appendix C (recalled,
 unverified).  Checked against this repo's own restatement only (tests/test_spk_cpu.py, tests/test_spk_gpu.py).
 ``SchNet`` (config/model/schnet.yaml) runs on its own engine entry points (csrc/schnet.hip; restatement
-oracle/spk_schnet_ref.py).  Not built: trainable / non-Gaussian radial bases, shared_interactions / shared_filters, atomrefs,
+oracle/spk_schnet_ref.py).  Not built: trainable / non-Gaussian radial bases, a radial-basis cutoff other than the cosine cutoff's, shared_interactions / shared_filters, atomrefs,
 stress and the ``AtomisticTask`` wrapper (nablaDFT/ase_model/task.py).
 """
 import ctypes as C
@@ -70,6 +70,13 @@ class _Mixing(nn.Module):
         self.mu_channel_mix = Dense(F, 2 * F, bias=False)
 
 
+def _one_cutoff(who, radial_basis, cutoff_fn):
+    """schnetpack lets GaussianRBF(cutoff=a) and CosineCutoff(b) differ; the engine has one cutoff for the centres, the width and the window."""
+    if float(radial_basis.cutoff) != float(cutoff_fn.cutoff):
+        raise NotImplementedError(f"nabladft_amd.spk.{who}: radial_basis.cutoff ({float(radial_basis.cutoff)}) != cutoff_fn.cutoff "
+                                  f"({float(cutoff_fn.cutoff)}) is not built")
+
+
 class PaiNN(nn.Module):
     """schnetpack.representation.PaiNN(n_atom_basis, n_interactions, radial_basis, cutoff_fn, ...) -- parameter holder."""
 
@@ -82,6 +89,7 @@ class PaiNN(nn.Module):
             raise NotImplementedError("nabladft_amd.spk.PaiNN: needs GaussianRBF + CosineCutoff (config/model/painn.yaml:9-16)")
         if abs(epsilon - 1e-8) > 0:
             raise NotImplementedError("nabladft_amd.spk.PaiNN: epsilon is fixed to 1e-8 in the kernels")
+        _one_cutoff("PaiNN", radial_basis, cutoff_fn)
         self.n_atom_basis, self.n_interactions, self.max_z = n_atom_basis, n_interactions, max_z
         self.radial_basis, self.cutoff_fn = radial_basis, cutoff_fn
         self.cutoff = float(cutoff_fn.cutoff)
@@ -114,6 +122,7 @@ class SchNet(nn.Module):
             raise NotImplementedError("nabladft_amd.spk.SchNet: n_filters must equal n_atom_basis")
         if not isinstance(radial_basis, GaussianRBF) or not isinstance(cutoff_fn, CosineCutoff):
             raise NotImplementedError("nabladft_amd.spk.SchNet: needs GaussianRBF + CosineCutoff (config/model/schnet.yaml:9-16)")
+        _one_cutoff("SchNet", radial_basis, cutoff_fn)
         self.n_atom_basis, self.n_interactions, self.max_z = n_atom_basis, n_interactions, max_z
         self.radial_basis, self.cutoff_fn = radial_basis, cutoff_fn
         self.cutoff = float(cutoff_fn.cutoff)

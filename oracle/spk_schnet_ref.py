@@ -199,9 +199,12 @@ class SchNetSweeps:
             Win, W1, b1, W2, b2, Wo1, bo1, Wo2, bo2 = self._w(l)
             gm = ((gx @ Wo2) * sig(S["t1", l])) @ Wo1
             gW = gm[self.i] * S["y", l][self.j]                                  # adjoint of the (cutoff-scaled) filter, per edge
-            gd = gd + self.drc * (gW * S["h2", l]).sum(1)
+            gd_cut = self.drc * (gW * S["h2", l]).sum(1)
+            gd = gd + gd_cut
             gz1 = ((gW * self.rc[:, None]) @ W2) * sig(S["z1", l])
-            gd = gd + ((gz1 @ W1) * self.dg).sum(1)
+            gd_win = ((gz1 @ W1) * self.dg).sum(1)
+            gd = gd + gd_win
+            S["gd", l] = gd_cut + gd_win                                         # this layer's share, per directed edge (kept for the operator tests)
             gy = self._gather_sum(gm, S["h2", l] * self.rc[:, None])             # own-row gather (symmetric filter)
             gx = gx + gy @ Win
         self.S["gd"] = gd
@@ -281,6 +284,11 @@ class SchNetSweeps:
             # in2f and the residual stream
             G[p + "in2f.weight"] = gy.T @ S["x", l] + gty.T @ S["tx", l]
             gx, gtx = gx + gy @ Win, gtx + gty @ Win
+            # the locals of this layer, kept for the operator tests (the engine's shared adjoint buffers; per directed edge where per edge)
+            S["r_gm", l], S["r_gtm", l], S["r_gy", l], S["r_gty", l] = gm, gtm, gy, gty
+            S["r_gh2", l], S["r_gth2", l], S["r_gz1", l], S["r_gtz1td", l] = gh2, gth2, gz1, gtz1 * td
+            S["r_gt1", l], S["r_gtt1", l] = gt1, gtt1
+        S["r_gx"], S["r_gtx"] = gx, gtx
         G["representation.embedding.weight"] = torch.zeros_like(P["representation.embedding.weight"]).index_add_(0, self.z, gx)
         return G
 

@@ -103,6 +103,85 @@ def test_backward_refuses_a_workspace_no_forward_has_prepared(lib):
     assert b"no forward call has prepared this workspace" in lib.nq_last_error()
 
 
+def _schnet_cfg(F, L, R, cutoff=5.0, max_z=20):
+    from nabladft_amd import _lib
+    cfg = _lib.SchnetCfg()
+    cfg.n_atom_basis, cfg.n_interactions, cfg.n_rbf, cfg.max_z = F, L, R, max_z
+    cfg.cutoff, cfg.rbf_coeff = cutoff, -0.5 / (cutoff / (R - 1)) ** 2
+    return cfg
+
+
+def test_schnet_workspace_and_lookup(lib):
+    """nq_schnet_ws_lookup: every named buffer lies inside nq_schnet_workspace_bytes, 16-byte aligned, no two overlap; the failures fail."""
+    F, L, N, E, B = 64, 2, 100, 900, 4
+    c = _schnet_cfg(F, L, 20)
+    cfg = C.byref(c)
+    total = lib.nq_schnet_workspace_bytes(cfg, N, E, B)
+    assert total > 0 and total % 16 == 0
+    off, cnt = C.c_size_t(), C.c_size_t()
+    Pn, H = E // 2, F // 2
+    per_layer = {"y": N * F, "m": N * F, "t1": N * F, "u": N * F, "a1": Pn * F, "h2": Pn * F}
+    shared_dual = {"zo": N * H, "gx": N * F, "gu": N * F, "gm": N * F, "gy": N * F, "gh2": Pn * F, "ga1": Pn * F}
+    single = {"e_atom": N, "te_atom": N, "rw": Pn * 32, "order": Pn, "pair_of": E, "pair_slot": Pn, "geomp": 4 * Pn, "td": E, "tdp": Pn, "gd_total": Pn}
+    asked = [("x", l, t, N * F) for l in range(L + 1) for t in (0, 1)]
+    asked += [(k, l, t, n) for k, n in per_layer.items() for l in range(L) for t in (0, 1)]
+    asked += [(k, 0, t, n) for k, n in shared_dual.items() for t in (0, 1)]
+    asked += [(k, 0, 0, n) for k, n in single.items()]
+    spans = []
+    for name, lay, tan, n in asked:
+        assert lib.nq_schnet_ws_lookup(cfg, N, E, B, name.encode(), lay, tan, C.byref(off), C.byref(cnt)) == 0, (name, lay, tan, lib.nq_last_error())
+        assert cnt.value == n, (name, cnt.value, n)
+        assert (off.value + cnt.value) * 4 <= total and off.value % 4 == 0, name
+        spans.append((off.value, off.value + cnt.value, name, lay, tan))
+    spans.sort()
+    for a, b in zip(spans, spans[1:]):
+        assert a[1] <= b[0], (a, b)                                                   # distinct and disjoint
+    where = {(name, lay, tan): a for a, _, name, lay, tan in spans}
+    for name, lay, tan, n in asked:                                                   # the tangent half follows the primal half
+        if tan == 1:
+            assert where[name, lay, 1] == where[name, lay, 0] + n, (name, lay)
+
+    def fails(name, lay, tan, msg):
+        assert lib.nq_schnet_ws_lookup(cfg, N, E, B, name, lay, tan, C.byref(off), C.byref(cnt)) == 2
+        assert msg in lib.nq_last_error(), lib.nq_last_error()
+    fails(b"nonsense", 0, 0, b"unknown workspace buffer")
+    fails(b"x", L + 1, 0, b"out of range")
+    fails(b"x", -1, 0, b"out of range")
+    for name in per_layer:
+        fails(name.encode(), L, 0, b"out of range")
+    for name in single:
+        fails(name.encode(), 0, 1, b"has no tangent half")
+    assert lib.nq_schnet_ws_lookup(None, N, E, B, b"x", 0, 0, C.byref(off), C.byref(cnt)) == 2
+    assert lib.nq_schnet_ws_lookup(cfg, N, E, B, None, 0, 0, C.byref(off), C.byref(cnt)) == 2
+
+
+def test_schnet_refuses_n_rbf_beyond_the_sort_or_lds_before_any_device_work(lib):
+    """nq_k0_sort has 256 bins (n_rbf <= 268) and W1^T must fit 156 KB of LDS (n_rbf <= 156 at F = 256): both are refused by the argument check of
+    nq_schnet_forward / nq_schnet_backward with NQ_ERR_ARG before any device work (so this runs on a host without a GPU), not by the sort after the
+    embedding, the pair kernel and the window kernel were launched.  Skipped where a device is visible: a regression must not enqueue work on host
+    buffers of a shared GPU."""
+    if torch.cuda.is_available():
+        pytest.skip("host-only check: a device is visible")
+    from nabladft_amd import _lib
+    N, E, B = 100, 900, 4
+    host = (C.c_float * 4096)()                                # stands in for every device array: nothing may read it
+    dummy = C.addressof(host)
+    g = _lib.Graph()
+    g.N, g.B, g.E, g.max_mol_atoms = N, B, E, 30
+    for f in ("mol_ptr", "row_ptr", "col", "dst", "rev", "geom", "z", "atom_mol", "lowptr"):
+        setattr(g, f, dummy)
+    for F, R in [(64, 269), (128, 269), (256, 157)]:
+        c = _schnet_cfg(F, 1, R)
+        cfg = C.byref(c)
+        ws_bytes = lib.nq_schnet_workspace_bytes(cfg, N, E, B)
+        assert ws_bytes > 0
+        ws = (C.c_char * 64)()                                 # never touched either: the refusal comes before the workspace is looked at
+        assert lib.nq_schnet_forward(cfg, dummy, dummy, C.byref(g), C.addressof(ws), ws_bytes, dummy, dummy, None) == 2, (F, R)       # NQ_ERR_ARG
+        assert b"n_rbf" in lib.nq_last_error()
+        assert lib.nq_schnet_backward(cfg, dummy, dummy, C.byref(g), C.addressof(ws), ws_bytes, dummy, dummy, dummy, None) == 2, (F, R)
+        assert b"n_rbf" in lib.nq_last_error()
+
+
 def test_unsupported_configs_fail_loudly():
     import nabladft_amd as nq
     kw = dict(rbf={"name": "gaussian"}, envelope={"name": "polynomial", "exponent": 5}, regress_forces=True, direct_forces=False,

@@ -60,7 +60,11 @@ def test_spk_rejects_unbuilt_options():
         spk.GaussianRBF(20, 5.0, trainable=True)
     with pytest.raises(NotImplementedError):
         spk.PaiNN(128, 3, spk.GaussianRBF(20, 5.0), spk.CosineCutoff(5.0), shared_filters=True)
-    pot = spk.NeuralNetworkPotential(spk.PaiNN(64, 1, spk.GaussianRBF(20, 5.0), spk.CosineCutoff(5.0), max_z=10), [spk.PairwiseDistances()],
+    for rep in (spk.PaiNN, spk.SchNet):     # one cutoff for the Gaussians and the cosine: the engine has a single one
+        with pytest.raises(NotImplementedError, match="cutoff"):
+            rep(64, 1, spk.GaussianRBF(20, 5.0), spk.CosineCutoff(4.0))
+        rep(64, 1, spk.GaussianRBF(20, 5.0), spk.CosineCutoff(5.0))
+    pot =spk.NeuralNetworkPotential(spk.PaiNN(64, 1, spk.GaussianRBF(20, 5.0), spk.CosineCutoff(5.0), max_z=10), [spk.PairwiseDistances()],
                                      [spk.Atomwise(n_in=64, output_key="energy"), spk.Forces()])
     names = set(pot.state_dict())
     assert {k for k, _ in S.spk_param_shapes(S.SpkPaiNNConfig(64, 1, 20, 5.0, 10))} <= names
