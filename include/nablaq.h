@@ -89,7 +89,8 @@ int nq_graph_count(const float* pos, const int32_t* mol_ptr, int32_t N, int32_t 
                    void* stream);
 /* Pass 2: fills the CSR arrays (col, dst, rev, geom[E][4], slot2canon, atom_mol[N]) and, if edge_index != NULL,
  * the reference's canonical outputs: edge_index int64[2][E] (row0 = source j, row1 = target i),
- * edge_dist f32[E], edge_vector f32[E][3], id_swap int64[E], neighbors int64[B]. */
+ * edge_dist f32[E], edge_vector f32[E][3], id_swap int64[E], neighbors int64[B].  E == 0 (no pair inside the cutoff): the per-slot
+ * arrays may be NULL, atom_mol and neighbors are still written.  max_mol_atoms above the limit of nq_graph_count: NQ_ERR_MOL_TOO_LARGE. */
 int nq_graph_fill(const float* pos, const int32_t* mol_ptr, int32_t N, int32_t B, int32_t E, int32_t max_mol_atoms, double cutoff,
                   int32_t max_neighbors, const int32_t* row_ptr, const int32_t* lowptr, int32_t* col, int32_t* dst, int32_t* rev,
                   float* geom, int32_t* slot2canon, int32_t* atom_mol, int64_t* edge_index, float* edge_dist, float* edge_vector,

@@ -395,8 +395,9 @@ int nq_graph_fill(const float* pos, const int32_t* mol_ptr, int32_t N, int32_t B
                   int32_t max_neighbors, const int32_t* row_ptr, const int32_t* lowptr, int32_t* col, int32_t* dst, int32_t* rev, float* geom,
                   int32_t* slot2canon, int32_t* atom_mol, int64_t* edge_index, float* edge_dist, float* edge_vector, int64_t* id_swap,
                   int64_t* neighbors, void* stream) {
-  if (!pos || !mol_ptr || !row_ptr || !lowptr || !col || !dst || !rev || !geom || !slot2canon || !atom_mol)
-    return nq_fail(NQ_ERR_ARG, "null argument");
+  if (!pos || !mol_ptr || !row_ptr || !lowptr || !atom_mol || E < 0) return nq_fail(NQ_ERR_ARG, "null argument");
+  // E == 0 (no pair inside the cutoff): no slot is written, the per-slot arrays may be empty; atom_mol and neighbors are still filled
+  if (E > 0 && (!col || !dst || !rev || !geom || !slot2canon)) return nq_fail(NQ_ERR_ARG, "null argument");
   if (edge_index && (!edge_dist || !edge_vector || !id_swap)) return nq_fail(NQ_ERR_ARG, "canonical outputs must be all set or all NULL");
   if ((reinterpret_cast<uintptr_t>(geom) & 15) != 0) return nq_fail(NQ_ERR_ARG, "geom must be 16-byte aligned");
   GraphFillArgs a;

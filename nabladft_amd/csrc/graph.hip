@@ -266,6 +266,9 @@ int nq_graph_count_impl(const float* pos, const int* mol_ptr, int N, int B, int 
 
 int nq_graph_fill_impl(GraphFillArgs args, int B, int max_mol_atoms, hipStream_t st) {
   NQ_PROF(st, "graph_fill");
+  if (max_mol_atoms > NQ_MAX_MOL_ATOMS)
+    return nq_fail(NQ_ERR_MOL_TOO_LARGE, "molecule with %d atoms exceeds NQ_MAX_MOL_ATOMS=%d", max_mol_atoms, NQ_MAX_MOL_ATOMS);
+  if (B <= 0) return nq_fail(NQ_ERR_ARG, "empty batch (B=%d)", B);
   size_t lds = graph_lds_bytes(max_mol_atoms);
   NQ_DYN_LDS(k_graph_fill, lds);
   hipLaunchKernelGGL(k_graph_fill, dim3(B), dim3(GRAPH_THREADS), lds, st, args);

@@ -516,7 +516,9 @@ int nq_adamw_impl(hipStream_t st, float* p, const float* g, float* m, float* v, 
   NQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sqnorm_final, dim3(1), dim3(64), 0, st, scratch, SQN_BLOCKS, scratch + SQN_BLOCKS);
   NQ_LAUNCH_CHECK();
-  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+  // bias corrections in double, as torch takes them (1 - beta ** step in Python): float32 powf leaves 1 - beta2^step off by up to 1e-5 relative at
+  // small steps, 4e-6 in the step size (tests/test_train_ops_gpu.py)
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2 = (float)(1.0 - pow((double)beta2, (double)step));
   hipLaunchKernelGGL(k_adamw, grid1d(count, 256), dim3(256), 0, st, p, g, m, v, count, scratch + SQN_BLOCKS, max_norm, lr, beta1,
                      beta2, eps, wd, bc1, bc2);
   NQ_LAUNCH_CHECK();

@@ -74,13 +74,11 @@ def build_neighbor_list(pos: torch.Tensor, batch: torch.Tensor, z: Optional[torc
         nl.edge_dist = torch.empty(E, device=dev, dtype=torch.float32)
         nl.edge_vector = torch.empty(E, 3, device=dev, dtype=torch.float32)
         nl.id_swap = torch.empty(E, device=dev, dtype=torch.int64)
-    if E > 0:
-        _lib.check(lib.nq_graph_fill(_lib.ptr(pos32), _lib.ptr(mol_ptr), N, B, E, max_n, float(cutoff), int(max_neighbors),
-                                     _lib.ptr(row_ptr), _lib.ptr(lowptr), _lib.ptr(col), _lib.ptr(dst), _lib.ptr(rev), _lib.ptr(geom),
-                                     _lib.ptr(s2c), _lib.ptr(atom_mol), _lib.ptr(nl.edge_index), _lib.ptr(nl.edge_dist),
-                                     _lib.ptr(nl.edge_vector), _lib.ptr(nl.id_swap), _lib.ptr(neighbors), st))
-    else:
-        neighbors.zero_()
+    want = canonical and E > 0           # E == 0: the canonical outputs are empty tensors (NULL pointers), atom_mol and neighbors are still filled
+    _lib.check(lib.nq_graph_fill(_lib.ptr(pos32), _lib.ptr(mol_ptr), N, B, E, max_n, float(cutoff), int(max_neighbors),
+                                 _lib.ptr(row_ptr), _lib.ptr(lowptr), _lib.ptr(col), _lib.ptr(dst), _lib.ptr(rev), _lib.ptr(geom),
+                                 _lib.ptr(s2c), _lib.ptr(atom_mol), _lib.ptr(nl.edge_index if want else None), _lib.ptr(nl.edge_dist if want else None),
+                                 _lib.ptr(nl.edge_vector if want else None), _lib.ptr(nl.id_swap if want else None), _lib.ptr(neighbors), st))
     nl.neighbors = neighbors
     z32 = None if z is None else z.to(device=dev, dtype=torch.int32).contiguous()
     nl.t = dict(pos=pos32, mol_ptr=mol_ptr, row_ptr=row_ptr, lowptr=lowptr, col=col, dst=dst, rev=rev, geom=geom, slot2canon=s2c,
