@@ -770,6 +770,38 @@ int nq_vib_accumulate(void* state, int32_t N, int32_t B, int32_t D, int64_t P, i
 int nq_vib_finish(void* state, int32_t N, int32_t B, int32_t D, int64_t P, void* stream);
 int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t n_lds, int32_t max_m_lds, int32_t max_m, int32_t scale_modes, void* stream);
 
+/* ---- Batched orbital energies: the generalized symmetric eigenproblem H C = S C diag(eps) (csrc/orbitals.hip; entry points added, ABI 17 unchanged) --------
+ * Fills: the `orbital_energies` / `orbital_coefficients` slots that phisnet/nn/neural_network.py:969-993 returns as zeros (every entry point below serves
+ * those lines), plus the HOMO / LUMO figures and the occupied-orbital errors the Hamiltonian papers report beside the matrix MAE.
+ * Layout: B molecules, molecule b has m_b = orb_ptr[b+1] - orb_ptr[b] orbitals, 1 <= m_b <= 1024 (NQ_ERR_MOL_TOO_LARGE above, before any device work),
+ * M = orb_ptr[B], and owns the m_b x m_b row-major block at pack_ptr[b] of every packed array, P = pack_ptr[B] = sum m_b^2 (BlockAssembler's pack_ptr /
+ * mol_orb_ptr).  H and S are float32, or float64 when the flag beside them is set; only their lower triangles (j <= i) are read.  S = NULL: the identity
+ * (the standard problem; the Cholesky and both triangular stages are skipped).  Every other array is float64 unless said otherwise.
+ * `state` is ONE caller-owned device buffer of nq_orb_state_bytes(B, M, P) bytes, 16-byte aligned (0 = bad dimensions, see nq_last_error).
+ * nq_orb_state_layout fills offsets_host[11] with the byte offsets of: header int32[16] = {B, M, P low word, P high word, status (-2: a call came with other
+ * dimensions than nq_orb_init and did nothing), largest m}; orb_ptr int32[B+1]; pack_ptr int64[B+1]; order int32[B] (largest molecule first); status int32[B]
+ * (0 solved, 1 S is not positive definite, 2 QL reached 60 sweeps on one eigenvalue, 3 the molecule's orb_ptr entries in the state are no longer within
+ * 1..1024 orbitals -- the buffer was overwritten after nq_orb_init, which refuses such a batch; nothing else of that molecule is touched); info int32[B] (status 1: the 1-based index of the pivot that was <= 0
+ * or not finite); iters int32[B] (QL sweeps); eps [M] (ascending inside each molecule); coeff [P] (ROW k of a molecule's block = orbital k, C^T S C = I, the
+ * largest-magnitude component of every orbital, the first on ties, positive); work [P]; chol [P] (the factor L of S = L L^T, lower triangle).
+ * nq_orb_init: orb_ptr_host is a HOST array [B+1]; checks it against M and P, builds pack_ptr and order, writes plan_host[2] = {largest m, LDS bytes of the
+ * solve}, synchronises `stream` once.
+ * nq_orb_solve: one launch, one 512-thread workgroup per molecule: Cholesky, A = L^-1 H L^-T symmetrised, Householder tridiagonalisation, implicit-shift QL
+ * (deflation at |e_i| <= 2^-52 (|d_i| + |d_i+1|)), C = L^-T Y.  A molecule with status 1 gets NaN in eps and coeff; the others are untouched by it.  No
+ * atomics: results are bitwise reproducible and do not depend on which other molecules share the batch.
+ * nq_orb_frontier: n_occ int32[B] (device) -> homo = eps[n_occ - 1], lumo = eps[n_occ] (NaN when n_occ = m), gap = lumo - homo; all NaN for n_occ outside 1..m.
+ * nq_orb_compare: a predicted against a target solution of the same batch (two states of the same dimensions, or the same state twice) under a common S ->
+ * out [7][B]: mean |eps - eps^| over the occupied orbitals, the same over all orbitals, mean over the occupied orbitals of |c_k^T S c^_k|, |d homo|, |d lumo|,
+ * |d gap|, min over the occupied orbitals of |c_k^T S c^_k|.  Overwrites the `work` part of state_pred (the full symmetric S).
+ * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
+size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P);
+int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host);
+int nq_orb_init(void* state, size_t state_bytes, const int32_t* orb_ptr_host, int32_t B, int32_t M, int64_t P, int32_t* plan_host, void* stream);
+int nq_orb_solve(void* state, int32_t B, int32_t M, int64_t P, const void* H, int32_t h_f64, const void* S_or_null, int32_t s_f64, void* stream);
+int nq_orb_frontier(void* state, int32_t B, int32_t M, int64_t P, const int32_t* n_occ, double* out_homo, double* out_lumo, double* out_gap, void* stream);
+int nq_orb_compare(void* state_pred, void* state_target, int32_t B, int32_t M, int64_t P, const void* S_or_null, int32_t s_f64, const int32_t* n_occ, double* out,
+                   void* stream);
+
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,
  * row-major behind pair_ptr int64[B+1] (P = pair_ptr[B]).  "head-major" = per molecule [H][n][n] starting at H * pair_ptr[b]: the layout of the attention bias,

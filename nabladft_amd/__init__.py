@@ -22,6 +22,8 @@ Public surface mirrors the reference plugin classes for this path:
                                     MD with the state on the device (md.py; the ase integrators restated, unpinned), relaxation through the device L-BFGS
   nabladft_amd.BatchedVibrations <-> ase.vibrations.Vibrations behind PYGAseInterface.compute_normal_modes (pyg_ase_interface.py:317-334): batched
                                     finite-difference Hessians and a Jacobi eigensolver on the device (vibrations.py; restated, unpinned)
+  nabladft_amd.BatchedOrbitals / OrbitalErrors <-> the orbital_energies / orbital_coefficients slots phisnet/nn/neural_network.py:969-993 returns as zeros:
+                                    batched generalized symmetric eigensolver on the device (orbitals.py; no reference code, tested against numpy)
   nabladft_amd.spk.*            <-> the schnetpack classes config/model/{painn,schnet}.yaml instantiate (parity unpinned)
   nabladft_amd.read_energy_database / ArenaLoader <-> PyGNablaDFT.process + DataLoader collate (dataset/pyg_datasets.py:101-109)
 """
@@ -41,7 +43,9 @@ from . import md  # noqa: F401
 from .md import BatchedMD, PYGAseInterface  # noqa: F401
 from . import vibrations  # noqa: F401
 from .vibrations import BatchedVibrations  # noqa: F401
+from . import orbitals  # noqa: F401
+from .orbitals import BatchedOrbitals, OrbitalErrors, OrbitalState, occupied_counts  # noqa: F401
 from .data import ArenaLoader, ConformerArena, HamiltonianBatch, HamiltonianDatabase, HamiltonianDataset, hamiltonian_batch, read_energy_database  # noqa: F401
 
 __all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "DimeNetPlusPlusForceLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
-           "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "BatchedVibrations", "PYGAseInterface"]
+           "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "BatchedVibrations", "PYGAseInterface", "BatchedOrbitals", "OrbitalState", "OrbitalErrors", "occupied_counts"]

@@ -224,6 +224,12 @@ SYMBOLS = {
     "nq_vib_accumulate": (C.c_int, [_P, _I32, _I32, _I32, _I64, _I32, _I32, _P, _I32, _I64, _P]),
     "nq_vib_finish": (C.c_int, [_P, _I32, _I32, _I32, _I64, _P]),
     "nq_vib_eigh": (C.c_int, [_P, _I32, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _P]),
+    "nq_orb_state_bytes": (_SZ, [_I32, _I32, _I64]),
+    "nq_orb_state_layout": (C.c_int, [_I32, _I32, _I64, C.POINTER(_SZ)]),
+    "nq_orb_init": (C.c_int, [_P, _SZ, _P, _I32, _I32, _I64, C.POINTER(C.c_int32), _P]),
+    "nq_orb_solve": (C.c_int, [_P, _I32, _I32, _I64, _P, _I32, _P, _I32, _P]),
+    "nq_orb_frontier": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P]),
+    "nq_orb_compare": (C.c_int, [_P, _P, _I32, _I32, _I64, _P, _I32, _P, _P, _P]),
     "nq_g3d_max_mol_atoms": (C.c_int32, []),
     "nq_g3d_pair_forward": (C.c_int, [_P] * 9 + [_I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "nq_g3d_pair_scratch_floats": (_SZ, [_I32, _I64, _I32]),

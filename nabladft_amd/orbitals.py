@@ -1,0 +1,291 @@
+"""Batched orbital energies on the GPU: the generalized symmetric eigenproblem ``H C = S C diag(eps)`` of every molecule of a batch in one launch
+(csrc/orbitals.hip, ``nq_orb_*`` of include/nablaq.h).
+
+Fills what the reference leaves empty: ``phisnet/nn/neural_network.py:969-993`` returns ``orbital_energies`` and ``orbital_coefficients`` as zeros.  Parity
+status: **no reference code to pin against** -- the kernels are tested against a float64 numpy restatement of the textbook route (tests/orbitals_ref.py:
+``np.linalg.cholesky``, two triangular solves, ``np.linalg.eigh``, back substitution).
+
+Algorithm (float64 throughout, one 512-thread workgroup per molecule, no atomics, no host round trip): Cholesky ``S = L L^T``; ``A = L^-1 H L^-T``
+symmetrised; Householder tridiagonalisation; implicit-shift QL with the vectors accumulated row-wise; ``C = L^-T Y``.  Only the lower triangles of ``H`` and
+``S`` are read.  ``S = None`` is the standard problem.  Results: ``eps`` ascending inside each molecule; ``coeff`` packed like the input, ROW k of a
+molecule's block = orbital k (``C^T S C = I``; the largest-magnitude component of every orbital, the first on ties, is positive).  ``per_molecule()`` hands
+the user orbitals as COLUMNS, the convention of ``scipy.linalg.eigh``.
+
+No gradient flows through the solver: inputs are detached.  (Gradients of an eigen-decomposition are out of scope; a loss on orbital energies needs them.)
+
+Limits (each raises, nothing degrades silently): 1..``MAX_ORBITALS`` = 1024 orbitals per molecule; closed shells only (``occupied_counts`` refuses an odd
+electron count); MI355X only, no CPU path.
+"""
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_ORBITALS = 1024
+MAX_QL_SWEEPS = 60            # per eigenvalue (NQ_ORB_MAX_ITER of csrc/orbitals.hip)
+FIGURES = ("eps_mae_occ", "eps_mae_all", "psi_sim_occ", "homo_abs_err", "lumo_abs_err", "gap_abs_err", "psi_sim_min_occ")
+_PARTS = ("header", "orb_ptr", "pack_ptr", "order", "status", "info", "iters", "eps", "coeff", "work", "chol")
+
+
+def _host_ptr(p) -> np.ndarray:
+    if isinstance(p, torch.Tensor):
+        p = p.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(p, dtype=np.int64).reshape(-1))
+
+
+def _orb_ptr_of(plan_or_orb_ptr) -> np.ndarray:
+    """``orb_ptr`` [B+1] on the host from a ``BlockAssembler`` / ``IrrepsAssembler`` plan (its ``mol_orb_ptr``; one small device->host copy) or from the array."""
+    src = getattr(plan_or_orb_ptr, "mol_orb_ptr", plan_or_orb_ptr)
+    return _host_ptr(src)
+
+
+def occupied_counts(z, ptr, charge=0, orb_ptr=None) -> torch.Tensor:
+    """Doubly occupied orbitals per molecule, int32 [B] on the host: ``(sum Z - charge) / 2``.  ``charge``: one number or one per molecule.  Raises
+    ``ValueError`` (on the host, before any device work) for an odd electron count or a count below 1, and, given the batch's ``orb_ptr`` (or a plan), for
+    ``n_occ > m``; ``BatchedOrbitals.frontier`` and ``OrbitalErrors.update`` check that upper end again against the orbitals they solved."""
+    zz, pp = _host_ptr(z), _host_ptr(ptr)
+    B = pp.shape[0] - 1
+    ch = np.broadcast_to(np.asarray(charge, dtype=np.int64), (B,))
+    ne = np.add.reduceat(zz, pp[:-1])[:B] - ch if B > 0 else np.zeros(0, dtype=np.int64)
+    if np.any(np.diff(pp) < 1):
+        raise ValueError("occupied_counts: a molecule without atoms")
+    if np.any(ne % 2 != 0):
+        b = int(np.nonzero(ne % 2)[0][0])
+        raise ValueError(f"occupied_counts: molecule {b} has {int(ne[b])} electrons: open shells are not built")
+    if np.any(ne < 2):
+        b = int(np.nonzero(ne < 2)[0][0])
+        raise ValueError(f"occupied_counts: molecule {b} has {int(ne[b])} electrons: n_occ must be in 1..m")
+    no = (ne // 2).astype(np.int32)
+    if orb_ptr is not None:
+        check_occupied(no, _orb_ptr_of(orb_ptr))
+    return torch.from_numpy(no)
+
+
+def check_occupied(n_occ, orb_ptr) -> np.ndarray:
+    """``n_occ`` [B] against the orbital counts of ``orb_ptr``: ``ValueError`` on the host unless ``1 <= n_occ <= m`` for every molecule.  -> int32 array."""
+    no = _host_ptr(n_occ).astype(np.int32)
+    m = np.diff(_host_ptr(orb_ptr))
+    if no.shape != m.shape:
+        raise ValueError(f"n_occ has {no.shape[0]} entries for {m.shape[0]} molecules")
+    bad = np.nonzero((no < 1) | (no > m))[0]
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError(f"molecule {b}: n_occ={int(no[b])} outside 1..m={int(m[b])}")
+    return no
+
+
+def _failure_text(b: int, status: int, info: int, m: int) -> str:
+    """What a non-zero ``status[b]`` means (include/nablaq.h)."""
+    if status == 1:
+        return f"molecule {b}: the overlap matrix is not positive definite (Cholesky pivot {info} of {m} is <= 0 or not finite)"
+    if status == 2:
+        return f"molecule {b}: the QL iteration did not converge in {MAX_QL_SWEEPS} sweeps on one eigenvalue"
+    return f"molecule {b}: the state buffer no longer holds the batch nq_orb_init prepared (status {status}): it was overwritten"
+
+
+def _require_gpu(t: torch.Tensor):
+    if not t.is_cuda:
+        raise RuntimeError("MI355X only: nabladft_amd.orbitals has no CPU path, move the matrices to cuda")
+
+
+def _packed(t: torch.Tensor, P: int, name: str) -> torch.Tensor:
+    _require_gpu(t)
+    t = t.detach()
+    if t.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{name} must be float32 or float64, not {t.dtype}")
+    if t.numel() != P:
+        raise ValueError(f"{name} has {t.numel()} entries, the plan packs {P}")
+    return t.reshape(-1).contiguous()
+
+
+class OrbitalState:
+    """One caller-owned device buffer behind ``nq_orb_*`` plus typed views of its parts: ``eps`` f64 [M], ``coeff`` f64 [P] (row k of a block = orbital k),
+    ``status`` / ``info`` / ``iters`` int32 [B] (include/nablaq.h)."""
+
+    def __init__(self, orb_ptr, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("MI355X only: nabladft_amd.orbitals has no CPU path")
+        lib = _lib.load()
+        op = _orb_ptr_of(orb_ptr)
+        if op.shape[0] < 2:
+            raise ValueError("orb_ptr needs at least one molecule")
+        m = np.diff(op)
+        if int(m.max()) > MAX_ORBITALS:
+            b = int(m.argmax())
+            raise _lib.NablaqError(_lib.NQ_ERR_MOL_TOO_LARGE, f"molecule {b} has {int(m[b])} orbitals, the limit is {MAX_ORBITALS}")
+        if int(m.min()) < 1:
+            raise ValueError(f"molecule {int(m.argmin())} has {int(m.min())} orbitals")
+        self.orb_ptr_host = op
+        self.pack_ptr_host = np.concatenate([[0], np.cumsum(m * m)]).astype(np.int64)
+        self.m = m
+        self.B, self.M, self.P = int(m.shape[0]), int(op[-1]), int(self.pack_ptr_host[-1])
+        self._dims = (self.B, self.M, self.P)
+        nbytes = lib.nq_orb_state_bytes(*self._dims)
+        if nbytes == 0:
+            raise _lib.NablaqError(_lib.NQ_ERR_ARG, lib.nq_last_error().decode(errors="replace"))
+        off = (C.c_size_t * len(_PARTS))()
+        _lib.check(lib.nq_orb_state_layout(*self._dims, off))
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        op32 = np.ascontiguousarray(op.astype(np.int32))
+        out = (C.c_int32 * 2)()
+        with torch.cuda.device(device):
+            _lib.check(lib.nq_orb_init(_lib.ptr(self.buf), nbytes, op32.ctypes.data_as(C.c_void_p), *self._dims, out, _lib.stream_ptr()))
+        self.max_m = int(out[0])
+        B, M, P = self._dims
+        shapes = {"header": (torch.int32, (16,)), "orb_ptr": (torch.int32, (B + 1,)), "pack_ptr": (torch.int64, (B + 1,)), "order": (torch.int32, (B,)),
+                  "status": (torch.int32, (B,)), "info": (torch.int32, (B,)), "iters": (torch.int32, (B,)), "eps": (torch.float64, (M,)),
+                  "coeff": (torch.float64, (P,)), "work": (torch.float64, (P,)), "chol": (torch.float64, (P,))}
+        for i, name in enumerate(_PARTS):
+            dtype, shape = shapes[name]
+            count = int(np.prod(shape))
+            size = torch.empty(0, dtype=dtype).element_size()
+            setattr(self, name if name != "header" else "header_dev", self.buf[off[i]:off[i] + count * size].view(dtype).view(shape))
+
+    def solve(self, H_packed: torch.Tensor, S_packed: Optional[torch.Tensor] = None):
+        H = _packed(H_packed, self.P, "H_packed")
+        S = None if S_packed is None else _packed(S_packed, self.P, "S_packed")
+        if H.device != self.buf.device or (S is not None and S.device != self.buf.device):
+            raise ValueError(f"the matrices must live on {self.buf.device}")
+        with torch.cuda.device(self.buf.device):
+            _lib.check(_lib.load().nq_orb_solve(_lib.ptr(self.buf), *self._dims, _lib.ptr(H), int(H.dtype == torch.float64), _lib.ptr(S),
+                                                int(S is not None and S.dtype == torch.float64), _lib.stream_ptr()))
+
+    def header(self) -> dict:
+        """The header words (one small device->host copy, synchronises the stream); raises if a call was refused on the device."""
+        h = self.header_dev.cpu().tolist()
+        if h[4] == -2:
+            raise RuntimeError("an nq_orb call came with other dimensions than nq_orb_init prepared the state for")
+        return dict(B=h[0], M=h[1], P=(h[2] & 0xffffffff) + (h[3] << 32), status=h[4], max_m=h[5])
+
+
+class BatchedOrbitals:
+    """Orbital energies and coefficients of every molecule of a batch.
+
+    ``BatchedOrbitals(orb_ptr)``: ``orb_ptr`` [B+1] (host array or tensor), or a ``BlockAssembler`` / ``IrrepsAssembler`` plan (its ``mol_orb_ptr``).
+    ``solve(H_packed, S_packed=None)`` launches the solver on the current stream and returns ``self``; nothing is read back.  ``energies`` [M] and
+    ``coefficients`` [P] stay on the device (float64; row k of a molecule's block = orbital k).  ``per_molecule()`` -> (list of [m], list of [m, m] with the
+    orbitals as columns).  ``frontier(n_occ)`` -> (homo, lumo, gap), float64 [B] on the device.  ``check()`` reads the status once (a host synchronisation)
+    and raises ``RuntimeError`` naming the molecule and the pivot where S was not positive definite.  Inputs are detached: no gradient flows through."""
+
+    def __init__(self, orb_ptr, device="cuda"):
+        self.state = OrbitalState(orb_ptr, device)
+
+    def solve(self, H_packed: torch.Tensor, S_packed: Optional[torch.Tensor] = None) -> "BatchedOrbitals":
+        self.state.solve(H_packed, S_packed)
+        return self
+
+    energies = property(lambda self: self.state.eps)
+    coefficients = property(lambda self: self.state.coeff)
+    status = property(lambda self: self.state.status)
+    info = property(lambda self: self.state.info)
+    iters = property(lambda self: self.state.iters)
+    orb_ptr = property(lambda self: self.state.orb_ptr_host)
+    pack_ptr = property(lambda self: self.state.pack_ptr_host)
+
+    def per_molecule(self):
+        st = self.state
+        eps = [st.eps[int(a):int(b)] for a, b in zip(st.orb_ptr_host[:-1], st.orb_ptr_host[1:])]
+        coeff = [st.coeff[int(a):int(b)].view(int(m), int(m)).t() for a, b, m in zip(st.pack_ptr_host[:-1], st.pack_ptr_host[1:], st.m)]
+        return eps, coeff
+
+    def dense_coefficients(self, dtype=torch.float64) -> torch.Tensor:
+        """Block-diagonal [M, M] with the orbitals as COLUMNS of each molecule's block (the layout of PhiSNet's ``orbital_coefficients``); no host read."""
+        st, dev = self.state, self.state.buf.device
+        m = torch.from_numpy(st.m).to(dev)
+        b = torch.repeat_interleave(torch.arange(st.B, device=dev), m * m, output_size=st.P)
+        loc = torch.arange(st.P, device=dev) - st.pack_ptr[b]
+        o = st.orb_ptr.long()[b]
+        dense = torch.zeros(st.M, st.M, dtype=dtype, device=dev)
+        dense[o + loc % m[b], o + loc // m[b]] = st.coeff.to(dtype)
+        return dense
+
+    def frontier(self, n_occ):
+        st = self.state
+        no = torch.from_numpy(check_occupied(n_occ, st.orb_ptr_host)).to(st.buf.device)
+        out = torch.empty(3, st.B, dtype=torch.float64, device=st.buf.device)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_frontier(_lib.ptr(st.buf), *st._dims, _lib.ptr(no), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream_ptr()))
+        return out[0], out[1], out[2]
+
+    def compare(self, target: "BatchedOrbitals", n_occ, S_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """This (predicted) solution against ``target`` under the common ``S`` -> float64 [7, B] on the device, rows in the order of ``FIGURES``."""
+        st, tt = self.state, target.state
+        if st._dims != tt._dims or not np.array_equal(st.orb_ptr_host, tt.orb_ptr_host):
+            raise ValueError("the two solutions belong to different batches")
+        no = torch.from_numpy(check_occupied(n_occ, st.orb_ptr_host)).to(st.buf.device)
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        out = torch.empty(len(FIGURES), st.B, dtype=torch.float64, device=st.buf.device)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_compare(_lib.ptr(st.buf), _lib.ptr(tt.buf), *st._dims, _lib.ptr(S), int(S is not None and S.dtype == torch.float64),
+                                                  _lib.ptr(no), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def check(self) -> "BatchedOrbitals":
+        st = self.state
+        st.header()
+        status = st.status.cpu().numpy()
+        bad = np.nonzero(status)[0]
+        if bad.size:
+            b = int(bad[0])
+            raise RuntimeError(_failure_text(b, int(status[b]), int(st.info[b]), int(st.m[b])))
+        return self
+
+
+class OrbitalErrors:
+    """The orbital figures of a test loop, accumulated over batches: for QHNet ``update(net(batch, packed=True), asm.pack_targets(plan, batch.hamiltonian),
+    asm.pack_targets(plan, batch.overlap), plan, batch.z, batch.ptr)``; for PhiSNet the ``*_packed`` results and targets with ``results["plan"]``.
+
+    ``update`` solves the predicted and the target Hamiltonian under the common overlap (``None``: the identity) and adds the seven per-molecule figures of
+    ``FIGURES`` to running sums on the device; nothing is read back.  It also keeps, on the device, the status words of both solves of every batch (a few
+    integers per molecule; the solver states themselves are released).  ``compute()`` reads them first and raises ``RuntimeError`` naming the batch (in
+    the order of the ``update`` calls), the molecule and, for an overlap that is not positive definite, the Cholesky pivot -- for a failure in ANY batch
+    since the last ``reset()``, so a mean is never taken over a silent subset.  Otherwise -> dict of the means over all molecules seen (one host read).
+    ``lumo_abs_err`` / ``gap_abs_err`` average over the molecules that have a virtual orbital.  No gradient flows through."""
+
+    def __init__(self, charge=0):
+        self.charge = charge
+        self.reset()
+
+    def reset(self):
+        self._sum = None
+        self._count = None
+        self._flags = []          # per update: int32 [2, 2, B] on the device = (predicted, target) x (status, info), and the two header status words
+
+    def update(self, pred_packed, target_packed, overlap_packed, plan_or_orb_ptr, z, ptr):
+        _require_gpu(pred_packed)
+        op = _orb_ptr_of(plan_or_orb_ptr)
+        n_occ = check_occupied(occupied_counts(z, ptr, self.charge), op)
+        pred = BatchedOrbitals(op, pred_packed.device).solve(pred_packed, overlap_packed)
+        targ = BatchedOrbitals(op, pred_packed.device).solve(target_packed, overlap_packed)
+        figs = pred.compare(targ, n_occ, overlap_packed)
+        ok = ~torch.isnan(figs)
+        if self._sum is None:
+            self._sum = torch.zeros(len(FIGURES), dtype=torch.float64, device=figs.device)
+            self._count = torch.zeros(len(FIGURES), dtype=torch.float64, device=figs.device)
+        self._sum += torch.where(ok, figs, torch.zeros_like(figs)).sum(1)
+        self._count += ok.sum(1).to(torch.float64)
+        flags = torch.stack([torch.stack([o.state.status, o.state.info]) for o in (pred, targ)])       # copies: the states go away with this call
+        self._flags.append((flags, torch.stack([pred.state.header_dev[4], targ.state.header_dev[4]]), pred.state.m))
+        return self
+
+    def compute(self) -> dict:
+        if self._sum is None:
+            raise RuntimeError("OrbitalErrors.compute() before any update()")
+        for i, (flags, hdr, m) in enumerate(self._flags):
+            flags, hdr = flags.cpu().numpy(), hdr.cpu().tolist()
+            for side, name in enumerate(("predicted", "target")):
+                if hdr[side] == -2:
+                    raise RuntimeError(f"batch {i}, {name} Hamiltonian: an nq_orb call came with other dimensions than nq_orb_init prepared the state for")
+                bad = np.nonzero(flags[side, 0])[0]
+                if bad.size:
+                    b = int(bad[0])
+                    raise RuntimeError(f"batch {i}, {name} Hamiltonian, " + _failure_text(b, int(flags[side, 0, b]), int(flags[side, 1, b]), int(m[b])))
+        mean = (self._sum / self._count).cpu().tolist()
+        return dict(zip(FIGURES, mean))
+
+
+__all__ = ["BatchedOrbitals", "OrbitalState", "OrbitalErrors", "occupied_counts", "check_occupied", "MAX_ORBITALS", "FIGURES"]

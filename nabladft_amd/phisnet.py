@@ -580,6 +580,7 @@ class NeuralNetwork(nn.Module):
         self.calculate_full_hamiltonian = self.calculate_core_hamiltonian = self.calculate_overlap_matrix = True
         self.calculate_energy = self.predict_energy = self.calculate_forces = False
         self.create_graph = True                       # neural_network.py:93; forces need False here (first-order adjoints only)
+        self.calculate_orbitals = False                # opt-in: fill orbital_energies / orbital_coefficients (neural_network.py:969-993 leaves them zero)
         self.max_orbitals, self.order, self.num_features, self.num_basis_functions = max_orbitals, order, num_features, num_basis_functions
         self.num_modules, self.cutoff, self.activation, self.Zmax = num_modules, cutoff, activation, Zmax
         order_max = max(l for orbs in max_orbitals for _, l in orbs)
@@ -785,8 +786,16 @@ class NeuralNetwork(nn.Module):
                 results["forces"] = -torch.autograd.grad(torch.sum(results["energy"]), R, create_graph=False, retain_graph=grad_was_enabled)[0]   # keep the graph only for a caller who will backpropagate through the other outputs
         else:
             results["forces"] = torch.zeros_like(R)
-        results["orbital_energies"] = torch.zeros(1, norb, device=R.device, dtype=R.dtype)
-        results["orbital_coefficients"] = torch.zeros(1, norb, norb, device=R.device, dtype=R.dtype)
+        if getattr(self, "calculate_orbitals", False) and self.calculate_full_hamiltonian:
+            # H C = S C diag(eps) of every molecule on the device (orbitals.py); S = None (the identity) when the overlap head is off.  Detached: no gradient.
+            from .orbitals import BatchedOrbitals
+            orb = BatchedOrbitals(plan, R.device).solve(results["full_hamiltonian_packed"], results.get("overlap_matrix_packed"))
+            results["orbital_energies"] = orb.energies.to(R.dtype).view(1, norb)
+            results["orbital_coefficients"] = orb.dense_coefficients(R.dtype).unsqueeze(0)      # block-diagonal, the orbitals as columns of each block
+            results["orbitals"] = orb                                                            # the float64 solution, its status and iteration counts
+        else:
+            results["orbital_energies"] = torch.zeros(1, norb, device=R.device, dtype=R.dtype)
+            results["orbital_coefficients"] = torch.zeros(1, norb, norb, device=R.device, dtype=R.dtype)
         results["plan"] = plan
         return results
 
