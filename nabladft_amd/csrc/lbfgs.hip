@@ -1,7 +1,7 @@
 // Batched L-BFGS for the geometry-optimisation job (nablaDFT/optimization/optimizers.py:437-605, the branch without line search), whole state on the device.
 //
-// One launch per optimiser step (k_lbfgs_step).  A molecule is owned by one wavefront (<= NQ_LBFGS_SMALL atoms, four molecules per 256-thread workgroup) or
-// by one workgroup (up to NQ_LBFGS_MAX atoms); a lane owns whole atoms (3 / 2 per lane), so the per-atom quantities -- force norms, step lengths, the
+// One launch per optimiser step (k_lbfgs_step).  A molecule is owned by one wavefront (<= NQ_MOL_SMALL atoms, four molecules per 256-thread workgroup) or
+// by one workgroup (up to NQ_MOL_MAX atoms); a lane owns whole atoms (3 / 2 per lane), so the per-atom quantities -- force norms, step lengths, the
 // fixed-atom mask -- never cross lanes and q / z of the two-loop recursion live in registers.  The only cross-lane traffic is the dot product of each history
 // entry: a 64-lane xor butterfly (wavefront path: no LDS, no barrier) plus, for the workgroup path, four partial sums through LDS added in a fixed order.  The
 // reduction tree of a molecule depends on its own atom count alone, never on the batch or on the launch geometry, and there is no floating-point atomic:
@@ -14,35 +14,20 @@
 #include <vector>
 
 #include "../../include/nablaq.h"
-#include "common.h"
+#include "devstate.h"
 
-#define NQ_LBFGS_SMALL 192      // 64 lanes x 3 atoms
-#define NQ_LBFGS_MAX 512        // 256 threads x 2 atoms (the project's molecule limit)
 #define NQ_LBFGS_MAX_MEMORY 1024
 #define NQ_LBFGS_HDR 16
 
 enum { H_ITER = 0, H_UNCONV, H_LATCH, H_NORM, H_N, H_B, H_MEM, H_NSMALL, H_ACC, H_TICKET };
 
-struct LbfgsLayout {
-  size_t hdr, mol_ptr, order, conv, rho, r, r0, f0, S, Y, total;
-};
+enum { LP_HDR = 0, LP_MOL_PTR, LP_ORDER, LP_CONV, LP_RHO, LP_R, LP_R0, LP_F0, LP_S, LP_Y, LP_PARTS };
+typedef NqStateLayout<LP_PARTS> LbfgsLayout;
 
 static LbfgsLayout lbfgs_layout(long N, long B, long memory) {
-  LbfgsLayout L;
-  auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  size_t o = 0;
-  L.hdr = o; o = up(o + NQ_LBFGS_HDR * 4);
-  L.mol_ptr = o; o = up(o + (B + 1) * 4);
-  L.order = o; o = up(o + B * 4);
-  L.conv = o; o = up(o + B * 4);
-  L.rho = o; o = up(o + (size_t)memory * B * 8);
-  L.r = o; o = up(o + (size_t)N * 24);
-  L.r0 = o; o = up(o + (size_t)N * 24);
-  L.f0 = o; o = up(o + (size_t)N * 24);
-  L.S = o; o = up(o + (size_t)memory * N * 24);
-  L.Y = o; o = up(o + (size_t)memory * N * 24);
-  L.total = o;
-  return L;
+  const size_t row = (size_t)N * 24, hist = (size_t)memory * N * 24;
+  const size_t bytes[LP_PARTS] = {NQ_LBFGS_HDR * 4, (size_t)(B + 1) * 4, (size_t)B * 4, (size_t)B * 4, (size_t)memory * B * 8, row, row, row, hist, hist};
+  return nq_state_layout(bytes);
 }
 
 struct LbfgsArgs {
@@ -53,31 +38,6 @@ struct LbfgsArgs {
   double fmax2, maxstep, damping, H0;
   int N, B, memory, n_small, evaluate_only;
 };
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);   // pairwise butterfly: every lane ends with the same bits
-  return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
-// BLOCK: four wavefronts own the molecule; their partial results meet in red[2][4] (alternating halves: one barrier per reduction) and are combined 0,1,2,3.
-template <bool BLOCK, bool MAX>
-__device__ __forceinline__ double mol_reduce(double v, double* red, int& parity) {
-  v = MAX ? wave_max_f64(v) : wave_sum_f64(v);
-  if (BLOCK) {
-    double* buf = red + parity * 4;
-    if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = MAX ? fmax(fmax(buf[0], buf[1]), fmax(buf[2], buf[3])) : ((buf[0] + buf[1]) + (buf[2] + buf[3]));
-    parity ^= 1;
-  }
-  return v;
-}
 
 template <int APL>
 __device__ __forceinline__ void load_row(const double* base, const int (&off)[APL], const bool (&act)[APL], double (&v)[APL][3]) {
@@ -124,12 +84,12 @@ __device__ __forceinline__ void lbfgs_molecule(const LbfgsArgs& A, int b, int t,
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       double v = 0.0;
-      if (live) v = A.forces_f64 ? ((const double*)A.forces)[off[k] + c] : (double)((const float*)A.forces)[off[k] + c];
+      if (live) v = nq_load_f64(A.forces, off[k] + c, A.forces_f64);
       f[k][c] = v;
     }
     fn2 = fmax(fn2, f[k][0] * f[k][0] + f[k][1] * f[k][1] + f[k][2] * f[k][2]);
   }
-  fn2 = mol_reduce<BLOCK, true>(fn2, red, parity);
+  fn2 = nq_mol_reduce<BLOCK, true>(fn2, red, parity);
   const bool conv = fn2 < A.fmax2;
   if (t == 0) {
     A.conv[b] = conv ? 1 : 0;
@@ -155,7 +115,7 @@ __device__ __forceinline__ void lbfgs_molecule(const LbfgsArgs& A, int b, int t,
         y[k][c] = f0[k][c] - f[k][c];
       }
     }
-    const double ys = mol_reduce<BLOCK, false>(dot_local<APL>(y, s), red, parity);
+    const double ys = nq_mol_reduce<BLOCK, false>(dot_local<APL>(y, s), red, parity);
     rho_cur = rho_new = ys > 1e-8 ? 1.0 / ys : 1.0;
     const int slot = (it - 1) % mem;
     double* Sw = A.S + (size_t)slot * row;
@@ -202,7 +162,7 @@ __device__ __forceinline__ void lbfgs_molecule(const LbfgsArgs& A, int b, int t,
       load_row<APL>(A.Y + (size_t)slot * row, off, act, yn);
       rho_n = A.rho[(size_t)slot * A.B + b];
     }
-    const double a = rho_cur * mol_reduce<BLOCK, false>(dot_local<APL>(s, q), red, parity);
+    const double a = rho_cur * nq_mol_reduce<BLOCK, false>(dot_local<APL>(s, q), red, parity);
     alds[j] = a;
 #pragma unroll
     for (int k = 0; k < APL; ++k) {
@@ -238,7 +198,7 @@ __device__ __forceinline__ void lbfgs_molecule(const LbfgsArgs& A, int b, int t,
       rho_n = j == 1 ? rho_new : A.rho[(size_t)slot * A.B + b];   // the newest rho was stored by lane 0 of this launch: every lane kept its own copy
     }
     const double a = alds[j];
-    const double bb = rho_cur * mol_reduce<BLOCK, false>(dot_local<APL>(y, q), red, parity);
+    const double bb = rho_cur * nq_mol_reduce<BLOCK, false>(dot_local<APL>(y, q), red, parity);
     const double w = a - bb;
 #pragma unroll
     for (int k = 0; k < APL; ++k) {
@@ -265,7 +225,7 @@ __device__ __forceinline__ void lbfgs_molecule(const LbfgsArgs& A, int b, int t,
     for (int c = 0; c < 3; ++c) q[k][c] = -q[k][c];
     longest = fmax(longest, sqrt(q[k][0] * q[k][0] + q[k][1] * q[k][1] + q[k][2] * q[k][2]));
   }
-  longest = mol_reduce<BLOCK, true>(longest, red, parity);
+  longest = nq_mol_reduce<BLOCK, true>(longest, red, parity);
   const bool clamp = longest >= A.maxstep;
   const double scale = clamp ? A.maxstep / longest : 1.0;
   if (clamp && t == 0) atomicAdd(&A.hdr[H_NORM], 1);
@@ -294,7 +254,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_step(LbfgsArgs A) {
   double* red = lds;                                      // [2][4]
   const int wave = threadIdx.x >> 6;
   double* alds = lds + 8 + (size_t)wave * A.memory;       // [4][memory]
-  const int small_blocks = (A.n_small + 3) >> 2;
+  const int small_blocks = nq_small_blocks(A.n_small);
   if (A.hdr[H_N] != A.N || A.hdr[H_B] != A.B || A.hdr[H_MEM] != A.memory || A.hdr[H_NSMALL] != A.n_small) {   // not the state nq_lbfgs_init prepared: touch nothing
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicExch(&A.hdr[H_UNCONV], -2);
     return;
@@ -321,14 +281,6 @@ __global__ __launch_bounds__(256) void k_lbfgs_step(LbfgsArgs A) {
   }
 }
 
-__global__ void k_lbfgs_init_pos(const void* pos, int pos_f64, long count, double* r, float* pos32) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const double v = pos_f64 ? ((const double*)pos)[i] : (double)((const float*)pos)[i];
-  r[i] = v;
-  pos32[i] = (float)v;
-}
-
 static int lbfgs_check_dims(int32_t N, int32_t B, int32_t memory) {
   if (N < 1 || B < 1) return nq_fail(NQ_ERR_ARG, "nq_lbfgs: empty batch (N=%d, B=%d)", N, B);
   if (memory < 1 || memory > NQ_LBFGS_MAX_MEMORY) return nq_fail(NQ_ERR_ARG, "nq_lbfgs: memory=%d out of range [1,%d]", memory, NQ_LBFGS_MAX_MEMORY);
@@ -338,53 +290,34 @@ static int lbfgs_check_dims(int32_t N, int32_t B, int32_t memory) {
 extern "C" {
 
 size_t nq_lbfgs_state_bytes(int32_t N, int32_t B, int32_t memory) {
-  if (lbfgs_check_dims(N, B, memory) != NQ_OK) return 0;
-  return lbfgs_layout(N, B, memory).total;
+  return lbfgs_check_dims(N, B, memory) == NQ_OK ? lbfgs_layout(N, B, memory).total : 0;
 }
 
 int nq_lbfgs_state_layout(int32_t N, int32_t B, int32_t memory, size_t* offsets_host) {
   if (!offsets_host) return nq_fail(NQ_ERR_ARG, "null argument");
   NQ_TRY(lbfgs_check_dims(N, B, memory));
-  const LbfgsLayout L = lbfgs_layout(N, B, memory);
-  const size_t o[10] = {L.hdr, L.mol_ptr, L.order, L.conv, L.rho, L.r, L.r0, L.f0, L.S, L.Y};
-  for (int i = 0; i < 10; ++i) offsets_host[i] = o[i];
-  return NQ_OK;
+  return nq_state_offsets(lbfgs_layout(N, B, memory), offsets_host);
 }
 
 int nq_lbfgs_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, int32_t N, int32_t B, int32_t memory, const void* pos, int32_t pos_f64,
                   float* pos32, int32_t* n_small_host, void* stream) {
   if (!state || !mol_ptr_host || !pos || !pos32 || !n_small_host) return nq_fail(NQ_ERR_ARG, "null argument");
   NQ_TRY(lbfgs_check_dims(N, B, memory));
-  if ((reinterpret_cast<uintptr_t>(state) & 15) != 0) return nq_fail(NQ_ERR_ARG, "nq_lbfgs_init: state must be 16-byte aligned");
   const LbfgsLayout L = lbfgs_layout(N, B, memory);
-  if (state_bytes < L.total) return nq_fail(NQ_ERR_WORKSPACE, "nq_lbfgs_init: state too small: %zu < %zu bytes", state_bytes, L.total);
+  NQ_TRY(nq_state_check("nq_lbfgs_init:", state, state_bytes, L.total));
   if (mol_ptr_host[0] != 0 || mol_ptr_host[B] != N) return nq_fail(NQ_ERR_ARG, "nq_lbfgs_init: mol_ptr must run from 0 to N=%d", N);
-  std::vector<int> small, large;
-  for (int b = 0; b < B; ++b) {
-    const int n = mol_ptr_host[b + 1] - mol_ptr_host[b];
-    if (n < 1) return nq_fail(NQ_ERR_ARG, "nq_lbfgs_init: molecule %d has %d atoms", b, n);
-    if (n > NQ_LBFGS_MAX) return nq_fail(NQ_ERR_MOL_TOO_LARGE, "nq_lbfgs_init: molecule %d has %d atoms, the limit is %d", b, n, NQ_LBFGS_MAX);
-    (n <= NQ_LBFGS_SMALL ? small : large).push_back(b);
-  }
   // header + mol_ptr + order are contiguous up to the converged flags: one host image, one copy
-  std::vector<int> img(L.conv / 4, 0);
-  int* hdr = img.data() + L.hdr / 4;
-  hdr[H_LATCH] = -1; hdr[H_N] = N; hdr[H_B] = B; hdr[H_MEM] = memory; hdr[H_NSMALL] = (int)small.size();
-  for (int b = 0; b <= B; ++b) img[L.mol_ptr / 4 + b] = mol_ptr_host[b];
-  int* order = img.data() + L.order / 4;
-  for (size_t i = 0; i < small.size(); ++i) order[i] = small[i];
-  for (size_t i = 0; i < large.size(); ++i) order[small.size() + i] = large[i];
-  *n_small_host = (int32_t)small.size();
+  std::vector<int> img(L.part[LP_CONV] / 4, 0);
+  NQ_TRY(nq_partition_molecules(mol_ptr_host, B, NQ_MOL_SMALL, NQ_MOL_MAX, "nq_lbfgs_init:", img.data() + L.part[LP_ORDER] / 4, n_small_host));
+  int* hdr = img.data() + L.part[LP_HDR] / 4;
+  hdr[H_LATCH] = -1; hdr[H_N] = N; hdr[H_B] = B; hdr[H_MEM] = memory; hdr[H_NSMALL] = *n_small_host;
+  for (int b = 0; b <= B; ++b) img[L.part[LP_MOL_PTR] / 4 + b] = mol_ptr_host[b];
   hipStream_t st = (hipStream_t)stream;
-  NQ_HIP(hipMemcpyAsync(state, img.data(), L.conv, hipMemcpyHostToDevice, st));
-  NQ_HIP(hipStreamSynchronize(st));   // the image is a host temporary
+  NQ_TRY(nq_state_upload(state, img.data(), L.part[LP_CONV], st));
   char* base = (char*)state;
-  NQ_HIP(hipMemsetAsync(base + L.conv, 0, (size_t)B * 4, st));
-  const long count = (long)N * 3;
+  NQ_HIP(hipMemsetAsync(base + L.part[LP_CONV], 0, (size_t)B * 4, st));
   NQ_PROF(st, "lbfgs_init");
-  hipLaunchKernelGGL(k_lbfgs_init_pos, dim3(nq_cdiv(count, 256)), dim3(256), 0, st, pos, pos_f64, count, (double*)(base + L.r), pos32);
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  return nq_init_pos_f64(st, pos, pos_f64, nullptr, (long)N * 3, (double*)(base + L.part[LP_R]), nullptr, pos32);
 }
 
 int nq_lbfgs_step(void* state, int32_t N, int32_t B, int32_t memory, int32_t n_small, const void* forces, int32_t forces_f64, const uint8_t* fixed_mask,
@@ -397,17 +330,16 @@ int nq_lbfgs_step(void* state, int32_t N, int32_t B, int32_t memory, int32_t n_s
   const LbfgsLayout L = lbfgs_layout(N, B, memory);
   char* base = (char*)state;
   LbfgsArgs A;
-  A.hdr = (int*)(base + L.hdr); A.mol_ptr = (const int*)(base + L.mol_ptr); A.order = (const int*)(base + L.order); A.conv = (int*)(base + L.conv);
-  A.rho = (double*)(base + L.rho); A.r = (double*)(base + L.r); A.r0 = (double*)(base + L.r0); A.f0 = (double*)(base + L.f0);
-  A.S = (double*)(base + L.S); A.Y = (double*)(base + L.Y);
+  A.hdr = (int*)(base + L.part[LP_HDR]); A.mol_ptr = (const int*)(base + L.part[LP_MOL_PTR]); A.order = (const int*)(base + L.part[LP_ORDER]);
+  A.conv = (int*)(base + L.part[LP_CONV]); A.rho = (double*)(base + L.part[LP_RHO]); A.r = (double*)(base + L.part[LP_R]); A.r0 = (double*)(base + L.part[LP_R0]);
+  A.f0 = (double*)(base + L.part[LP_F0]); A.S = (double*)(base + L.part[LP_S]); A.Y = (double*)(base + L.part[LP_Y]);
   A.forces = forces; A.forces_f64 = forces_f64; A.fixed = fixed_mask; A.pos32 = pos32;
   A.fmax2 = fmax * fmax; A.maxstep = maxstep; A.damping = damping; A.H0 = 1.0 / alpha;
   A.N = N; A.B = B; A.memory = memory; A.n_small = n_small; A.evaluate_only = evaluate_only;
-  const int blocks = ((n_small + 3) >> 2) + (B - n_small);
   const size_t lds = (8 + (size_t)4 * memory) * sizeof(double);
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "lbfgs_step");
-  hipLaunchKernelGGL(k_lbfgs_step, dim3(blocks), dim3(256), lds, st, A);
+  hipLaunchKernelGGL(k_lbfgs_step, dim3(nq_owned_grid(n_small, B)), dim3(256), lds, st, A);
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }

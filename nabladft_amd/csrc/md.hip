@@ -2,8 +2,8 @@
 // _init_velocities: ase VelocityVerlet, Langevin with fix_com, MaxwellBoltzmannDistribution + Stationary + ZeroRotation, FixAtoms), whole state on the device.
 // ase is not part of the reference tree: the equations are restated (nabladft_amd/md.py lists them) and unpinned against ase.
 //
-// One launch per MD step (k_md_step).  Ownership is that of lbfgs.hip: a molecule belongs to one wavefront (<= NQ_MD_SMALL atoms, four molecules per 256-thread
-// workgroup) or to one workgroup (up to NQ_MD_MAX atoms); a lane owns whole atoms (3 / 2 per lane), so positions, velocities, masses and the noise of an atom never
+// One launch per MD step (k_md_step).  Ownership is that of lbfgs.hip: a molecule belongs to one wavefront (<= NQ_MOL_SMALL atoms, four molecules per 256-thread
+// workgroup) or to one workgroup (up to NQ_MOL_MAX atoms); a lane owns whole atoms (3 / 2 per lane), so positions, velocities, masses and the noise of an atom never
 // cross lanes.  The per-molecule sums (centre of the noise, momentum, angular momentum, kinetic energy) go through a 64-lane xor butterfly plus, on the workgroup
 // path, four partial sums through LDS added in a fixed order: the reduction tree of a molecule depends on its own atom count alone, there is no floating-point
 // atomic, and the results are bitwise reproducible and independent of what else shares the batch.
@@ -24,10 +24,8 @@
 #include <vector>
 
 #include "../../include/nablaq.h"
-#include "common.h"
+#include "devstate.h"
 
-#define NQ_MD_SMALL 192      // 64 lanes x 3 atoms
-#define NQ_MD_MAX 512        // 256 threads x 2 atoms (the project's molecule limit)
 #define NQ_MD_HDR 32
 #define NQ_MD_LOGCOLS 8
 #define NQ_MD_RED 9          // widest per-molecule sum (angular momentum + inertia tensor)
@@ -43,30 +41,16 @@ static constexpr double MD_KB = MD_KSI / MD_EH;
 
 enum { M_STEP = 0, M_STATUS, M_PENDING, M_LOGROWS, M_FRAMES, M_OVERFLOW, M_N, M_B, M_NSMALL, M_LOGCAP, M_FRAMECAP, M_FLAGS, M_LASTLOG, M_TICKET };
 
-struct MdLayout {
-  size_t hdr, mol_ptr, order, key, mass, fixed, r, v, rv, log, frames, vframes, total;
-};
+enum { MP_HDR = 0, MP_MOL_PTR, MP_ORDER, MP_KEY, MP_MASS, MP_FIXED, MP_R, MP_V, MP_RV, MP_LOG, MP_FRAMES, MP_VFRAMES, MP_PARTS };
+typedef NqStateLayout<MP_PARTS> MdLayout;
 
 static MdLayout md_layout(long N, long B, long log_cap, long frame_cap, int flags) {
-  MdLayout L;
-  auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  if (!(flags & NQ_MD_FLAG_LOG)) log_cap = 0;
+  if (!(flags & NQ_MD_FLAG_LOG)) log_cap = 0;      // a ring whose flag is off takes no room
   if (!(flags & NQ_MD_FLAG_FRAMES)) frame_cap = 0;
-  size_t o = 0;
-  L.hdr = o; o = up(o + NQ_MD_HDR * 4);
-  L.mol_ptr = o; o = up(o + (B + 1) * 4);
-  L.order = o; o = up(o + B * 4);
-  L.key = o; o = up(o + B * 8);
-  L.mass = o; o = up(o + (size_t)N * 8);
-  L.fixed = o; o = up(o + (size_t)N);
-  L.r = o; o = up(o + (size_t)N * 24);
-  L.v = o; o = up(o + (size_t)N * 24);
-  L.rv = o; o = up(o + (size_t)N * 24);
-  L.log = o; o = up(o + (size_t)log_cap * B * NQ_MD_LOGCOLS * 8);
-  L.frames = o; o = up(o + (size_t)frame_cap * N * 24);
-  L.vframes = o; o = up(o + ((flags & NQ_MD_FLAG_VEL) ? (size_t)frame_cap * N * 24 : 0));
-  L.total = o;
-  return L;
+  const size_t row = (size_t)N * 24, ring = (size_t)frame_cap * N * 24;
+  const size_t bytes[MP_PARTS] = {NQ_MD_HDR * 4, (size_t)(B + 1) * 4, (size_t)B * 4, (size_t)B * 8, (size_t)N * 8, (size_t)N, row, row, row,
+                                  (size_t)log_cap * B * NQ_MD_LOGCOLS * 8, ring, (flags & NQ_MD_FLAG_VEL) ? ring : 0};
+  return nq_state_layout(bytes);
 }
 
 struct MdArgs {
@@ -105,28 +89,10 @@ __device__ __forceinline__ void md_normal_pair(unsigned long long seed, long lon
 }
 
 // ---- per-molecule sums ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double md_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);   // pairwise butterfly: every lane ends with the same bits
-  return v;
-}
-
-// BLOCK: four wavefronts own the molecule; their partial sums meet in red[2][NQ_MD_RED][4] (alternating halves: one barrier per reduction), combined (0+1)+(2+3)
+// every sum of this file shares red[2][NQ_MD_RED][4]
 template <bool BLOCK, int K>
 __device__ __forceinline__ void md_mol_sum(double (&v)[K], double* red, int& parity) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = md_wave_sum(v[k]);
-  if (BLOCK) {
-    double* buf = red + parity * (NQ_MD_RED * 4);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) buf[k * 4 + (threadIdx.x >> 6)] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = (buf[k * 4] + buf[k * 4 + 1]) + (buf[k * 4 + 2] + buf[k * 4 + 3]);
-    parity ^= 1;
-  }
+  nq_mol_reduce<BLOCK, false, K, NQ_MD_RED>(v, red, parity);
 }
 
 // what a lane holds of its molecule
@@ -233,6 +199,8 @@ __device__ __forceinline__ void md_molecule(const MdArgs& A, int b, int t, doubl
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       double f = 0.0;
+      // not nq_load_f64: with one index shared by both arms the compiler addresses the forces with two instructions instead of one, and the step kernel
+      // measured 1 % slower; written out, its code is instruction for instruction what it was
       if (M.act[k]) f = A.forces_f64 ? ((const double*)A.forces)[(size_t)M.idx[k] * 3 + c] : (double)((const float*)A.forces)[(size_t)M.idx[k] * 3 + c];
       acc[k][c] = MD_KAPPA * f / M.m[k];
     }
@@ -292,7 +260,7 @@ __device__ __forceinline__ void md_molecule(const MdArgs& A, int b, int t, doubl
         const double ekin = 0.5 * s2[3] / MD_KAPPA;
         const double dof = 3.0 * s1[4];
         double epot = 0.0;
-        if (A.energies) epot = A.energies_f64 ? ((const double*)A.energies)[b] : (double)((const float*)A.energies)[b];
+        if (A.energies) epot = nq_load_f64(A.energies, b, A.energies_f64);
         double* row = A.log + ((size_t)log_slot * A.B + b) * NQ_MD_LOGCOLS;
         row[0] = (double)step;
         row[1] = epot + ekin;
@@ -370,7 +338,7 @@ __device__ __forceinline__ bool md_header_matches(const MdArgs& A) {
 __global__ __launch_bounds__(256) void k_md_step(MdArgs A) {
   __shared__ double red[2 * NQ_MD_RED * 4];
   const int wave = threadIdx.x >> 6;
-  const int small_blocks = (A.n_small + 3) >> 2;
+  const int small_blocks = nq_small_blocks(A.n_small);
   if (!md_header_matches(A)) {   // not the state nq_md_init prepared: touch nothing
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicExch(&A.hdr[M_STATUS], -2);
     return;
@@ -551,7 +519,7 @@ __device__ __forceinline__ void md_init_vel_molecule(const MdArgs& A, int b, int
 __global__ __launch_bounds__(256) void k_md_init_vel(MdArgs A) {
   __shared__ double red[2 * NQ_MD_RED * 4];
   const int wave = threadIdx.x >> 6;
-  const int small_blocks = (A.n_small + 3) >> 2;
+  const int small_blocks = nq_small_blocks(A.n_small);
   if (!md_header_matches(A)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicExch(&A.hdr[M_STATUS], -2);
     return;
@@ -563,15 +531,6 @@ __global__ __launch_bounds__(256) void k_md_init_vel(MdArgs A) {
     md_init_vel_molecule<2, true>(A, A.order[A.n_small + (blockIdx.x - small_blocks)], threadIdx.x, red);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicExch(&A.hdr[M_PENDING], 0);   // new velocities belong to the current positions: no half-kick is owed
-}
-
-__global__ void k_md_init_state(const void* pos, int pos_f64, const double* vel, long count, double* r, double* v, float* pos32) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  const double x = pos_f64 ? ((const double*)pos)[i] : (double)((const float*)pos)[i];
-  r[i] = x;
-  pos32[i] = (float)x;
-  v[i] = vel ? vel[i] : 0.0;
 }
 
 // one thread per atom: the molecule is found by bisection of mol_ptr
@@ -606,10 +565,10 @@ static MdArgs md_args(void* state, int32_t N, int32_t B, int32_t n_small, int32_
   const MdLayout L = md_layout(N, B, log_cap, frame_cap, flags);
   char* base = (char*)state;
   MdArgs A = {};
-  A.hdr = (int*)(base + L.hdr); A.mol_ptr = (const int*)(base + L.mol_ptr); A.order = (const int*)(base + L.order); A.key = (const long long*)(base + L.key);
-  A.mass = (const double*)(base + L.mass); A.fixed = (const unsigned char*)(base + L.fixed);
-  A.r = (double*)(base + L.r); A.v = (double*)(base + L.v); A.rv = (double*)(base + L.rv); A.log = (double*)(base + L.log);
-  A.frames = (double*)(base + L.frames); A.vframes = (double*)(base + L.vframes);
+  A.hdr = (int*)(base + L.part[MP_HDR]); A.mol_ptr = (const int*)(base + L.part[MP_MOL_PTR]); A.order = (const int*)(base + L.part[MP_ORDER]);
+  A.key = (const long long*)(base + L.part[MP_KEY]); A.mass = (const double*)(base + L.part[MP_MASS]); A.fixed = (const unsigned char*)(base + L.part[MP_FIXED]);
+  A.r = (double*)(base + L.part[MP_R]); A.v = (double*)(base + L.part[MP_V]); A.rv = (double*)(base + L.part[MP_RV]); A.log = (double*)(base + L.part[MP_LOG]);
+  A.frames = (double*)(base + L.part[MP_FRAMES]); A.vframes = (double*)(base + L.part[MP_VFRAMES]);
   A.N = N; A.B = B; A.n_small = n_small; A.flags = flags;
   A.log_cap = (flags & NQ_MD_FLAG_LOG) ? log_cap : 0;
   A.frame_cap = (flags & NQ_MD_FLAG_FRAMES) ? frame_cap : 0;
@@ -627,17 +586,13 @@ int nq_md_constants(double* kappa_kb_host) {
 }
 
 size_t nq_md_state_bytes(int32_t N, int32_t B, int32_t log_cap, int32_t frame_cap, int32_t flags) {
-  if (md_check_dims(N, B, log_cap, frame_cap, flags) != NQ_OK) return 0;
-  return md_layout(N, B, log_cap, frame_cap, flags).total;
+  return md_check_dims(N, B, log_cap, frame_cap, flags) == NQ_OK ? md_layout(N, B, log_cap, frame_cap, flags).total : 0;
 }
 
 int nq_md_state_layout(int32_t N, int32_t B, int32_t log_cap, int32_t frame_cap, int32_t flags, size_t* offsets_host) {
   if (!offsets_host) return nq_fail(NQ_ERR_ARG, "null argument");
   NQ_TRY(md_check_dims(N, B, log_cap, frame_cap, flags));
-  const MdLayout L = md_layout(N, B, log_cap, frame_cap, flags);
-  const size_t o[12] = {L.hdr, L.mol_ptr, L.order, L.key, L.mass, L.fixed, L.r, L.v, L.rv, L.log, L.frames, L.vframes};
-  for (int i = 0; i < 12; ++i) offsets_host[i] = o[i];
-  return NQ_OK;
+  return nq_state_offsets(md_layout(N, B, log_cap, frame_cap, flags), offsets_host);
 }
 
 int nq_md_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, const int64_t* mol_key_host, const double* masses_host, const uint8_t* fixed_host,
@@ -645,49 +600,36 @@ int nq_md_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, con
                int32_t* n_small_host, void* stream) {
   if (!state || !mol_ptr_host || !masses_host || !pos || !pos32 || !n_small_host) return nq_fail(NQ_ERR_ARG, "null argument");
   NQ_TRY(md_check_dims(N, B, log_cap, frame_cap, flags));
-  if ((reinterpret_cast<uintptr_t>(state) & 15) != 0) return nq_fail(NQ_ERR_ARG, "nq_md_init: state must be 16-byte aligned");
   const MdLayout L = md_layout(N, B, log_cap, frame_cap, flags);
-  if (state_bytes < L.total) return nq_fail(NQ_ERR_WORKSPACE, "nq_md_init: state too small: %zu < %zu bytes", state_bytes, L.total);
+  NQ_TRY(nq_state_check("nq_md_init:", state, state_bytes, L.total));
   if (mol_ptr_host[0] != 0 || mol_ptr_host[B] != N) return nq_fail(NQ_ERR_ARG, "nq_md_init: mol_ptr must run from 0 to N=%d", N);
-  std::vector<int> small, large;
-  for (int b = 0; b < B; ++b) {
-    const int n = mol_ptr_host[b + 1] - mol_ptr_host[b];
-    if (n < 1) return nq_fail(NQ_ERR_ARG, "nq_md_init: molecule %d has %d atoms", b, n);
-    if (n > NQ_MD_MAX) return nq_fail(NQ_ERR_MOL_TOO_LARGE, "nq_md_init: molecule %d has %d atoms, the limit is %d", b, n, NQ_MD_MAX);
-    (n <= NQ_MD_SMALL ? small : large).push_back(b);
-  }
+  // header .. fixed mask are contiguous: one host image, one copy
+  std::vector<char> img(L.part[MP_R], 0);
+  int n_small = 0;
+  NQ_TRY(nq_partition_molecules(mol_ptr_host, B, NQ_MOL_SMALL, NQ_MOL_MAX, "nq_md_init:", (int*)(img.data() + L.part[MP_ORDER]), &n_small));
   for (int i = 0; i < N; ++i) {
     if (!(masses_host[i] > 0.0) || !std::isfinite(masses_host[i])) return nq_fail(NQ_ERR_ARG, "nq_md_init: atom %d has mass %g, masses must be positive", i, masses_host[i]);
   }
-  // header .. fixed mask are contiguous: one host image, one copy
-  std::vector<char> img(L.r, 0);
-  int* hdr = (int*)(img.data() + L.hdr);
-  hdr[M_N] = N; hdr[M_B] = B; hdr[M_NSMALL] = (int)small.size(); hdr[M_FLAGS] = flags; hdr[M_LASTLOG] = -1;
+  int* hdr = (int*)(img.data() + L.part[MP_HDR]);
+  hdr[M_N] = N; hdr[M_B] = B; hdr[M_NSMALL] = n_small; hdr[M_FLAGS] = flags; hdr[M_LASTLOG] = -1;
   hdr[M_LOGCAP] = (flags & NQ_MD_FLAG_LOG) ? log_cap : 0;
   hdr[M_FRAMECAP] = (flags & NQ_MD_FLAG_FRAMES) ? frame_cap : 0;
-  int* mp = (int*)(img.data() + L.mol_ptr);
+  int* mp = (int*)(img.data() + L.part[MP_MOL_PTR]);
   for (int b = 0; b <= B; ++b) mp[b] = mol_ptr_host[b];
-  int* order = (int*)(img.data() + L.order);
-  for (size_t i = 0; i < small.size(); ++i) order[i] = small[i];
-  for (size_t i = 0; i < large.size(); ++i) order[small.size() + i] = large[i];
-  long long* key = (long long*)(img.data() + L.key);
+  long long* key = (long long*)(img.data() + L.part[MP_KEY]);
   for (int b = 0; b < B; ++b) key[b] = mol_key_host ? (long long)mol_key_host[b] : (long long)b;
-  double* mass = (double*)(img.data() + L.mass);
-  unsigned char* fixed = (unsigned char*)(img.data() + L.fixed);
+  double* mass = (double*)(img.data() + L.part[MP_MASS]);
+  unsigned char* fixed = (unsigned char*)(img.data() + L.part[MP_FIXED]);
   for (int i = 0; i < N; ++i) {
     mass[i] = masses_host[i];
     fixed[i] = fixed_host && fixed_host[i] ? 1 : 0;
   }
-  *n_small_host = (int32_t)small.size();
+  *n_small_host = n_small;
   hipStream_t st = (hipStream_t)stream;
-  NQ_HIP(hipMemcpyAsync(state, img.data(), L.r, hipMemcpyHostToDevice, st));
-  NQ_HIP(hipStreamSynchronize(st));   // the image is a host temporary
+  NQ_TRY(nq_state_upload(state, img.data(), L.part[MP_R], st));
   char* base = (char*)state;
-  const long count = (long)N * 3;
   NQ_PROF(st, "md_init");
-  hipLaunchKernelGGL(k_md_init_state, dim3(nq_cdiv(count, 256)), dim3(256), 0, st, pos, pos_f64, vel, count, (double*)(base + L.r), (double*)(base + L.v), pos32);
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  return nq_init_pos_f64(st, pos, pos_f64, vel, (long)N * 3, (double*)(base + L.part[MP_R]), (double*)(base + L.part[MP_V]), pos32);
 }
 
 int nq_md_init_velocities(void* state, int32_t N, int32_t B, int32_t n_small, int32_t log_cap, int32_t frame_cap, int32_t flags, double T_init, int64_t seed,
@@ -698,10 +640,9 @@ int nq_md_init_velocities(void* state, int32_t N, int32_t B, int32_t n_small, in
   if (!(T_init >= 0.0) || !std::isfinite(T_init)) return nq_fail(NQ_ERR_ARG, "nq_md_init_velocities: T_init=%g must be non-negative", T_init);
   MdArgs A = md_args(state, N, B, n_small, log_cap, frame_cap, flags);
   A.kT = MD_KB * T_init; A.seed = (unsigned long long)seed; A.remove_translation = remove_translation; A.remove_rotation = remove_rotation;
-  const int blocks = ((n_small + 3) >> 2) + (B - n_small);
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "md_init_velocities");
-  hipLaunchKernelGGL(k_md_init_vel, dim3(blocks), dim3(256), 0, st, A);
+  hipLaunchKernelGGL(k_md_init_vel, dim3(nq_owned_grid(n_small, B)), dim3(256), 0, st, A);
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }
@@ -722,10 +663,9 @@ int nq_md_step(void* state, int32_t N, int32_t B, int32_t n_small, int32_t log_c
   A.xi = mode == 1 ? xi : nullptr; A.eta = mode == 1 ? eta : nullptr;
   A.dt = dt; A.kT = kT; A.fr = mode == 1 ? fr : 0.0; A.seed = (unsigned long long)seed;
   A.mode = mode; A.interval = interval; A.finish_only = finish_only;
-  const int blocks = ((n_small + 3) >> 2) + (B - n_small);
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "md_step");
-  hipLaunchKernelGGL(k_md_step, dim3(blocks), dim3(256), 0, st, A);
+  hipLaunchKernelGGL(k_md_step, dim3(nq_owned_grid(n_small, B)), dim3(256), 0, st, A);
   NQ_LAUNCH_CHECK();
   return NQ_OK;
 }

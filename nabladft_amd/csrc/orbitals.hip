@@ -30,37 +30,24 @@
 #include <vector>
 
 #include "../../include/nablaq.h"
-#include "common.h"
+#include "devstate.h"
 
 #define NQ_ORB_MAX_M 1024
 #define NQ_ORB_NT 512
 #define NQ_ORB_NW (NQ_ORB_NT / 64)
 #define NQ_ORB_MAX_ITER 60
 #define NQ_ORB_HDR 16
-#define NQ_ORB_PARTS 11
-#define NQ_ORB_EPS 2.220446049250313e-16
 // dynamic LDS of k_orb_solve: d e tau v p [1024 each], 16 scalars, 8 control words
 #define NQ_ORB_LDS_BYTES ((5 * NQ_ORB_MAX_M + 16) * 8 + 8 * 4)
 
 enum { OH_B = 0, OH_M, OH_PLO, OH_PHI, OH_STATUS, OH_MAXM };
-enum { OP_HDR = 0, OP_ORB_PTR, OP_PACK_PTR, OP_ORDER, OP_STATUS, OP_INFO, OP_ITERS, OP_EPS, OP_COEFF, OP_WORK, OP_CHOL };
-
-struct OrbLayout {
-  size_t part[NQ_ORB_PARTS], total;
-};
+enum { OP_HDR = 0, OP_ORB_PTR, OP_PACK_PTR, OP_ORDER, OP_STATUS, OP_INFO, OP_ITERS, OP_EPS, OP_COEFF, OP_WORK, OP_CHOL, OP_PARTS };
+typedef NqStateLayout<OP_PARTS> OrbLayout;
 
 static OrbLayout orb_layout(long B, long M, long long P) {
-  OrbLayout L;
-  auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t bytes[NQ_ORB_PARTS] = {NQ_ORB_HDR * 4, (size_t)(B + 1) * 4, (size_t)(B + 1) * 8, (size_t)B * 4, (size_t)B * 4, (size_t)B * 4, (size_t)B * 4,
-                                      (size_t)M * 8, (size_t)P * 8, (size_t)P * 8, (size_t)P * 8};
-  size_t o = 0;
-  for (int i = 0; i < NQ_ORB_PARTS; ++i) {
-    L.part[i] = o;
-    o = up(o + bytes[i]);
-  }
-  L.total = o;
-  return L;
+  const size_t bytes[OP_PARTS] = {NQ_ORB_HDR * 4, (size_t)(B + 1) * 4, (size_t)(B + 1) * 8, (size_t)B * 4, (size_t)B * 4, (size_t)B * 4, (size_t)B * 4,
+                                  (size_t)M * 8, (size_t)P * 8, (size_t)P * 8, (size_t)P * 8};
+  return nq_state_layout(bytes);
 }
 
 struct OrbArgs {
@@ -70,26 +57,14 @@ struct OrbArgs {
 };
 
 __device__ __forceinline__ bool orb_dims_ok(const OrbArgs& a) {
-  const bool ok = a.hdr[OH_B] == a.B && a.hdr[OH_M] == a.M && a.hdr[OH_PLO] == (int)(a.P & 0xffffffffLL) && a.hdr[OH_PHI] == (int)(a.P >> 32);
+  const bool ok = a.hdr[OH_B] == a.B && a.hdr[OH_M] == a.M && nq_split64_is(a.hdr + OH_PLO, a.P);
   if (!ok && blockIdx.x == 0 && threadIdx.x == 0) a.hdr[OH_STATUS] = -2;   // not the state nq_orb_init prepared: touch nothing else
   return ok;
 }
 
-__device__ __forceinline__ double orb_in(const void* p, long long i, int f64) { return f64 ? ((const double*)p)[i] : (double)((const float*)p)[i]; }
-
-__device__ __forceinline__ double orb_wave_sum(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);   // pairwise butterfly: every lane ends with the same bits
-  return v;
-}
-__device__ __forceinline__ double orb_wave_max(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v = fmax(v, __shfl_xor(v, s, 64));
-  return v;
-}
 // the wavefronts' partial sums meet in red[NQ_ORB_NW] and are added in wavefront order; every thread returns what it read from LDS (uniform)
 __device__ __forceinline__ double orb_block_sum(double v, double* red) {
-  v = orb_wave_sum(v);
+  v = nq_wave_sum_f64(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   double r = 0.0;
@@ -123,15 +98,15 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_solve(OrbArgs a, const void* 
   double* sc = p + NQ_ORB_MAX_M;
   int* ctl = (int*)(sc + 16);
   int* perm = (int*)v;          // after the last sweep
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double nan = nq_nan_f64();
 
   // ---- 0. load ------------------------------------------------------------------------------------------------------------------------
   for (int i = wave; i < m; i += NQ_ORB_NW)
     for (int j = lane; j <= i; j += 64) {
-      const double h = orb_in(H, base + (long long)i * m + j, h_f64);
+      const double h = nq_load_f64(H, base + (long long)i * m + j, h_f64);
       A[i * m + j] = h;
       A[j * m + i] = h;
-      if (S) L[i * m + j] = orb_in(S, base + (long long)i * m + j, s_f64);
+      if (S) L[i * m + j] = nq_load_f64(S, base + (long long)i * m + j, s_f64);
     }
   __syncthreads();
 
@@ -212,7 +187,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_solve(OrbArgs a, const void* 
     if (wave == 0) {
       double mx = 0.0;
       for (int j = 1 + lane; j < n; j += 64) mx = fmax(mx, fabs(v[j]));
-      mx = orb_wave_max(mx);
+      mx = nq_wave_max_f64(mx);
       double tk = 0.0, ek = v[0], scal = 0.0;
       if (mx != 0.0) {
         const double alpha = v[0], amx = fmax(mx, fabs(alpha));
@@ -221,7 +196,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_solve(OrbArgs a, const void* 
           const double t = v[j] / amx;
           ss += t * t;
         }
-        ss = orb_wave_sum(ss);
+        ss = nq_wave_sum_f64(ss);
         const double nrm = amx * sqrt(ss);
         const double beta = alpha >= 0.0 ? -nrm : nrm;
         tk = (beta - alpha) / beta;
@@ -250,7 +225,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_solve(OrbArgs a, const void* 
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        acc[u] = orb_wave_sum(acc[u]);
+        acc[u] = nq_wave_sum_f64(acc[u]);
         if (lane == 0 && i0 + u < n) p[i0 + u] = tk * acc[u];
       }
     }
@@ -258,7 +233,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_solve(OrbArgs a, const void* 
     if (wave == 0) {
       double s = 0.0;
       for (int i = lane; i < n; i += 64) s = fma(p[i], v[i], s);
-      s = orb_wave_sum(s);
+      s = nq_wave_sum_f64(s);
       if (lane == 0) sc[2] = -0.5 * tk * s;
     }
     __syncthreads();
@@ -293,7 +268,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_solve(OrbArgs a, const void* 
           if (i0 + u < n) acc[u] = fma(T[(k + 1 + i0 + u) * m + k + 1 + j], vj, acc[u]);
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) acc[u] = tk * orb_wave_sum(acc[u]);
+      for (int u = 0; u < 4; ++u) acc[u] = tk * nq_wave_sum_f64(acc[u]);
       for (int j = lane; j < n; j += 64) {
         const double vj = v[j];
 #pragma unroll
@@ -316,7 +291,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_solve(OrbArgs a, const void* 
         int mm = l;
         for (; mm < m - 1; ++mm) {
           const double dd = fabs(d[mm]) + fabs(d[mm + 1]);
-          if (fabs(e[mm]) <= NQ_ORB_EPS * dd) break;
+          if (fabs(e[mm]) <= NQ_F64_EPS * dd) break;
         }
         if (mm == l) { ++l; it = 0; continue; }
         if (it == NQ_ORB_MAX_ITER) { flag = 2; break; }
@@ -390,23 +365,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_solve(OrbArgs a, const void* 
   // ---- 5. order, back-transform, sign ------------------------------------------------------------------------------------------------------
   for (int i = tid; i < m; i += NQ_ORB_NT) perm[i] = i;   // the identity first, so that NaNs leave it in range
   __syncthreads();
-  int rank[NQ_ORB_MAX_M / NQ_ORB_NT];
-#pragma unroll
-  for (int u = 0; u < NQ_ORB_MAX_M / NQ_ORB_NT; ++u) {
-    const int i = tid + u * NQ_ORB_NT;
-    rank[u] = -1;
-    if (i < m) {
-      const double di = d[i];
-      int rk = 0;
-      for (int j = 0; j < m; ++j) rk += (d[j] < di || (d[j] == di && j < i)) ? 1 : 0;
-      rank[u] = rk;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < NQ_ORB_MAX_M / NQ_ORB_NT; ++u)
-    if (rank[u] >= 0) perm[rank[u]] = tid + u * NQ_ORB_NT;
-  __syncthreads();
+  nq_rank_perm<NQ_ORB_NT, NQ_ORB_MAX_M / NQ_ORB_NT>(d, m, perm);
   for (int k = tid; k < m; k += NQ_ORB_NT) ev[k] = d[perm[k]];
   for (int k = wave; k < m; k += NQ_ORB_NW) {            // sorted rows into the matrix's storage, which nothing needs any more
     const double* src = T + perm[k] * m;
@@ -455,7 +414,7 @@ __global__ void k_orb_frontier(OrbArgs a, const int* n_occ, double* homo, double
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.B) return;
   const int o0 = a.orb_ptr[b], m = a.orb_ptr[b + 1] - o0, no = n_occ[b];
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double nan = nq_nan_f64();
   double h = nan, l = nan;
   if (no >= 1 && no <= m) {
     h = a.eps[o0 + no - 1];
@@ -475,7 +434,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_compare(OrbArgs a, OrbArgs t,
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = a.order[blockIdx.x], B = a.B;
   const int o0 = a.orb_ptr[b], m = a.orb_ptr[b + 1] - o0, no = n_occ[b];
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  const double nan = nq_nan_f64();
   if (m < 1 || m > NQ_ORB_MAX_M || no < 1 || no > m || t.orb_ptr[b] != o0 || t.orb_ptr[b + 1] != o0 + m) {   // uniform
     if (tid < 7) out[(long)tid * B + b] = nan;
     return;
@@ -497,7 +456,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_compare(OrbArgs a, OrbArgs t,
   if (S) {
     for (int i = wave; i < m; i += NQ_ORB_NW)
       for (int j = lane; j <= i; j += 64) {
-        const double s = orb_in(S, base + (long long)i * m + j, s_f64);
+        const double s = nq_load_f64(S, base + (long long)i * m + j, s_f64);
         W[i * m + j] = s;
         W[j * m + i] = s;
       }
@@ -519,13 +478,13 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_compare(OrbArgs a, OrbArgs t,
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          dot[u] = orb_wave_sum(dot[u]);
+          dot[u] = nq_wave_sum_f64(dot[u]);
           if (i0 + u < m) acc = fma(ca[k * m + i0 + u], dot[u], acc);   // the same in every lane
         }
       }
     } else {
       for (int i = tid; i < m; i += NQ_ORB_NT) acc = fma(ca[k * m + i], ct[k * m + i], acc);
-      acc = orb_wave_sum(acc);
+      acc = nq_wave_sum_f64(acc);
     }
     if (lane == 0) red[wave] = acc;
     __syncthreads();
@@ -573,16 +532,13 @@ static OrbArgs orb_args(void* state, int32_t B, int32_t M, int64_t P) {
 extern "C" {
 
 size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P) {
-  if (orb_check_dims(B, M, P) != NQ_OK) return 0;
-  return orb_layout(B, M, P).total;
+  return orb_check_dims(B, M, P) == NQ_OK ? orb_layout(B, M, P).total : 0;
 }
 
 int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host) {
   if (!offsets_host) return nq_fail(NQ_ERR_ARG, "null argument");
   NQ_TRY(orb_check_dims(B, M, P));
-  const OrbLayout L = orb_layout(B, M, P);
-  for (int i = 0; i < NQ_ORB_PARTS; ++i) offsets_host[i] = L.part[i];
-  return NQ_OK;
+  return nq_state_offsets(orb_layout(B, M, P), offsets_host);
 }
 
 int nq_orb_init(void* state, size_t state_bytes, const int32_t* orb_ptr_host, int32_t B, int32_t M, int64_t P, int32_t* plan_host, void* stream) {
@@ -594,9 +550,8 @@ int nq_orb_init(void* state, size_t state_bytes, const int32_t* orb_ptr_host, in
     }
   }
   NQ_TRY(orb_check_dims(B, M, P));
-  if ((reinterpret_cast<uintptr_t>(state) & 15) != 0) return nq_fail(NQ_ERR_ARG, "nq_orb_init: state must be 16-byte aligned");
   const OrbLayout L = orb_layout(B, M, P);
-  if (state_bytes < L.total) return nq_fail(NQ_ERR_WORKSPACE, "nq_orb_init: state too small: %zu < %zu bytes", state_bytes, L.total);
+  NQ_TRY(nq_state_check("nq_orb_init:", state, state_bytes, L.total));
   if (orb_ptr_host[0] != 0 || orb_ptr_host[B] != M) return nq_fail(NQ_ERR_ARG, "nq_orb_init: orb_ptr must run from 0 to M=%d", M);
   // the host-built parts are contiguous from the header up to order: one host image, one copy
   std::vector<char> img(L.part[OP_STATUS], 0);
@@ -619,11 +574,10 @@ int nq_orb_init(void* state, size_t state_bytes, const int32_t* orb_ptr_host, in
   if (pp != P) return nq_fail(NQ_ERR_ARG, "nq_orb_init: orb_ptr packs to P=%lld entries, the call said P=%lld", pp, (long long)P);
   orb_ptr[B] = M; pack_ptr[B] = P;
   std::stable_sort(order, order + B, [&](int x, int y) { return orb_ptr_host[x + 1] - orb_ptr_host[x] > orb_ptr_host[y + 1] - orb_ptr_host[y]; });   // largest first
-  hdr[OH_B] = B; hdr[OH_M] = M; hdr[OH_PLO] = (int)(P & 0xffffffffLL); hdr[OH_PHI] = (int)(P >> 32); hdr[OH_MAXM] = max_m;
+  hdr[OH_B] = B; hdr[OH_M] = M; nq_split64(P, hdr + OH_PLO); hdr[OH_MAXM] = max_m;
   plan_host[0] = max_m; plan_host[1] = NQ_ORB_LDS_BYTES;
   hipStream_t st = (hipStream_t)stream;
-  NQ_HIP(hipMemcpyAsync(state, img.data(), L.part[OP_STATUS], hipMemcpyHostToDevice, st));
-  NQ_HIP(hipStreamSynchronize(st));   // the image is a host temporary
+  NQ_TRY(nq_state_upload(state, img.data(), L.part[OP_STATUS], st));
   NQ_HIP(hipMemsetAsync((char*)state + L.part[OP_STATUS], 0, L.part[OP_COEFF] - L.part[OP_STATUS], st));   // status, info, iters, eps
   return NQ_OK;
 }

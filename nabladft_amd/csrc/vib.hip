@@ -23,35 +23,24 @@
 #include <vector>
 
 #include "../../include/nablaq.h"
-#include "common.h"
+#include "devstate.h"
 
 #define NQ_VIB_MAX_DOF 576
 #define NQ_VIB_LDS_BYTES 163840
 #define NQ_VIB_MAX_SWEEPS 30
 #define NQ_VIB_HDR 16
-#define NQ_VIB_PARTS 18
 
 enum { VH_N = 0, VH_B, VH_D, VH_PLO, VH_PHI, VH_STATUS, VH_NLDS };
 
-struct VibLayout {
-  size_t part[NQ_VIB_PARTS], total;
-};
 enum { VP_HDR = 0, VP_MOL_PTR, VP_DOF_PTR, VP_HESS_PTR, VP_ORDER, VP_FREE_ATOM, VP_DISP_MOL, VP_DISP_OFF, VP_IM, VP_R, VP_H, VP_ASYM, VP_SWEEPS, VP_STATUS,
-       VP_OMEGA2, VP_WORK, VP_HESS, VP_MODES };
+       VP_OMEGA2, VP_WORK, VP_HESS, VP_MODES, VP_PARTS };
+typedef NqStateLayout<VP_PARTS> VibLayout;
 
 static VibLayout vib_layout(long N, long B, long D, long long P) {
-  VibLayout L;
-  auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t bytes[NQ_VIB_PARTS] = {NQ_VIB_HDR * 4, (size_t)(B + 1) * 4, (size_t)(B + 1) * 4, (size_t)(B + 1) * 8, (size_t)B * 4, (size_t)(D / 3) * 4,
-                                      (size_t)D * 4, (size_t)(D + 1) * 8, (size_t)D * 8, (size_t)N * 24, (size_t)D * 8, (size_t)B * 8, (size_t)B * 4,
-                                      (size_t)B * 4, (size_t)D * 8, (size_t)P * 8, (size_t)P * 8, (size_t)P * 8};
-  size_t o = 0;
-  for (int i = 0; i < NQ_VIB_PARTS; ++i) {
-    L.part[i] = o;
-    o = up(o + bytes[i]);
-  }
-  L.total = o;
-  return L;
+  const size_t bytes[VP_PARTS] = {NQ_VIB_HDR * 4, (size_t)(B + 1) * 4, (size_t)(B + 1) * 4, (size_t)(B + 1) * 8, (size_t)B * 4, (size_t)(D / 3) * 4,
+                                  (size_t)D * 4, (size_t)(D + 1) * 8, (size_t)D * 8, (size_t)N * 24, (size_t)D * 8, (size_t)B * 8, (size_t)B * 4,
+                                  (size_t)B * 4, (size_t)D * 8, (size_t)P * 8, (size_t)P * 8, (size_t)P * 8};
+  return nq_state_layout(bytes);
 }
 
 // dynamic LDS of k_vib_jacobi: [A: m x (m | 1)] d[m] cs[2 np] red[8] pq[2 np] perm[m], np = pairs per round
@@ -69,15 +58,9 @@ struct VibArgs {
 };
 
 __device__ __forceinline__ bool vib_dims_ok(const VibArgs& a) {
-  const bool ok = a.hdr[VH_N] == a.N && a.hdr[VH_B] == a.B && a.hdr[VH_D] == a.D && a.hdr[VH_PLO] == (int)(a.P & 0xffffffffLL) && a.hdr[VH_PHI] == (int)(a.P >> 32);
+  const bool ok = a.hdr[VH_N] == a.N && a.hdr[VH_B] == a.B && a.hdr[VH_D] == a.D && nq_split64_is(a.hdr + VH_PLO, a.P);
   if (!ok && blockIdx.x == 0 && threadIdx.x == 0) a.hdr[VH_STATUS] = -2;   // not the state nq_vib_init prepared: touch nothing else
   return ok;
-}
-
-__global__ void k_vib_init_pos(const void* pos, int pos_f64, long count, double* r) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  r[i] = pos_f64 ? ((const double*)pos)[i] : (double)((const float*)pos)[i];
 }
 
 // one 64-thread workgroup per displacement of the chunk
@@ -122,26 +105,15 @@ __global__ __launch_bounds__(64) void k_vib_accumulate(VibArgs a, int c0, int c1
   for (int c = threadIdx.x; c < m; c += 64) {
     const int la = a.free_atom[d0 / 3 + c / 3] - start;
     const long long im = (base + la) * 3 + c % 3, ip = im + (long long)n * 3;
-    const double fm = forces_f64 ? ((const double*)forces)[im] : (double)((const float*)forces)[im];
-    const double fp = forces_f64 ? ((const double*)forces)[ip] : (double)((const float*)forces)[ip];
+    const double fm = nq_load_f64(forces, im, forces_f64), fp = nq_load_f64(forces, ip, forces_f64);
     row[c] = (fm - fp) / h;
   }
 }
 
-__device__ __forceinline__ double vib_wave_sum(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);   // pairwise butterfly: every lane ends with the same bits
-  return v;
-}
-__device__ __forceinline__ double vib_wave_max(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v = fmax(v, __shfl_xor(v, s, 64));
-  return v;
-}
 // the four wavefronts' partial results meet in red[4] and are combined 0,1,2,3; every thread returns what it read from LDS (uniform)
 template <bool MAX>
 __device__ __forceinline__ double vib_block_reduce(double v, double* red) {
-  v = MAX ? vib_wave_max(v) : vib_wave_sum(v);
+  v = MAX ? nq_wave_max_f64(v) : nq_wave_sum_f64(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   const double r = MAX ? fmax(fmax(red[0], red[1]), fmax(red[2], red[3])) : ((red[0] + red[1]) + (red[2] + red[3]));
@@ -211,7 +183,7 @@ __global__ __launch_bounds__(256) void k_vib_jacobi(VibArgs a, int first, int sc
     fro += v * v;
   }
   fro = vib_block_reduce<false>(fro, red);   // its barriers also publish A and V
-  const double eps_m = (double)m * 2.220446049250313e-16;
+  const double eps_m = (double)m * NQ_F64_EPS;
   const double thr2 = (eps_m * eps_m) * fro;   // off^2 <= (m 2^-52)^2 |A|_F^2
 
   int sweeps = 0, status = 1;
@@ -327,26 +299,10 @@ __global__ __launch_bounds__(256) void k_vib_jacobi(VibArgs a, int first, int sc
     ++sweeps;
   }
 
-  // ascending order by rank (ties by index); perm starts as the identity so that NaNs leave it in range
+  // ascending order by rank (ties by index)
   for (int i = tid; i < m; i += 256) { dg[i] = A[i * ld + i]; perm[i] = i; }
   __syncthreads();
-  int rank[3];      // m <= 576 < 3 * 256
-#pragma unroll
-  for (int u = 0; u < 3; ++u) {
-    const int i = tid + u * 256;
-    rank[u] = -1;
-    if (i < m) {
-      const double di = dg[i];
-      int rk = 0;
-      for (int j = 0; j < m; ++j) rk += (dg[j] < di || (dg[j] == di && j < i)) ? 1 : 0;
-      rank[u] = rk;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < 3; ++u)
-    if (rank[u] >= 0) perm[rank[u]] = tid + u * 256;
-  __syncthreads();
+  nq_rank_perm<256, 3>(dg, m, perm);      // m <= 576 < 3 * 256
   for (int k = tid; k < m; k += 256) a.omega2[d0 + k] = dg[perm[k]];
   // sorted (and mass-scaled) rows: through the matrix's global storage, which nothing needs any more
   for (int idx = tid; idx < mm; idx += 256) {
@@ -383,25 +339,21 @@ static VibArgs vib_args(void* state, int32_t N, int32_t B, int32_t D, int64_t P)
 extern "C" {
 
 size_t nq_vib_state_bytes(int32_t N, int32_t B, int32_t D, int64_t P) {
-  if (vib_check_dims(N, B, D, P) != NQ_OK) return 0;
-  return vib_layout(N, B, D, P).total;
+  return vib_check_dims(N, B, D, P) == NQ_OK ? vib_layout(N, B, D, P).total : 0;
 }
 
 int nq_vib_state_layout(int32_t N, int32_t B, int32_t D, int64_t P, size_t* offsets_host) {
   if (!offsets_host) return nq_fail(NQ_ERR_ARG, "null argument");
   NQ_TRY(vib_check_dims(N, B, D, P));
-  const VibLayout L = vib_layout(N, B, D, P);
-  for (int i = 0; i < NQ_VIB_PARTS; ++i) offsets_host[i] = L.part[i];
-  return NQ_OK;
+  return nq_state_offsets(vib_layout(N, B, D, P), offsets_host);
 }
 
 int nq_vib_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, const double* masses_host, const uint8_t* fixed_host, int32_t N, int32_t B,
                 int32_t D, int64_t P, const void* pos, int32_t pos_f64, int32_t* plan_host, void* stream) {
   if (!state || !mol_ptr_host || !masses_host || !pos || !plan_host) return nq_fail(NQ_ERR_ARG, "null argument");
   NQ_TRY(vib_check_dims(N, B, D, P));
-  if ((reinterpret_cast<uintptr_t>(state) & 15) != 0) return nq_fail(NQ_ERR_ARG, "nq_vib_init: state must be 16-byte aligned");
   const VibLayout L = vib_layout(N, B, D, P);
-  if (state_bytes < L.total) return nq_fail(NQ_ERR_WORKSPACE, "nq_vib_init: state too small: %zu < %zu bytes", state_bytes, L.total);
+  NQ_TRY(nq_state_check("nq_vib_init:", state, state_bytes, L.total));
   if (mol_ptr_host[0] != 0 || mol_ptr_host[B] != N) return nq_fail(NQ_ERR_ARG, "nq_vib_init: mol_ptr must run from 0 to N=%d", N);
   // the host-built parts are contiguous from the header up to im: one host image, one copy
   std::vector<char> img(L.part[VP_R], 0);
@@ -452,18 +404,14 @@ int nq_vib_init(void* state, size_t state_bytes, const int32_t* mol_ptr_host, co
   mol_ptr[B] = N; dof_ptr[B] = D; hess_ptr[B] = P; disp_off[D] = ioff;
   for (size_t i = 0; i < in_lds.size(); ++i) order[i] = in_lds[i];
   for (size_t i = 0; i < in_global.size(); ++i) order[in_lds.size() + i] = in_global[i];
-  hdr[VH_N] = N; hdr[VH_B] = B; hdr[VH_D] = D; hdr[VH_PLO] = (int)(P & 0xffffffffLL); hdr[VH_PHI] = (int)(P >> 32); hdr[VH_NLDS] = (int)in_lds.size();
+  hdr[VH_N] = N; hdr[VH_B] = B; hdr[VH_D] = D; nq_split64(P, hdr + VH_PLO); hdr[VH_NLDS] = (int)in_lds.size();
   plan_host[0] = (int32_t)in_lds.size(); plan_host[1] = max_m_lds; plan_host[2] = max_m;
   hipStream_t st = (hipStream_t)stream;
-  NQ_HIP(hipMemcpyAsync(state, img.data(), L.part[VP_R], hipMemcpyHostToDevice, st));
-  NQ_HIP(hipStreamSynchronize(st));   // the image is a host temporary
+  NQ_TRY(nq_state_upload(state, img.data(), L.part[VP_R], st));
   char* base = (char*)state;
   NQ_HIP(hipMemsetAsync(base + L.part[VP_H], 0, L.part[VP_WORK] - L.part[VP_H], st));   // h, asymmetry, sweeps, status, omega2
-  const long count = (long)N * 3;
   NQ_PROF(st, "vib_init");
-  hipLaunchKernelGGL(k_vib_init_pos, dim3(nq_cdiv(count, 256)), dim3(256), 0, st, pos, pos_f64, count, (double*)(base + L.part[VP_R]));
-  NQ_LAUNCH_CHECK();
-  return NQ_OK;
+  return nq_init_pos_f64(st, pos, pos_f64, nullptr, (long)N * 3, (double*)(base + L.part[VP_R]), nullptr, nullptr);
 }
 
 static int vib_check_chunk(const char* who, int32_t D, int32_t c0, int32_t c1, int64_t img_atoms) {

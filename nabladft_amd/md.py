@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._devstate import DeviceState, batch_ptr_host, fixed_to_uint8, require_forces, require_positions
 from .optimization import ASEBatchwiseLBFGS, PyGBatchwiseCalculator
 from .trainer import Batch
 
@@ -77,17 +78,13 @@ def masses_for(z, masses=None) -> np.ndarray:
 
 
 # ---- device state -----------------------------------------------------------------------------------------------------------------------
-class MDState:
+class MDState(DeviceState):
     """One caller-owned device buffer behind ``nq_md_init`` / ``nq_md_step`` plus typed views of its parts (include/nablaq.h; entry points added under ABI 17).
     ``log_capacity`` / ``frame_capacity``: rows of the device rings, 0 or None = that ring is not kept."""
 
     def __init__(self, ptr_host: Sequence[int], pos: torch.Tensor, masses, fixed=None, mol_key=None, velocities: Optional[torch.Tensor] = None,
                  log_capacity: Optional[int] = 0, frame_capacity: Optional[int] = 0, store_velocities: bool = False):
-        lib = _lib.load()
-        if not pos.is_cuda:
-            raise RuntimeError("nabladft_amd.md runs on MI355X only (no CPU fallback): move the batch to cuda")
-        if pos.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"positions must be float32 or float64, not {pos.dtype}")
+        require_positions(pos, "md")
         ptr_host = np.ascontiguousarray(np.asarray(ptr_host, dtype=np.int32))
         self.B, self.N = int(ptr_host.shape[0]) - 1, int(pos.shape[0])
         self.ptr_host = ptr_host
@@ -96,21 +93,17 @@ class MDState:
         masses = np.ascontiguousarray(np.asarray(masses, dtype=np.float64).reshape(-1))
         if masses.shape[0] != self.N:
             raise ValueError(f"masses has {masses.shape[0]} entries for {self.N} atoms")
-        fixed_host = None
-        if fixed is not None:
-            fixed_host = np.zeros(self.N, dtype=np.uint8)
-            fixed_host[np.asarray(fixed.cpu() if isinstance(fixed, torch.Tensor) else fixed)] = 1          # indices or a boolean mask
+        fixed_host = fixed_to_uint8(fixed, self.N)
         key_host = None if mol_key is None else np.ascontiguousarray(np.asarray(mol_key, dtype=np.int64).reshape(-1))
         if key_host is not None and key_host.shape[0] != self.B:
             raise ValueError(f"mol_key has {key_host.shape[0]} entries for {self.B} molecules")
         self.mol_key = np.arange(self.B, dtype=np.int64) if key_host is None else key_host
-        self._dims = (self.N, self.B, self.log_capacity, self.frame_capacity, self.flags)
-        nbytes = lib.nq_md_state_bytes(*self._dims)
-        if nbytes == 0:
-            raise _lib.NablaqError(_lib.NQ_ERR_ARG, lib.nq_last_error().decode(errors="replace"))
-        off = (C.c_size_t * 12)()
-        _lib.check(lib.nq_md_state_layout(*self._dims, off))
-        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=pos.device)
+        N, B, lc, fc, i32, f64 = self.N, self.B, self.log_capacity, self.frame_capacity, torch.int32, torch.float64
+        self.frame_velocities = None
+        nbytes = self._allocate("md", (N, B, lc, fc, self.flags), (
+            ("header_dev", i32, (32,)), ("ptr_dev", i32, (B + 1,)), (None, i32, (B,)), ("key_dev", torch.int64, (B,)), ("mass", f64, (N,)),
+            (None, torch.uint8, (N,)), ("r", f64, (N, 3)), ("v", f64, (N, 3)), (None, f64, (N, 3)), ("log", f64, (lc, B, 8)), ("frames", f64, (fc, N, 3)),
+            ("frame_velocities" if store_velocities else None, f64, (fc, N, 3))), pos.device)
         self.pos32 = torch.empty(self.N, 3, dtype=torch.float32, device=pos.device)      # what the model reads; written by the step kernel
         pos = pos.contiguous()
         if velocities is not None:
@@ -119,25 +112,10 @@ class MDState:
                 raise ValueError(f"velocities must be [{self.N}, 3]")
         n_small = C.c_int32(0)
         hp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        _lib.check(lib.nq_md_init(_lib.ptr(self.buf), nbytes, hp(ptr_host), hp(key_host), hp(masses), hp(fixed_host), *self._dims, _lib.ptr(pos),
-                                  int(pos.dtype == torch.float64), _lib.ptr(velocities), _lib.ptr(self.pos32), C.byref(n_small), _lib.stream_ptr()))
+        _lib.check(_lib.load().nq_md_init(_lib.ptr(self.buf), nbytes, hp(ptr_host), hp(key_host), hp(masses), hp(fixed_host), *self._dims, _lib.ptr(pos),
+                                          int(pos.dtype == torch.float64), _lib.ptr(velocities), _lib.ptr(self.pos32), C.byref(n_small), _lib.stream_ptr()))
         self.n_small = n_small.value
         self.masses_host, self.fixed_host = masses, fixed_host
-        N, B = self.N, self.B
-
-        def view(i, dtype, count, shape):
-            size = torch.empty(0, dtype=dtype).element_size()
-            return self.buf[off[i]:off[i] + count * size].view(dtype).view(shape)
-        self.header_dev = view(0, torch.int32, 32, (32,))
-        self.ptr_dev = view(1, torch.int32, B + 1, (B + 1,))
-        self.key_dev = view(3, torch.int64, B, (B,))
-        self.mass = view(4, torch.float64, N, (N,))
-        self.r = view(6, torch.float64, N * 3, (N, 3))
-        self.v = view(7, torch.float64, N * 3, (N, 3))
-        lc, fc = self.log_capacity, self.frame_capacity
-        self.log = view(9, torch.float64, lc * B * 8, (lc, B, 8))
-        self.frames = view(10, torch.float64, fc * N * 3, (fc, N, 3))
-        self.frame_velocities = view(11, torch.float64, fc * N * 3, (fc, N, 3)) if store_velocities else None
 
     def _args(self):
         return (_lib.ptr(self.buf), self.N, self.B, self.n_small, self.log_capacity, self.frame_capacity, self.flags)
@@ -148,9 +126,7 @@ class MDState:
     def step(self, forces: torch.Tensor, energies: Optional[torch.Tensor] = None, mode: int = 0, dt: float = 0.5, kT: float = 0.0, friction: float = 0.0,
              interval: int = 1, seed: int = 0, xi: Optional[torch.Tensor] = None, eta: Optional[torch.Tensor] = None, finish_only: bool = False):
         dev = self.buf.device
-        if forces.dtype not in (torch.float32, torch.float64) or tuple(forces.shape) != (self.N, 3) or forces.device != dev:
-            raise ValueError(f"forces must be a float32 / float64 [{self.N}, 3] tensor on {dev}")
-        forces = forces.contiguous()
+        forces = require_forces(forces, self.N, dev)
         if energies is not None:
             energies = energies.reshape(-1).contiguous()
             if energies.dtype not in (torch.float32, torch.float64) or energies.shape[0] != self.B or energies.device != dev:
@@ -175,7 +151,7 @@ class MDState:
 
     def header(self) -> dict:
         """The header words (one small device->host copy, synchronises the stream)."""
-        h = self.header_dev.cpu().tolist()
+        h = self._read_header()
         if h[1] < 0:
             raise RuntimeError("nq_md_step was called with other dimensions than nq_md_init prepared the state for")
         return dict(zip(_HDR, h))
@@ -221,9 +197,8 @@ class BatchedMD:
             if self.state.N != int(batch.pos.shape[0]):
                 raise ValueError("this BatchedMD holds the state of another batch")
             return self.state
-        ptr = batch.ptr.cpu().numpy() if getattr(batch, "ptr", None) is not None else np.concatenate([[0], np.cumsum(np.bincount(batch.batch.cpu().numpy()))])
         m = masses_for(batch.z, self.masses)
-        st = self.state = MDState(ptr, batch.pos, m, self.fixed_atoms_mask, self.mol_key, None, self.log_capacity, self.frame_capacity, self.store_velocities)
+        st = self.state = MDState(batch_ptr_host(batch), batch.pos, m, self.fixed_atoms_mask, self.mol_key, None, self.log_capacity, self.frame_capacity, self.store_velocities)
         # the model's batch: same z / batch / ptr tensors, positions = the float32 tensor the step kernel rewrites
         self._work = Batch(st.pos32, batch.z, batch.batch, getattr(batch, "y", None), getattr(batch, "forces", None), batch.ptr if getattr(batch, "ptr", None) is not None else None)
         self._log, self._frames, self._fvel = [], [], []

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._devstate import DeviceState, batch_ptr_host, fixed_to_uint8, require_forces, require_positions
 from .data import _decode_ase_blob
 from .trainer import Batch
 
@@ -37,49 +38,28 @@ _HDR = ("iteration", "unconverged", "latch", "normalizations", "N", "B", "memory
 
 
 # ---- device state -----------------------------------------------------------------------------------------------------------------------
-class LBFGSState:
+class LBFGSState(DeviceState):
     """One caller-owned device buffer behind ``nq_lbfgs_init`` / ``nq_lbfgs_step`` plus typed views of its parts (include/nablaq.h, ABI 17)."""
 
     def __init__(self, ptr_host: Sequence[int], pos: torch.Tensor, memory: int):
-        lib = _lib.load()
-        if not pos.is_cuda:
-            raise RuntimeError("nabladft_amd.optimization runs on MI355X only (no CPU fallback): move the batch to cuda")
-        if pos.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"positions must be float32 or float64, not {pos.dtype}")
+        require_positions(pos, "optimization")
         ptr_host = np.ascontiguousarray(np.asarray(ptr_host, dtype=np.int32))
         self.B, self.N, self.memory = int(ptr_host.shape[0]) - 1, int(pos.shape[0]), int(memory)
         self.ptr_host = ptr_host
-        nbytes = lib.nq_lbfgs_state_bytes(self.N, self.B, self.memory)
-        if nbytes == 0:
-            raise _lib.NablaqError(_lib.NQ_ERR_ARG, lib.nq_last_error().decode(errors="replace"))
-        off = (C.c_size_t * 10)()
-        _lib.check(lib.nq_lbfgs_state_layout(self.N, self.B, self.memory, off))
-        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=pos.device)
+        N, B, m, i32, f64 = self.N, self.B, self.memory, torch.int32, torch.float64
+        nbytes = self._allocate("lbfgs", (N, B, m), (
+            ("header_dev", i32, (16,)), (None, i32, (B + 1,)), (None, i32, (B,)), ("converged_dev", i32, (B,)), ("rho", f64, (m, B)), ("r", f64, (N, 3)),
+            ("r0", f64, (N, 3)), ("f0", f64, (N, 3)), ("S", f64, (m, N, 3)), ("Y", f64, (m, N, 3))), pos.device)
         self.pos32 = torch.empty(self.N, 3, dtype=torch.float32, device=pos.device)      # what the model reads; written by the step kernel
         pos = pos.contiguous()
         n_small = C.c_int32(0)
-        _lib.check(lib.nq_lbfgs_init(_lib.ptr(self.buf), nbytes, ptr_host.ctypes.data_as(C.c_void_p), self.N, self.B, self.memory, _lib.ptr(pos),
-                                     int(pos.dtype == torch.float64), _lib.ptr(self.pos32), C.byref(n_small), _lib.stream_ptr()))
+        _lib.check(_lib.load().nq_lbfgs_init(_lib.ptr(self.buf), nbytes, ptr_host.ctypes.data_as(C.c_void_p), *self._dims, _lib.ptr(pos),
+                                             int(pos.dtype == torch.float64), _lib.ptr(self.pos32), C.byref(n_small), _lib.stream_ptr()))
         self.n_small = n_small.value
-        N, B, m = self.N, self.B, self.memory
-
-        def view(i, dtype, count, shape):
-            size = torch.empty(0, dtype=dtype).element_size()
-            return self.buf[off[i]:off[i] + count * size].view(dtype).view(shape)
-        self.header_dev = view(0, torch.int32, 16, (16,))
-        self.converged_dev = view(3, torch.int32, B, (B,))
-        self.rho = view(4, torch.float64, m * B, (m, B))
-        self.r = view(5, torch.float64, N * 3, (N, 3))
-        self.r0 = view(6, torch.float64, N * 3, (N, 3))
-        self.f0 = view(7, torch.float64, N * 3, (N, 3))
-        self.S = view(8, torch.float64, m * N * 3, (m, N, 3))
-        self.Y = view(9, torch.float64, m * N * 3, (m, N, 3))
 
     def step(self, forces: torch.Tensor, fmax: float, maxstep: float, damping: float, alpha: float, fixed: Optional[torch.Tensor] = None,
              evaluate_only: bool = False):
-        if forces.dtype not in (torch.float32, torch.float64) or tuple(forces.shape) != (self.N, 3) or forces.device != self.buf.device:
-            raise ValueError(f"forces must be a float32 / float64 [{self.N}, 3] tensor on {self.buf.device}")
-        forces = forces.contiguous()
+        forces = require_forces(forces, self.N, self.buf.device)
         _lib.check(_lib.load().nq_lbfgs_step(_lib.ptr(self.buf), self.N, self.B, self.memory, self.n_small, _lib.ptr(forces), int(forces.dtype == torch.float64),
                                              _lib.ptr(fixed), _lib.ptr(self.pos32), float(fmax), float(maxstep), float(damping), float(alpha),
                                              int(evaluate_only), _lib.stream_ptr()))
@@ -90,7 +70,7 @@ class LBFGSState:
 
     def header(self) -> dict:
         """The header words (one small device->host copy, synchronises the stream)."""
-        h = self.header_dev.cpu().tolist()
+        h = self._read_header()
         if h[1] < 0:
             raise RuntimeError("nq_lbfgs_step was called with other dimensions than nq_lbfgs_init prepared the state for")
         return dict(zip(_HDR, h))
@@ -172,11 +152,8 @@ class ASEBatchwiseLBFGS:
         self.state = self.positions = self.converged_mask = None
 
     def _fixed(self, N, device):
-        if self.fixed_atoms_mask is None:
-            return None
-        m = torch.zeros(N, dtype=torch.uint8)
-        m[torch.as_tensor(np.asarray(self.fixed_atoms_mask))] = 1          # indices or a boolean mask, like f[fixed_atoms_mask] = 0 (calculator.py:86)
-        return m.to(device)
+        m = fixed_to_uint8(self.fixed_atoms_mask, N)                       # indices or a boolean mask, like f[fixed_atoms_mask] = 0 (calculator.py:86)
+        return None if m is None else torch.from_numpy(m).to(device)
 
     def _log(self, forces):
         if self.logfile is None:
@@ -201,8 +178,7 @@ class ASEBatchwiseLBFGS:
         if steps:
             self.max_steps = steps
         dev = batch.pos.device
-        ptr = batch.ptr.cpu().numpy() if getattr(batch, "ptr", None) is not None else np.concatenate([[0], np.cumsum(np.bincount(batch.batch.cpu().numpy()))])
-        st = self.state = LBFGSState(ptr, batch.pos, self.memory)
+        st = self.state = LBFGSState(batch_ptr_host(batch), batch.pos, self.memory)
         fixed = self._fixed(st.N, dev)
         # the model's batch: same z / batch / ptr tensors, positions = the float32 tensor the step kernel rewrites (atoms_list_to_PYG does .float())
         work = Batch(st.pos32, batch.z, batch.batch, getattr(batch, "y", None), getattr(batch, "forces", None), batch.ptr if getattr(batch, "ptr", None) is not None else None)

@@ -23,11 +23,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._devstate import DeviceState
 
 MAX_ORBITALS = 1024
 MAX_QL_SWEEPS = 60            # per eigenvalue (NQ_ORB_MAX_ITER of csrc/orbitals.hip)
 FIGURES = ("eps_mae_occ", "eps_mae_all", "psi_sim_occ", "homo_abs_err", "lumo_abs_err", "gap_abs_err", "psi_sim_min_occ")
-_PARTS = ("header", "orb_ptr", "pack_ptr", "order", "status", "info", "iters", "eps", "coeff", "work", "chol")
 
 
 def _host_ptr(p) -> np.ndarray:
@@ -101,7 +101,7 @@ def _packed(t: torch.Tensor, P: int, name: str) -> torch.Tensor:
     return t.reshape(-1).contiguous()
 
 
-class OrbitalState:
+class OrbitalState(DeviceState):
     """One caller-owned device buffer behind ``nq_orb_*`` plus typed views of its parts: ``eps`` f64 [M], ``coeff`` f64 [P] (row k of a block = orbital k),
     ``status`` / ``info`` / ``iters`` int32 [B] (include/nablaq.h)."""
 
@@ -109,8 +109,7 @@ class OrbitalState:
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("MI355X only: nabladft_amd.orbitals has no CPU path")
-        lib = _lib.load()
-        op = _orb_ptr_of(orb_ptr)
+        op =_orb_ptr_of(orb_ptr)
         if op.shape[0] < 2:
             raise ValueError("orb_ptr needs at least one molecule")
         m = np.diff(op)
@@ -123,27 +122,15 @@ class OrbitalState:
         self.pack_ptr_host = np.concatenate([[0], np.cumsum(m * m)]).astype(np.int64)
         self.m = m
         self.B, self.M, self.P = int(m.shape[0]), int(op[-1]), int(self.pack_ptr_host[-1])
-        self._dims = (self.B, self.M, self.P)
-        nbytes = lib.nq_orb_state_bytes(*self._dims)
-        if nbytes == 0:
-            raise _lib.NablaqError(_lib.NQ_ERR_ARG, lib.nq_last_error().decode(errors="replace"))
-        off = (C.c_size_t * len(_PARTS))()
-        _lib.check(lib.nq_orb_state_layout(*self._dims, off))
-        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        B, M, P, i32, f64 = self.B, self.M, self.P, torch.int32, torch.float64
+        nbytes = self._allocate("orb", (B, M, P), (
+            ("header_dev", i32, (16,)), ("orb_ptr", i32, (B + 1,)), ("pack_ptr", torch.int64, (B + 1,)), ("order", i32, (B,)), ("status", i32, (B,)),
+            ("info", i32, (B,)), ("iters", i32, (B,)), ("eps", f64, (M,)), ("coeff", f64, (P,)), ("work", f64, (P,)), ("chol", f64, (P,))), device)
         op32 = np.ascontiguousarray(op.astype(np.int32))
         out = (C.c_int32 * 2)()
         with torch.cuda.device(device):
-            _lib.check(lib.nq_orb_init(_lib.ptr(self.buf), nbytes, op32.ctypes.data_as(C.c_void_p), *self._dims, out, _lib.stream_ptr()))
+            _lib.check(_lib.load().nq_orb_init(_lib.ptr(self.buf), nbytes, op32.ctypes.data_as(C.c_void_p), *self._dims, out, _lib.stream_ptr()))
         self.max_m = int(out[0])
-        B, M, P = self._dims
-        shapes = {"header": (torch.int32, (16,)), "orb_ptr": (torch.int32, (B + 1,)), "pack_ptr": (torch.int64, (B + 1,)), "order": (torch.int32, (B,)),
-                  "status": (torch.int32, (B,)), "info": (torch.int32, (B,)), "iters": (torch.int32, (B,)), "eps": (torch.float64, (M,)),
-                  "coeff": (torch.float64, (P,)), "work": (torch.float64, (P,)), "chol": (torch.float64, (P,))}
-        for i, name in enumerate(_PARTS):
-            dtype, shape = shapes[name]
-            count = int(np.prod(shape))
-            size = torch.empty(0, dtype=dtype).element_size()
-            setattr(self, name if name != "header" else "header_dev", self.buf[off[i]:off[i] + count * size].view(dtype).view(shape))
 
     def solve(self, H_packed: torch.Tensor, S_packed: Optional[torch.Tensor] = None):
         H = _packed(H_packed, self.P, "H_packed")
@@ -156,7 +143,7 @@ class OrbitalState:
 
     def header(self) -> dict:
         """The header words (one small device->host copy, synchronises the stream); raises if a call was refused on the device."""
-        h = self.header_dev.cpu().tolist()
+        h = self._read_header()
         if h[4] == -2:
             raise RuntimeError("an nq_orb call came with other dimensions than nq_orb_init prepared the state for")
         return dict(B=h[0], M=h[1], P=(h[2] & 0xffffffff) + (h[3] << 32), status=h[4], max_m=h[5])

@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._devstate import DeviceState, batch_ptr_host, fixed_to_uint8, require_forces, require_positions
 from .md import AMU_SI, E_H_SI, SYMBOLS, masses_for
 from .trainer import Batch
 
@@ -48,8 +49,6 @@ HARTREE_TO_EV = E_H_SI / E_SI
 
 MAX_DOF = 576                 # 3 n_free per molecule; AT it the one-workgroup global-memory eigensolver takes 4 s per molecule (profiles/vib_step.json)
 LDS_MAX_DOF = 141             # the matrix and the rotation parameters fit one workgroup's 160 KiB of LDS
-_PARTS = ("header", "mol_ptr", "dof_ptr", "hess_ptr", "order", "free_atom", "disp_mol", "disp_off", "im", "r", "h", "asymmetry", "sweeps", "status", "omega2",
-          "work", "hessian", "modes")
 
 
 def plan(ptr, fixed=None):
@@ -57,10 +56,7 @@ def plan(ptr, fixed=None):
     ``disp_off`` [D+1] (image atoms before each displacement), ``D``, ``P``."""
     ptr = np.asarray(ptr, dtype=np.int64)
     N, B = int(ptr[-1]), ptr.shape[0] - 1
-    free = np.ones(N, dtype=bool)
-    if fixed is not None:
-        f = np.asarray(fixed.cpu() if isinstance(fixed, torch.Tensor) else fixed)
-        free[f] = False                                                  # indices or a boolean mask
+    free = np.ones(N, dtype=bool) if fixed is None else fixed_to_uint8(fixed, N) == 0
     n = np.diff(ptr)
     mol = np.repeat(np.arange(B), n)
     nf = np.bincount(mol[free], minlength=B)
@@ -80,15 +76,11 @@ def chunks(pl, images_per_call: int):
 
 
 # ---- device state -----------------------------------------------------------------------------------------------------------------------
-class VibState:
+class VibState(DeviceState):
     """One caller-owned device buffer behind ``nq_vib_*`` plus typed views of its parts (include/nablaq.h)."""
 
     def __init__(self, ptr_host: Sequence[int], pos: torch.Tensor, masses, fixed=None):
-        lib = _lib.load()
-        if not pos.is_cuda:
-            raise RuntimeError("nabladft_amd.vibrations runs on MI355X only (no CPU fallback): move the batch to cuda")
-        if pos.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"positions must be float32 or float64, not {pos.dtype}")
+        require_positions(pos, "vibrations")
         ptr32 = np.ascontiguousarray(np.asarray(ptr_host, dtype=np.int32))
         self.plan = pl = plan(ptr32, fixed)
         self.B, self.N, self.D, self.P = pl["B"], int(pos.shape[0]), pl["D"], pl["P"]
@@ -99,31 +91,19 @@ class VibState:
         if masses.shape[0] != self.N:
             raise ValueError(f"masses has {masses.shape[0]} entries for {self.N} atoms")
         fixed_host = np.ascontiguousarray((~pl["free"]).astype(np.uint8)) if fixed is not None else None
-        self._dims = (self.N, self.B, self.D, self.P)
-        nbytes = lib.nq_vib_state_bytes(*self._dims)
-        if nbytes == 0:
-            raise _lib.NablaqError(_lib.NQ_ERR_ARG, lib.nq_last_error().decode(errors="replace"))
-        off = (C.c_size_t * len(_PARTS))()
-        _lib.check(lib.nq_vib_state_layout(*self._dims, off))
-        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=pos.device)
+        N, B, D, P, i32, i64, f64 = self.N, self.B, self.D, self.P, torch.int32, torch.int64, torch.float64
+        nbytes = self._allocate("vib", (N, B, D, P), (
+            ("header_dev", i32, (16,)), ("mol_ptr", i32, (B + 1,)), ("dof_ptr", i32, (B + 1,)), ("hess_ptr", i64, (B + 1,)), ("order", i32, (B,)),
+            ("free_atom", i32, (D // 3,)), ("disp_mol", i32, (D,)), ("disp_off", i64, (D + 1,)), ("im", f64, (D,)), ("r", f64, (N, 3)), ("h", f64, (D,)),
+            ("asymmetry", f64, (B,)), ("sweeps", i32, (B,)), ("status", i32, (B,)), ("omega2", f64, (D,)), ("work", f64, (P,)), ("hessian", f64, (P,)),
+            ("modes", f64, (P,))), pos.device)
         pos = pos.contiguous()
         out = (C.c_int32 * 3)()
         hp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        _lib.check(lib.nq_vib_init(_lib.ptr(self.buf), nbytes, hp(ptr32), hp(masses), hp(fixed_host), *self._dims, _lib.ptr(pos),
-                                   int(pos.dtype == torch.float64), out, _lib.stream_ptr()))
+        _lib.check(_lib.load().nq_vib_init(_lib.ptr(self.buf), nbytes, hp(ptr32), hp(masses), hp(fixed_host), *self._dims, _lib.ptr(pos),
+                                           int(pos.dtype == torch.float64), out, _lib.stream_ptr()))
         self.n_lds, self.max_m_lds, self.max_m = out[0], out[1], out[2]
         self.masses_host = masses
-        N, B, D, P = self._dims
-        shapes = {"header": (torch.int32, (16,)), "mol_ptr": (torch.int32, (B + 1,)), "dof_ptr": (torch.int32, (B + 1,)), "hess_ptr": (torch.int64, (B + 1,)),
-                  "order": (torch.int32, (B,)), "free_atom": (torch.int32, (D // 3,)), "disp_mol": (torch.int32, (D,)), "disp_off": (torch.int64, (D + 1,)),
-                  "im": (torch.float64, (D,)), "r": (torch.float64, (N, 3)), "h": (torch.float64, (D,)), "asymmetry": (torch.float64, (B,)),
-                  "sweeps": (torch.int32, (B,)), "status": (torch.int32, (B,)), "omega2": (torch.float64, (D,)), "work": (torch.float64, (P,)),
-                  "hessian": (torch.float64, (P,)), "modes": (torch.float64, (P,))}
-        for i, name in enumerate(_PARTS):
-            dtype, shape = shapes[name]
-            count = int(np.prod(shape))
-            size = torch.empty(0, dtype=dtype).element_size()
-            setattr(self, name if name != "header" else "header_dev", self.buf[off[i]:off[i] + count * size].view(dtype).view(shape))
 
     def image_atoms(self, c0: int, c1: int) -> int:
         return int(self.plan["disp_off"][c1] - self.plan["disp_off"][c0])
@@ -142,9 +122,7 @@ class VibState:
         if not (0 <= c0 < c1 <= self.D):
             raise ValueError(f"chunk [{c0}, {c1}) outside the {self.D} displacements")
         n = self.image_atoms(c0, c1)
-        if forces.dtype not in (torch.float32, torch.float64) or tuple(forces.shape) != (n, 3) or forces.device != self.buf.device:
-            raise ValueError(f"forces must be a float32 / float64 [{n}, 3] tensor on {self.buf.device}")
-        forces = forces.contiguous()
+        forces = require_forces(forces, n, self.buf.device)
         _lib.check(_lib.load().nq_vib_accumulate(_lib.ptr(self.buf), *self._dims, int(c0), int(c1), _lib.ptr(forces), int(forces.dtype == torch.float64), n,
                                                  _lib.stream_ptr()))
 
@@ -157,7 +135,7 @@ class VibState:
 
     def header(self) -> dict:
         """The header words (one small device->host copy, synchronises the stream)."""
-        h = self.header_dev.cpu().tolist()
+        h = self._read_header()
         if h[5] == -2:
             raise RuntimeError("an nq_vib call came with other dimensions than nq_vib_init prepared the state for")
         if h[5] == -3:
@@ -194,8 +172,7 @@ class BatchedVibrations:
 
     def prepare(self, batch) -> VibState:
         """The state, the chunk list and the device-side plan of the image batches (the only host-side planning of a run)."""
-        ptr = batch.ptr.cpu().numpy() if getattr(batch, "ptr", None) is not None else np.concatenate([[0], np.cumsum(np.bincount(batch.batch.cpu().numpy()))])
-        st = self.state = VibState(ptr, batch.pos, masses_for(batch.z, self.masses), self.fixed_atoms_mask)
+        st = self.state = VibState(batch_ptr_host(batch), batch.pos, masses_for(batch.z, self.masses), self.fixed_atoms_mask)
         pl, dev = st.plan, batch.pos.device
         self.todo = chunks(pl, self.images_per_call)
         cap = max([st.image_atoms(c0, c1) for c0, c1 in self.todo] or [0])
