@@ -770,7 +770,7 @@ int nq_vib_accumulate(void* state, int32_t N, int32_t B, int32_t D, int64_t P, i
 int nq_vib_finish(void* state, int32_t N, int32_t B, int32_t D, int64_t P, void* stream);
 int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t n_lds, int32_t max_m_lds, int32_t max_m, int32_t scale_modes, void* stream);
 
-/* ---- Batched orbital energies: the generalized symmetric eigenproblem H C = S C diag(eps) (csrc/orbitals.hip; entry points added, ABI 17 unchanged) --------
+/* ---- Batched orbital energies: the generalized symmetric eigenproblem H C = S C diag(eps) (csrc/orbitals.hip, csrc/orbdens.hip; entry points added, ABI 17 unchanged) --------
  * Fills: the `orbital_energies` / `orbital_coefficients` slots that phisnet/nn/neural_network.py:969-993 returns as zeros (every entry point below serves
  * those lines), plus the HOMO / LUMO figures and the occupied-orbital errors the Hamiltonian papers report beside the matrix MAE.
  * Layout: B molecules, molecule b has m_b = orb_ptr[b+1] - orb_ptr[b] orbitals, 1 <= m_b <= 1024 (NQ_ERR_MOL_TOO_LARGE above, before any device work),
@@ -793,6 +793,21 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  * nq_orb_compare: a predicted against a target solution of the same batch (two states of the same dimensions, or the same state twice) under a common S ->
  * out [7][B]: mean |eps - eps^| over the occupied orbitals, the same over all orbitals, mean over the occupied orbitals of |c_k^T S c^_k|, |d homo|, |d lumo|,
  * |d gap|, min over the occupied orbitals of |c_k^T S c^_k|.  Overwrites the `work` part of state_pred (the full symmetric S).
+ * nq_orb_wgram (csrc/orbdens.hip): the weighted Gram product of the coefficient rows a solve left in the state,
+ *   out[pack_ptr[b] + i m_b + j] = sum_{k = lo_b .. hi_b - 1} w[orb_ptr[b] + k] C_b[k][i] C_b[k][j],
+ * for one weight vector w0 [M] or two (w1 [M] -> out1, from the same operand loads); k_lo / k_hi int32 [B] on the device, NULL: 0 and m_b (values outside
+ * 0..m_b are clamped); out0 / out1 [P], packed like coeff.  w = dL/d eps gives dL/dH and w = -eps dL/d eps gives dL/dS (d eps_k = c_k^T (dH - eps_k dS) c_k:
+ * no difference of eigenvalues is divided by), both as the symmetric matrix sum_k g_k c_k c_k^T -- the gradient with respect to a symmetric input, the
+ * convention of torch.linalg.eigh; w = 2 and w = 2 eps with k_hi = n_occ give the density matrix D and the energy-weighted density W.  One launch, one
+ * workgroup per (molecule, 64 x 64 lower-triangle tile), v_mfma_f64_16x16x4_f64, no atomics; only j <= i is computed and written to (i, j) and (j, i): the
+ * result is exactly symmetric, bitwise reproducible and independent of the rest of the batch.  A molecule with status != 0 gets NaN in its block, an empty
+ * range zeros.  out1 is not touched when w1 is NULL; w1 without out1 is refused.
+ * nq_orb_population (csrc/orbdens.hip): D [P] (a density matrix packed like coeff; any array of that layout) -> out_atom_pop [N] = sum over the atom's
+ * orbitals of pop_mu = sum_nu D_mu,nu S_mu,nu (Mulliken), out_nelec [B] = sum_mu pop_mu = Tr(D S), out_eband [B] (NULL: skipped; needs H) = sum_mu,nu D_mu,nu
+ * H_mu,nu = Tr(D H).  mol_ptr int32 [B+1] (atoms of molecule b) and atom_orb_ptr int64 [N+1] (first orbital of every atom, counted over the batch) are the
+ * plan's mol_ptr / orb_ptr (nq_hblock_tables); an atom whose range leaves its molecule gets NaN.  Only the lower triangles of S and H are read; S = NULL: the
+ * identity, pop = diag(D).  One workgroup per molecule, fixed summation orders, no atomics.
+ * Both serve the same lines as the solver: they differentiate and post-process the `orbital_energies` / `orbital_coefficients` of neural_network.py:969-993.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
 size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P);
 int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host);
@@ -801,6 +816,11 @@ int nq_orb_solve(void* state, int32_t B, int32_t M, int64_t P, const void* H, in
 int nq_orb_frontier(void* state, int32_t B, int32_t M, int64_t P, const int32_t* n_occ, double* out_homo, double* out_lumo, double* out_gap, void* stream);
 int nq_orb_compare(void* state_pred, void* state_target, int32_t B, int32_t M, int64_t P, const void* S_or_null, int32_t s_f64, const int32_t* n_occ, double* out,
                    void* stream);
+int nq_orb_wgram(void* state, int32_t B, int32_t M, int64_t P, const double* w0, const double* w1_or_null, const int32_t* k_lo_or_null, const int32_t* k_hi_or_null,
+                 double* out0, double* out1_or_null, void* stream);
+int nq_orb_population(void* state, int32_t B, int32_t M, int64_t P, const double* D, const void* H_or_null, int32_t h_f64, const void* S_or_null, int32_t s_f64,
+                      int32_t N, const int32_t* mol_ptr, const int64_t* atom_orb_ptr, double* out_atom_pop, double* out_nelec, double* out_eband_or_null,
+                      void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

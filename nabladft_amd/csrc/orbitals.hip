@@ -29,50 +29,11 @@
 #include <math.h>
 #include <vector>
 
-#include "../../include/nablaq.h"
-#include "devstate.h"
+#include "orbstate.h"   // the state's parts, OrbArgs, orb_dims_ok, orb_block_sum, orb_check_dims, orb_args: shared with orbdens.hip
 
-#define NQ_ORB_MAX_M 1024
-#define NQ_ORB_NT 512
-#define NQ_ORB_NW (NQ_ORB_NT / 64)
 #define NQ_ORB_MAX_ITER 60
-#define NQ_ORB_HDR 16
 // dynamic LDS of k_orb_solve: d e tau v p [1024 each], 16 scalars, 8 control words
 #define NQ_ORB_LDS_BYTES ((5 * NQ_ORB_MAX_M + 16) * 8 + 8 * 4)
-
-enum { OH_B = 0, OH_M, OH_PLO, OH_PHI, OH_STATUS, OH_MAXM };
-enum { OP_HDR = 0, OP_ORB_PTR, OP_PACK_PTR, OP_ORDER, OP_STATUS, OP_INFO, OP_ITERS, OP_EPS, OP_COEFF, OP_WORK, OP_CHOL, OP_PARTS };
-typedef NqStateLayout<OP_PARTS> OrbLayout;
-
-static OrbLayout orb_layout(long B, long M, long long P) {
-  const size_t bytes[OP_PARTS] = {NQ_ORB_HDR * 4, (size_t)(B + 1) * 4, (size_t)(B + 1) * 8, (size_t)B * 4, (size_t)B * 4, (size_t)B * 4, (size_t)B * 4,
-                                  (size_t)M * 8, (size_t)P * 8, (size_t)P * 8, (size_t)P * 8};
-  return nq_state_layout(bytes);
-}
-
-struct OrbArgs {
-  int* hdr; const int* orb_ptr; const long long* pack_ptr; const int* order; int* status; int* info; int* iters; double* eps; double* coeff; double* work;
-  double* chol;
-  int B, M; long long P;
-};
-
-__device__ __forceinline__ bool orb_dims_ok(const OrbArgs& a) {
-  const bool ok = a.hdr[OH_B] == a.B && a.hdr[OH_M] == a.M && nq_split64_is(a.hdr + OH_PLO, a.P);
-  if (!ok && blockIdx.x == 0 && threadIdx.x == 0) a.hdr[OH_STATUS] = -2;   // not the state nq_orb_init prepared: touch nothing else
-  return ok;
-}
-
-// the wavefronts' partial sums meet in red[NQ_ORB_NW] and are added in wavefront order; every thread returns what it read from LDS (uniform)
-__device__ __forceinline__ double orb_block_sum(double v, double* red) {
-  v = nq_wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = 0.0;
-#pragma unroll
-  for (int w = 0; w < NQ_ORB_NW; ++w) r += red[w];
-  __syncthreads();
-  return r;
-}
 
 __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_solve(OrbArgs a, const void* H, int h_f64, const void* S, int s_f64) {
   extern __shared__ double sm[];
@@ -508,25 +469,6 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_compare(OrbArgs a, OrbArgs t,
     out[5L * B + b] = fabs((la - ha) - (lt - ht));
     out[6L * B + b] = simmin;
   }
-}
-
-static int orb_check_dims(int32_t B, int32_t M, int64_t P) {
-  if (B < 1) return nq_fail(NQ_ERR_ARG, "nq_orb: empty batch (B=%d)", B);
-  if (M < B || (int64_t)M > (int64_t)B * NQ_ORB_MAX_M) return nq_fail(NQ_ERR_ARG, "nq_orb: M=%d orbitals do not fit B=%d molecules of 1..%d", M, B, NQ_ORB_MAX_M);
-  if (P < M || P > (int64_t)M * NQ_ORB_MAX_M) return nq_fail(NQ_ERR_ARG, "nq_orb: P=%lld does not fit M=%d", (long long)P, M);
-  return NQ_OK;
-}
-
-static OrbArgs orb_args(void* state, int32_t B, int32_t M, int64_t P) {
-  const OrbLayout L = orb_layout(B, M, P);
-  char* s = (char*)state;
-  OrbArgs a;
-  a.hdr = (int*)(s + L.part[OP_HDR]); a.orb_ptr = (const int*)(s + L.part[OP_ORB_PTR]); a.pack_ptr = (const long long*)(s + L.part[OP_PACK_PTR]);
-  a.order = (const int*)(s + L.part[OP_ORDER]); a.status = (int*)(s + L.part[OP_STATUS]); a.info = (int*)(s + L.part[OP_INFO]);
-  a.iters = (int*)(s + L.part[OP_ITERS]); a.eps = (double*)(s + L.part[OP_EPS]); a.coeff = (double*)(s + L.part[OP_COEFF]);
-  a.work = (double*)(s + L.part[OP_WORK]); a.chol = (double*)(s + L.part[OP_CHOL]);
-  a.B = B; a.M = M; a.P = P;
-  return a;
 }
 
 extern "C" {

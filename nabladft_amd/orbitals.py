@@ -1,5 +1,5 @@
 """Batched orbital energies on the GPU: the generalized symmetric eigenproblem ``H C = S C diag(eps)`` of every molecule of a batch in one launch
-(csrc/orbitals.hip, ``nq_orb_*`` of include/nablaq.h).
+(csrc/orbitals.hip, csrc/orbdens.hip, ``nq_orb_*`` of include/nablaq.h).
 
 Fills what the reference leaves empty: ``phisnet/nn/neural_network.py:969-993`` returns ``orbital_energies`` and ``orbital_coefficients`` as zeros.  Parity
 status: **no reference code to pin against** -- the kernels are tested against a float64 numpy restatement of the textbook route (tests/orbitals_ref.py:
@@ -11,7 +11,12 @@ symmetrised; Householder tridiagonalisation; implicit-shift QL with the vectors 
 molecule's block = orbital k (``C^T S C = I``; the largest-magnitude component of every orbital, the first on ties, is positive).  ``per_molecule()`` hands
 the user orbitals as COLUMNS, the convention of ``scipy.linalg.eigh``.
 
-No gradient flows through the solver: inputs are detached.  (Gradients of an eigen-decomposition are out of scope; a loss on orbital energies needs them.)
+No gradient flows through the solver: the inputs of ``BatchedOrbitals`` are detached.  A loss on orbital energies needs the gradient of the eigenvalues: that is
+``nabladft_amd.orbital_loss`` (``orbital_energies``, ``OrbitalEnergyLoss``, ``QHNetOrbitalLightning``), built on this class.  Gradients through the eigenvectors
+stay out of scope.
+
+After a solve, ``density(n_occ)`` gives the closed-shell density matrix ``D = 2 sum_occ c_k c_k^T`` (and the energy-weighted one) and ``populations(D, plan, S)``
+the Mulliken populations per atom, the electron count ``Tr(D S)`` and the band energy ``Tr(D H)`` (csrc/orbdens.hip), all on the device.
 
 Limits (each raises, nothing degrades silently): 1..``MAX_ORBITALS`` = 1024 orbitals per molecule; closed shells only (``occupied_counts`` refuses an odd
 electron count); MI355X only, no CPU path.
@@ -156,7 +161,9 @@ class BatchedOrbitals:
     ``solve(H_packed, S_packed=None)`` launches the solver on the current stream and returns ``self``; nothing is read back.  ``energies`` [M] and
     ``coefficients`` [P] stay on the device (float64; row k of a molecule's block = orbital k).  ``per_molecule()`` -> (list of [m], list of [m, m] with the
     orbitals as columns).  ``frontier(n_occ)`` -> (homo, lumo, gap), float64 [B] on the device.  ``check()`` reads the status once (a host synchronisation)
-    and raises ``RuntimeError`` naming the molecule and the pivot where S was not positive definite.  Inputs are detached: no gradient flows through."""
+    and raises ``RuntimeError`` naming the molecule and the pivot where S was not positive definite.  Inputs are detached: no gradient flows through
+    (``nabladft_amd.orbital_loss.orbital_energies`` is the differentiable call).  ``density(n_occ)`` / ``populations(D, plan, S, H)`` / ``weighted_gram(w)``:
+    density matrices, Mulliken populations and weighted Gram products of the solved coefficients, on the device."""
 
     def __init__(self, orb_ptr, device="cuda"):
         self.state = OrbitalState(orb_ptr, device)
@@ -210,6 +217,66 @@ class BatchedOrbitals:
             _lib.check(_lib.load().nq_orb_compare(_lib.ptr(st.buf), _lib.ptr(tt.buf), *st._dims, _lib.ptr(S), int(S is not None and S.dtype == torch.float64),
                                                   _lib.ptr(no), _lib.ptr(out), _lib.stream_ptr()))
         return out
+
+    def weighted_gram(self, w0: torch.Tensor, w1: Optional[torch.Tensor] = None, k_lo=None, k_hi=None):
+        """``X_b = sum_{k in [lo_b, hi_b)} w[k] c_k c_k^T`` of every molecule from the coefficients of the last solve, one launch (``nq_orb_wgram``): packed float64
+        [P], exactly symmetric; with ``w1`` a pair from the same operand loads.  ``w*``: float64 [M] on the device; ``k_lo`` / ``k_hi``: int32 [B] on the device or
+        None (0 and m).  A molecule the solver failed on gets NaN.  Nothing is read back."""
+        st, dev = self.state, self.state.buf.device
+        ws = []
+        for name, w in (("w0", w0), ("w1", w1)):
+            if w is None:
+                ws.append(None)
+                continue
+            _require_gpu(w)
+            if w.dtype != torch.float64 or w.numel() != st.M or w.device != dev:
+                raise ValueError(f"{name} must be float64 [{st.M}] on {dev}")
+            ws.append(w.detach().reshape(-1).contiguous())
+        ks = []
+        for name, k in (("k_lo", k_lo), ("k_hi", k_hi)):
+            if k is not None and (not isinstance(k, torch.Tensor) or k.dtype != torch.int32 or k.numel() != st.B or k.device != dev):
+                raise ValueError(f"{name} must be an int32 [{st.B}] tensor on {dev}")
+            ks.append(None if k is None else k.contiguous())
+        out0 = torch.empty(st.P, dtype=torch.float64, device=dev)
+        out1 = None if ws[1] is None else torch.empty(st.P, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().nq_orb_wgram(_lib.ptr(st.buf), *st._dims, _lib.ptr(ws[0]), _lib.ptr(ws[1]), _lib.ptr(ks[0]), _lib.ptr(ks[1]), _lib.ptr(out0),
+                                                _lib.ptr(out1), _lib.stream_ptr()))
+        return out0 if out1 is None else (out0, out1)
+
+    def density(self, n_occ, energy_weighted: bool = False):
+        """The closed-shell density matrix ``D = 2 sum_{k < n_occ} c_k c_k^T`` of every molecule, packed float64 [P] like the input; with ``energy_weighted`` also
+        ``W = 2 sum_{k < n_occ} eps_k c_k c_k^T`` -> ``(D, W)``.  ``n_occ``: [B], checked on the host against the orbital counts."""
+        st = self.state
+        no = torch.from_numpy(check_occupied(n_occ, st.orb_ptr_host)).to(st.buf.device)
+        two = torch.full((st.M,), 2.0, dtype=torch.float64, device=st.buf.device)
+        return self.weighted_gram(two, 2.0 * st.eps if energy_weighted else None, None, no)
+
+    def populations(self, D: torch.Tensor, plan, S_packed: Optional[torch.Tensor] = None, H_packed: Optional[torch.Tensor] = None):
+        """Mulliken analysis of a packed density ``D`` -> ``(atom_pop [N], nelec [B], eband [B] or None without H_packed)``, float64 on the device:
+        ``pop_mu = sum_nu D_mu,nu S_mu,nu`` summed over each atom's orbitals, ``nelec = Tr(D S)``, ``eband = Tr(D H)``.  ``plan``: the ``BlockAssembler`` /
+        ``IrrepsAssembler`` plan of the batch (its ``mol_ptr`` and per-atom ``orb_ptr``).  ``S_packed = None``: the identity."""
+        st, dev = self.state, self.state.buf.device
+        Dp = _packed(D, st.P, "D")
+        if Dp.dtype != torch.float64:
+            raise TypeError("D must be float64 (what density() returns)")
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        H = None if H_packed is None else _packed(H_packed, st.P, "H_packed")
+        if int(plan.B) != st.B or int(plan.m_total) != st.M or int(plan.total) != st.P:
+            raise ValueError("the plan belongs to another batch")
+        mol_ptr = plan.mol_ptr.to(device=dev, dtype=torch.int32).contiguous()
+        atom_ptr = plan.orb_ptr.to(device=dev, dtype=torch.int64).contiguous()
+        N = int(plan.N)
+        if mol_ptr.numel() != st.B + 1 or atom_ptr.numel() != N + 1:
+            raise ValueError("the plan's mol_ptr / orb_ptr do not have B + 1 / N + 1 entries")
+        pop = torch.empty(N, dtype=torch.float64, device=dev)
+        nelec = torch.empty(st.B, dtype=torch.float64, device=dev)
+        eband = None if H is None else torch.empty(st.B, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().nq_orb_population(_lib.ptr(st.buf), *st._dims, _lib.ptr(Dp), _lib.ptr(H), int(H is not None and H.dtype == torch.float64),
+                                                     _lib.ptr(S), int(S is not None and S.dtype == torch.float64), N, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
+                                                     _lib.ptr(pop), _lib.ptr(nelec), _lib.ptr(eband), _lib.stream_ptr()))
+        return pop, nelec, eband
 
     def check(self) -> "BatchedOrbitals":
         st = self.state
@@ -275,4 +342,12 @@ class OrbitalErrors:
         return dict(zip(FIGURES, mean))
 
 
-__all__ = ["BatchedOrbitals", "OrbitalState", "OrbitalErrors", "occupied_counts", "check_occupied", "MAX_ORBITALS", "FIGURES"]
+def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
+    """Mulliken charges ``q_A = Z_A - pop_A`` (float64 [N], on the device of ``atom_pop``) from the populations of ``BatchedOrbitals.populations``."""
+    zz = z if isinstance(z, torch.Tensor) else torch.as_tensor(np.asarray(z))
+    if zz.numel() != atom_pop.numel():
+        raise ValueError(f"z has {zz.numel()} atoms, atom_pop {atom_pop.numel()}")
+    return zz.to(device=atom_pop.device, dtype=torch.float64).reshape(-1) - atom_pop.to(torch.float64)
+
+
+__all__ = ["BatchedOrbitals", "OrbitalState", "OrbitalErrors", "occupied_counts", "check_occupied", "mulliken_charges", "MAX_ORBITALS", "FIGURES"]

@@ -581,6 +581,7 @@ class NeuralNetwork(nn.Module):
         self.calculate_energy = self.predict_energy = self.calculate_forces = False
         self.create_graph = True                       # neural_network.py:93; forces need False here (first-order adjoints only)
         self.calculate_orbitals = False                # opt-in: fill orbital_energies / orbital_coefficients (neural_network.py:969-993 leaves them zero)
+        self.orbital_gradients = False                 # opt-in beside calculate_orbitals: orbital_energies carry a grad_fn (orbital_loss.orbital_energies)
         self.max_orbitals, self.order, self.num_features, self.num_basis_functions = max_orbitals, order, num_features, num_basis_functions
         self.num_modules, self.cutoff, self.activation, self.Zmax = num_modules, cutoff, activation, Zmax
         order_max = max(l for orbs in max_orbitals for _, l in orbs)
@@ -787,10 +788,16 @@ class NeuralNetwork(nn.Module):
         else:
             results["forces"] = torch.zeros_like(R)
         if getattr(self, "calculate_orbitals", False) and self.calculate_full_hamiltonian:
-            # H C = S C diag(eps) of every molecule on the device (orbitals.py); S = None (the identity) when the overlap head is off.  Detached: no gradient.
-            from .orbitals import BatchedOrbitals
-            orb = BatchedOrbitals(plan, R.device).solve(results["full_hamiltonian_packed"], results.get("overlap_matrix_packed"))
-            results["orbital_energies"] = orb.energies.to(R.dtype).view(1, norb)
+            # H C = S C diag(eps) of every molecule on the device (orbitals.py); S = None (the identity) when the overlap head is off.  Detached: no gradient,
+            # unless orbital_gradients asks for the eigenvalues' (orbital_loss.py; the coefficients stay detached either way).
+            if getattr(self, "orbital_gradients", False):
+                from .orbital_loss import orbital_energies
+                eps, orb = orbital_energies(results["full_hamiltonian_packed"], results.get("overlap_matrix_packed"), plan, return_solution=True)
+            else:
+                from .orbitals import BatchedOrbitals
+                orb = BatchedOrbitals(plan, R.device).solve(results["full_hamiltonian_packed"], results.get("overlap_matrix_packed"))
+                eps = orb.energies
+            results["orbital_energies"] = eps.to(R.dtype).view(1, norb)
             results["orbital_coefficients"] = orb.dense_coefficients(R.dtype).unsqueeze(0)      # block-diagonal, the orbitals as columns of each block
             results["orbitals"] = orb                                                            # the float64 solution, its status and iteration counts
         else:
