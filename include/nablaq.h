@@ -808,6 +808,25 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  * plan's mol_ptr / orb_ptr (nq_hblock_tables); an atom whose range leaves its molecule gets NaN.  Only the lower triangles of S and H are read; S = NULL: the
  * identity, pop = diag(D).  One workgroup per molecule, fixed summation orders, no atomics.
  * Both serve the same lines as the solver: they differentiate and post-process the `orbital_energies` / `orbital_coefficients` of neural_network.py:969-993.
+ * The density response (csrc/orbresp.hip; entry points added, ABI 17 unchanged): the gradient of a loss on the closed-shell density D = 2 C_o C_o^T with respect to
+ * H and S, as four products on the coefficient rows of the state.  n_occ int32 [B] (device; clamped to 0..m_b), occ_ptr int64 [B+1] (device) with
+ * occ_ptr[b+1] - occ_ptr[b] >= n_occ_b m_b and O = occ_ptr[B] <= P: the "occupied-packed" layout of the caller-owned scratch arrays T, A_H, A_S ([m_b][n_occ_b]
+ * row-major at occ_ptr[b]) and Rt_H, Rt_S ([n_occ_b][m_b]), O doubles each.  A block that does not lie inside [0, O) is not touched.
+ *   nq_orb_resp_project: G [P] = dL/dD (need not be symmetric) -> Gs [P] = (G + G^T) / 2 (a scratch array, not G itself) and T = Gs C_o.
+ *   nq_orb_resp_mo: W = C^T T -> A_H[k][i] = 4 W / (eps_i - eps_k) for k >= n_occ, 0 below; A_S[k][i] (NULL: skipped) = -eps_i A_H for k >= n_occ, -2 W below.
+ *     The only division: by occupied-virtual differences.  Equal levels inside the occupied or inside the virtual orbitals are harmless; a vanishing
+ *     HOMO-LUMO gap gives inf / NaN in that molecule's block only.
+ *   nq_orb_resp_back: Rt_H[i][mu] = sum_k A_H[k][i] C[mu][k], and Rt_S from A_S (NULL: skipped) out of the same loads of the coefficients.  A_H must be
+ *     zero over k < n_occ, as nq_orb_resp_mo writes it: without A_S the sum starts at the multiple of 4 below n_occ.
+ *   nq_orb_syr2k: out[mu][nu] = 1/2 sum_{i < n_occ} (Rt[i][mu] C[nu][i] + C[mu][i] Rt[i][nu]) [P] for Rt0 and, from the same loads, Rt1 (NULL: skipped):
+ *     Rt_H -> dL/dH, Rt_S -> dL/dS, symmetric matrices in the convention of nq_orb_wgram.  Lower-triangle 64 x 64 tiles mirrored: exactly symmetric.
+ * All float64 on v_mfma_f64_16x16x4_f64, 64 x 64 output tiles, operands staged through LDS, the grid sized from (B, M, P), no atomics, a fixed summation order:
+ * bitwise reproducible and independent of the rest of the batch.  status != 0: NaN in the molecule's own block of every output; n_occ = 0 or no virtual
+ * orbital: zeros.  A second input without a second output is refused.
+ * nq_orb_population_backward: the reverse of nq_orb_population.  g_pop [N], g_nelec [B], g_eband [B] (each NULL: zero) ->
+ *   out_gD_ij = ((g_A(i) + g_A(j)) / 2 + g_nelec) S_ij + g_eband H_ij (S = NULL: the identity), and on request (NULL: skipped)
+ *   out_gS_ij = ((g_A(i) + g_nelec) D_ij + (g_A(j) + g_nelec) D_ji) / 2 (needs S and D) and out_gH_ij = g_eband (D_ij + D_ji) / 2 (needs H and D):
+ *   the gradients with respect to symmetric D, S and H, spread over both triangles; like the forward kernel only the lower triangles of S and H are read.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
 size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P);
 int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host);
@@ -821,6 +840,18 @@ int nq_orb_wgram(void* state, int32_t B, int32_t M, int64_t P, const double* w0,
 int nq_orb_population(void* state, int32_t B, int32_t M, int64_t P, const double* D, const void* H_or_null, int32_t h_f64, const void* S_or_null, int32_t s_f64,
                       int32_t N, const int32_t* mol_ptr, const int64_t* atom_orb_ptr, double* out_atom_pop, double* out_nelec, double* out_eband_or_null,
                       void* stream);
+int nq_orb_resp_project(void* state, int32_t B, int32_t M, int64_t P, const int32_t* n_occ, const int64_t* occ_ptr, int64_t O, const double* G, double* Gs,
+                        double* T, void* stream);
+int nq_orb_resp_mo(void* state, int32_t B, int32_t M, int64_t P, const int32_t* n_occ, const int64_t* occ_ptr, int64_t O, const double* T, double* A_H,
+                   double* A_S_or_null, void* stream);
+int nq_orb_resp_back(void* state, int32_t B, int32_t M, int64_t P, const int32_t* n_occ, const int64_t* occ_ptr, int64_t O, const double* A_H,
+                     const double* A_S_or_null, double* Rt_H, double* Rt_S_or_null, void* stream);
+int nq_orb_syr2k(void* state, int32_t B, int32_t M, int64_t P, const int32_t* n_occ, const int64_t* occ_ptr, int64_t O, const double* Rt0,
+                 const double* Rt1_or_null, double* out0, double* out1_or_null, void* stream);
+int nq_orb_population_backward(void* state, int32_t B, int32_t M, int64_t P, const double* g_pop_or_null, const double* g_nelec_or_null,
+                               const double* g_eband_or_null, const double* D_or_null, const void* H_or_null, int32_t h_f64, const void* S_or_null, int32_t s_f64,
+                               int32_t N, const int32_t* mol_ptr, const int64_t* atom_orb_ptr, double* out_gD, double* out_gS_or_null, double* out_gH_or_null,
+                               void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

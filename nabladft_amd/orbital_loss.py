@@ -1,5 +1,6 @@
-"""Training on the spectrum: differentiable orbital energies of a predicted Hamiltonian, a loss on them, and the QHNet task that adds it to the matrix loss
-(csrc/orbdens.hip, ``nq_orb_wgram`` of include/nablaq.h, on top of nabladft_amd/orbitals.py).
+"""Training on the spectrum and on the occupied subspace: differentiable orbital energies, density matrices and Mulliken populations of a predicted
+Hamiltonian, losses on them, and the QHNet tasks that add them to the matrix loss (csrc/orbdens.hip, csrc/orbresp.hip, ``nq_orb_wgram`` / ``nq_orb_resp_*`` /
+``nq_orb_syr2k`` / ``nq_orb_population_backward`` of include/nablaq.h, on top of nabladft_amd/orbitals.py).
 
 Fills the same empty slots as the solver: ``phisnet/nn/neural_network.py:969-993`` returns ``orbital_energies`` as zeros, so the reference has nothing a loss on
 them could be compared with.  Parity status: **no reference code to pin against** -- the gradients are tested against ``torch.linalg`` autograd of the
@@ -18,8 +19,20 @@ coefficient rows the solver left on the device (float64 matrix instructions, exa
 assemblers (``BlockAssembler`` / ``IrrepsAssembler`` with ``symmetrize=True``) build ``H`` as ``X + X^T``, so the gradients of the network's parameters are the
 true ones.
 
-**Coefficients stay detached.**  No gradient flows through the eigenvectors: there is no loss on coefficients, densities or populations here
-(``BatchedOrbitals.density`` / ``populations`` are post-processing).
+**Eigenvectors.**  No gradient flows through the eigenvectors of ``orbital_energies``: its coefficients stay detached, and ``BatchedOrbitals.density`` /
+``populations`` are post-processing.  The occupied subspace is differentiated by ``orbital_solution`` / ``density_matrix`` below: the closed-shell density
+``D = 2 C_o C_o^T`` depends on the eigenvectors only through the occupied subspace, and with ``Gs = (G + G^T) / 2`` for ``G = dL/dD``
+
+    T = Gs C_o        W = C^T T        Z_ai = 4 W_ai / (eps_i - eps_a)   (a virtual, i occupied)
+    R_H = C_v Z       R_S = -C_v (Z o eps_i) - 2 C_o W_o
+    dL/dH = (R_H C_o^T + C_o R_H^T) / 2        dL/dS = (R_S C_o^T + C_o R_S^T) / 2
+
+(csrc/orbresp.hip: four float64 matrix-instruction launches on the coefficient rows the solver left on the device, bitwise reproducible, exactly symmetric).
+Only occupied-virtual differences are divided by: equal levels inside the occupied or inside the virtual orbitals are harmless, where the backward of
+``torch.linalg.eigh`` divides by every difference and returns garbage.  With every orbital occupied ``dL/dH`` is exactly zero and ``dL/dS`` is that of
+``D = 2 S^-1``.  **No gap regularisation, no clamping:** a vanishing HOMO-LUMO gap gives inf / NaN in that molecule's gradient block only;
+``BatchedOrbitals.frontier`` gives the gap to watch.  Tested against ``torch.linalg`` autograd of Cholesky -> reduce -> ``eigh`` -> ``D`` and against the
+closed form on a permuted copy (tests/orbital_density_ref.py).
 
 Limits (each raises, nothing degrades silently): what ``BatchedOrbitals`` has -- 1..1024 orbitals per molecule, closed shells, MI355X only, no CPU path.
 """
@@ -164,4 +177,203 @@ class QHNetOrbitalLightning(QHNetLightning):
         return self.hparams.metric({"hamiltonian": y_pred["hamiltonian"]}, {"hamiltonian": y_true["hamiltonian"]})
 
 
-__all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges"]
+class _OrbitalSolution(torch.autograd.Function):
+    """Forward: ONE ``BatchedOrbitals.solve`` and the density of its occupied orbitals.  Backward: ``nq_orb_wgram`` for the energies' upstream gradient plus the
+    response chain for the density's; a half without an upstream gradient is skipped, and so is the ``S`` half when ``S`` asks for nothing."""
+
+    @staticmethod
+    def forward(ctx, orb, H, S, n_occ):
+        orb.solve(H, S)
+        ctx.set_materialize_grads(False)
+        ctx.orb, ctx.n_occ = orb, n_occ
+        ctx.h = (H.shape, H.dtype)
+        ctx.s = None if S is None else (S.shape, S.dtype)
+        return orb.energies.clone(), orb.density(n_occ)
+
+    @staticmethod
+    def backward(ctx, g_eps, g_D):
+        orb = ctx.orb
+        want_h = ctx.needs_input_grad[1]
+        want_s = ctx.s is not None and ctx.needs_input_grad[2]
+        if (g_eps is None and g_D is None) or not (want_h or want_s):
+            return None, None, None, None
+        gH = gS = None
+        if g_eps is not None:
+            g = g_eps.to(torch.float64).reshape(-1).contiguous()
+            if want_s:
+                gH, gS = orb.weighted_gram(g, -(orb.energies * g))
+            else:
+                gH = orb.weighted_gram(g)
+        if g_D is not None:
+            rH, rS = orb.density_response(g_D.to(torch.float64).reshape(-1).contiguous(), ctx.n_occ, want_s)
+            gH = rH if gH is None else gH + rH
+            if want_s:
+                gS = rS if gS is None else gS + rS
+        return (None, gH.to(ctx.h[1]).view(ctx.h[0]) if want_h else None, gS.to(ctx.s[1]).view(ctx.s[0]) if want_s else None, None)
+
+
+def orbital_solution(H_packed: torch.Tensor, S_packed: Optional[torch.Tensor], plan_or_orb_ptr, n_occ, return_solution: bool = False):
+    """Orbital energies AND the closed-shell density matrix of every molecule from ONE solve -> ``(eps float64 [M], D float64 [P])`` on the device
+    (``return_solution=True``: ``(eps, D, BatchedOrbitals)``), both differentiable with respect to ``H_packed`` and ``S_packed``.
+
+    Arguments as for ``orbital_energies``; ``n_occ`` [B]: doubly occupied orbitals per molecule (``occupied_counts``), checked on the host.
+    ``D = 2 sum_{k < n_occ} c_k c_k^T`` is packed like the input and exactly symmetric.  The backward adds the ``nq_orb_wgram`` term of ``eps`` to the response
+    chain of ``D`` (module text; the upstream gradient of ``D`` need not be symmetric), skips whichever output has no upstream gradient, skips the ``S`` half
+    when ``S`` is None or requires no gradient, and casts the gradients to the inputs' dtypes.  The symmetric-matrix convention of ``orbital_energies``
+    holds.  **No gap regularisation and no clamping**: the response divides by ``eps_i - eps_a`` over occupied i and virtual a, so a vanishing HOMO-LUMO gap
+    gives inf / NaN in that molecule's gradient block only (``BatchedOrbitals.frontier`` returns the gap); degenerate levels inside the occupied or inside the
+    virtual orbitals are harmless.  A molecule the solver fails on yields NaN energies, density and gradient blocks, for that molecule only."""
+    _require_gpu(H_packed)
+    if S_packed is not None:
+        _require_gpu(S_packed)
+    orb = BatchedOrbitals(plan_or_orb_ptr, H_packed.device)
+    no = torch.from_numpy(check_occupied(n_occ, orb.orb_ptr))
+    eps, D = _OrbitalSolution.apply(orb, H_packed, S_packed, no)
+    return (eps, D, orb) if return_solution else (eps, D)
+
+
+def density_matrix(H_packed: torch.Tensor, S_packed: Optional[torch.Tensor], plan_or_orb_ptr, n_occ, return_solution: bool = False):
+    """``orbital_solution`` without the energies -> ``D`` float64 [P] (``return_solution=True``: ``(D, BatchedOrbitals)``); the backward is the response chain
+    alone."""
+    out = orbital_solution(H_packed, S_packed, plan_or_orb_ptr, n_occ, return_solution)
+    return out[1:] if return_solution else out[1]
+
+
+class _Populations(torch.autograd.Function):
+    """Forward: ``nq_orb_population``.  Backward: ``nq_orb_population_backward`` (one elementwise launch)."""
+
+    @staticmethod
+    def forward(ctx, orb, plan, D, S, H):
+        ctx.set_materialize_grads(False)
+        pop, nelec, eband = orb.populations(D, plan, S, H)
+        ctx.orb, ctx.plan = orb, plan
+        ctx.save_for_backward(D, S, H)
+        ctx.s = None if S is None else (S.shape, S.dtype)
+        ctx.h = None if H is None else (H.shape, H.dtype)
+        if eband is None:
+            eband = nelec.new_zeros(nelec.shape)             # a placeholder the caller drops: a Function returns tensors
+            ctx.mark_non_differentiable(eband)
+        return pop, nelec, eband
+
+    @staticmethod
+    def backward(ctx, g_pop, g_nelec, g_eband):
+        D, S, H = ctx.saved_tensors
+        want_s = ctx.s is not None and ctx.needs_input_grad[3]
+        want_h = ctx.h is not None and ctx.needs_input_grad[4]
+        if g_pop is None and g_nelec is None and g_eband is None:
+            return None, None, None, None, None
+        f64 = lambda g: None if g is None else g.to(torch.float64).reshape(-1).contiguous()
+        gD, gS, gH = ctx.orb.populations_backward(ctx.plan, f64(g_pop), f64(g_nelec), f64(g_eband) if ctx.h is not None else None, D, S, H, want_s, want_h)
+        return (None, None, gD.view(D.shape) if ctx.needs_input_grad[2] else None, gS.to(ctx.s[1]).view(ctx.s[0]) if want_s else None,
+                gH.to(ctx.h[1]).view(ctx.h[0]) if want_h else None)
+
+
+def populations(D: torch.Tensor, plan, S_packed: Optional[torch.Tensor] = None, H_packed: Optional[torch.Tensor] = None, orbitals: Optional[BatchedOrbitals] = None):
+    """Differentiable Mulliken analysis of a packed float64 density -> ``(atom_pop [N], nelec [B], eband [B] or None without H_packed)`` as
+    ``BatchedOrbitals.populations``, with gradients for ``D`` and, where they require one, ``S_packed`` and ``H_packed``.  The gradients are those with respect
+    to SYMMETRIC matrices, spread over both triangles (the convention of this module): ``dL/dD_ij = ((g_A(i) + g_A(j)) / 2 + g_nelec) S_ij + g_eband H_ij``.
+    ``orbitals``: the solution of the same batch, whose state the kernels read the layout from (None: one is prepared, which synchronises the stream once)."""
+    _require_gpu(D)
+    orb = BatchedOrbitals(plan, D.device) if orbitals is None else orbitals
+    pop, nelec, eband = _Populations.apply(orb, plan, D, S_packed, H_packed)
+    return pop, nelec, (None if H_packed is None else eband)
+
+
+def _molecule_mean_weights(counts: np.ndarray, device) -> torch.Tensor:
+    """float64 [sum counts]: 1 / (count of the entry's molecule) / B -- the mean over a molecule's entries, then over the molecules."""
+    return torch.from_numpy(np.repeat(1.0 / (counts.astype(np.float64) * counts.shape[0]), counts)).to(device)
+
+
+class _PackedMeanLoss(nn.Module):
+    packed = True
+
+    def __init__(self, kind: str = "mae", charge=0):
+        super().__init__()
+        if kind not in ("mae", "mse"):
+            raise ValueError(f"kind must be 'mae' or 'mse', not {kind!r}")
+        self.kind, self.charge = kind, charge
+
+    def _mean(self, pred, target, counts):
+        _require_gpu(pred)
+        n = int(counts.sum())
+        if pred.numel() != n or target.numel() != n:
+            raise ValueError(f"prediction and target have {pred.numel()} / {target.numel()} entries, the pointer counts {n}")
+        d = pred.reshape(-1).to(torch.float64) - target.reshape(-1).to(torch.float64).detach()
+        return torch.sum(_molecule_mean_weights(counts, pred.device) * (d.abs() if self.kind == "mae" else d * d))
+
+
+class DensityMatrixLoss(_PackedMeanLoss):
+    """``kind`` "mae" | "mse" of packed density matrices: the mean over the ``m^2`` entries of each molecule, then the mean over the molecules.  ``charge`` is what
+    ``QHNetDensityLightning`` counts the occupied orbitals with."""
+
+    def forward(self, D_pred: torch.Tensor, D_target: torch.Tensor, orb_ptr) -> torch.Tensor:
+        m = np.diff(_orb_ptr_of(orb_ptr))
+        return self._mean(D_pred, D_target, m * m)
+
+
+class MullikenChargeLoss(_PackedMeanLoss):
+    """``kind`` "mae" | "mse" of Mulliken charges (or populations) per atom: the mean over the atoms of each molecule, then the mean over the molecules.
+    ``mol_ptr`` [B+1]: the atoms of every molecule (the batch's ``ptr``)."""
+
+    def forward(self, q_pred: torch.Tensor, q_target: torch.Tensor, mol_ptr) -> torch.Tensor:
+        return self._mean(q_pred, q_target, np.diff(_orb_ptr_of(mol_ptr)))
+
+
+class QHNetDensityLightning(QHNetOrbitalLightning):
+    """``QHNetOrbitalLightning`` with terms on the occupied subspace: ``losses`` / ``loss_coefs`` take ``"density_matrix"`` (a ``DensityMatrixLoss``) and
+    ``"mulliken_charges"`` (a ``MullikenChargeLoss``) beside ``"hamiltonian"`` and ``"orbital_energies"``.  A step solves the packed prediction ONCE
+    (``orbital_solution``; ``orbital_energies`` when no density is asked for) and the packed target once, detached, however many of the three keys are active;
+    densities, populations under ``batch.overlap`` and charges ``Z - pop`` come from those two solutions.  The occupied orbitals are counted with the ``charge``
+    of the active losses, which must agree.  With all three coefficients at 0 (or without the keys) nothing is solved and the step is ``QHNetLightning``'s."""
+
+    KEYS = ("orbital_energies", "density_matrix", "mulliken_charges")
+
+    def _active(self):
+        return [k for k in self.KEYS if k in self.hparams.losses and self.hparams.loss_coefs.get(k, 0) != 0]
+
+    def _evaluate(self, batch):
+        if not self._packed():
+            raise ValueError("QHNetDensityLightning needs packed losses (HamiltonianLoss, OrbitalEnergyLoss, DensityMatrixLoss, MullikenChargeLoss)")
+        preds, targets, loss_args = QHNetLightning._evaluate(self, batch)
+        active = self._active()
+        if not active:
+            return preds, targets, loss_args
+        charges = [getattr(self.hparams.losses[k], "charge", 0) for k in active]
+        if any(not np.array_equal(np.asarray(c), np.asarray(charges[0])) for c in charges[1:]):
+            raise ValueError("the orbital losses count the occupied orbitals with different charges")
+        plan, asm = self.net.last_plan, self.net._asm
+        overlap = getattr(batch, "overlap", None)
+        S = None if overlap is None else asm.pack_targets(plan, overlap)
+        op = _orb_ptr_of(plan)
+        n_occ = occupied_counts(batch.z, batch.ptr, charges[0], op)
+        Hp, Ht = preds["hamiltonian"], targets["hamiltonian"]
+        sol_t = BatchedOrbitals(op, Hp.device).solve(Ht, S)
+        if active == ["orbital_energies"]:
+            eps, sol_p = orbital_energies(Hp, S, op, return_solution=True)
+        else:
+            eps, D, sol_p = orbital_solution(Hp, S, op, n_occ, return_solution=True)
+            D_t = sol_t.density(n_occ)
+        for k in active:
+            if k == "orbital_energies":
+                preds[k], targets[k], preds[k + "_args"] = eps, sol_t.energies, (n_occ, op)
+            elif k == "density_matrix":
+                preds[k], targets[k], preds[k + "_args"] = D, D_t, (op,)
+            else:
+                preds[k] = mulliken_charges(batch.z, populations(D, plan, S, None, sol_p)[0])
+                targets[k] = mulliken_charges(batch.z, sol_t.populations(D_t, plan, S)[0])
+                preds[k + "_args"] = (batch.ptr,)
+        return preds, targets, loss_args
+
+    def _calculate_loss(self, y_pred, y_true, *loss_args):
+        active, total = self._active(), 0
+        for name, fn in self.hparams.losses.items():
+            if name in self.KEYS:
+                if name in active:
+                    total = total + self.hparams.loss_coefs[name] * fn(y_pred[name], y_true[name], *y_pred[name + "_args"])
+            else:
+                total = total + self.hparams.loss_coefs[name] * fn(y_pred[name], y_true[name], *loss_args)
+        return total
+
+
+__all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "orbital_solution", "density_matrix", "populations",
+           "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning"]

@@ -11,9 +11,10 @@ symmetrised; Householder tridiagonalisation; implicit-shift QL with the vectors 
 molecule's block = orbital k (``C^T S C = I``; the largest-magnitude component of every orbital, the first on ties, is positive).  ``per_molecule()`` hands
 the user orbitals as COLUMNS, the convention of ``scipy.linalg.eigh``.
 
-No gradient flows through the solver: the inputs of ``BatchedOrbitals`` are detached.  A loss on orbital energies needs the gradient of the eigenvalues: that is
-``nabladft_amd.orbital_loss`` (``orbital_energies``, ``OrbitalEnergyLoss``, ``QHNetOrbitalLightning``), built on this class.  Gradients through the eigenvectors
-stay out of scope.
+No gradient flows through the solver: the inputs of ``BatchedOrbitals`` are detached.  A loss on orbital energies needs the gradient of the eigenvalues, a loss
+on densities or populations the response of the occupied subspace: both are ``nabladft_amd.orbital_loss`` (``orbital_energies``, ``orbital_solution``,
+``density_matrix``, ``populations``, the losses and the QHNet tasks), built on this class and on the launches ``resp_*`` / ``syr2k`` / ``density_response`` /
+``populations_backward`` below (csrc/orbresp.hip).
 
 After a solve, ``density(n_occ)`` gives the closed-shell density matrix ``D = 2 sum_occ c_k c_k^T`` (and the energy-weighted one) and ``populations(D, plan, S)``
 the Mulliken populations per atom, the electron count ``Tr(D S)`` and the band energy ``Tr(D H)`` (csrc/orbdens.hip), all on the device.
@@ -277,6 +278,81 @@ class BatchedOrbitals:
                                                      _lib.ptr(S), int(S is not None and S.dtype == torch.float64), N, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
                                                      _lib.ptr(pop), _lib.ptr(nelec), _lib.ptr(eband), _lib.stream_ptr()))
         return pop, nelec, eband
+
+    # ---- the density response (csrc/orbresp.hip): thin launches; nabladft_amd.orbital_loss chains them -------------------------------------------------------
+    def occupied_layout(self, n_occ):
+        """The occupied-packed layout of the response's scratch arrays -> ``(n_occ int32 [B], occ_ptr int64 [B+1], O)``, the first two on the device:
+        molecule b owns ``n_occ_b m_b`` doubles at ``occ_ptr[b]``.  ``n_occ`` is checked on the host against the orbital counts."""
+        st = self.state
+        no = check_occupied(n_occ, st.orb_ptr_host)
+        occ = np.concatenate([[0], np.cumsum(no.astype(np.int64) * st.m)]).astype(np.int64)
+        return torch.from_numpy(no).to(st.buf.device), torch.from_numpy(occ).to(st.buf.device), int(occ[-1])
+
+    def _resp(self, name, layout, ins, outs):
+        st = self.state
+        no, occ, O = layout
+        with torch.cuda.device(st.buf.device):
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(st.buf), *st._dims, _lib.ptr(no), _lib.ptr(occ), O, *[_lib.ptr(t) for t in ins + outs], _lib.stream_ptr()))
+        return outs
+
+    def _f64(self, t: torch.Tensor, n: int, name: str) -> torch.Tensor:
+        dev = self.state.buf.device
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.numel() != n or t.device != dev:
+            raise ValueError(f"{name} must be float64 [{n}] on {dev}")
+        return t.detach().reshape(-1).contiguous()
+
+    def _scratch(self, n: int, make: bool = True):
+        return torch.empty(n, dtype=torch.float64, device=self.state.buf.device) if make else None
+
+    def resp_project(self, G: torch.Tensor, layout) -> torch.Tensor:
+        """``T = Gs C_o`` with ``Gs = (G + G^T) / 2`` (``nq_orb_resp_project``): ``G`` packed float64 [P], any matrix -> occupied-packed [m][n_occ], float64 [O]."""
+        P = self.state.P
+        return self._resp("nq_orb_resp_project", layout, [self._f64(G, P, "G")], [self._scratch(P), self._scratch(layout[2])])[1]
+
+    def resp_mo(self, T: torch.Tensor, layout, overlap: bool = True):
+        """``W = C^T T`` divided by the occupied-virtual differences (``nq_orb_resp_mo``) -> ``(A_H, A_S or None)``, occupied-packed [m][n_occ]."""
+        O = layout[2]
+        return tuple(self._resp("nq_orb_resp_mo", layout, [self._f64(T, O, "T")], [self._scratch(O), self._scratch(O, overlap)]))
+
+    def resp_back(self, A_H: torch.Tensor, A_S: Optional[torch.Tensor], layout):
+        """``Rt_X = A_X^T C^T`` (``nq_orb_resp_back``) -> ``(Rt_H, Rt_S or None)``, occupied-packed [n_occ][m]; both from the same loads of the coefficients."""
+        O = layout[2]
+        ins = [self._f64(A_H, O, "A_H"), None if A_S is None else self._f64(A_S, O, "A_S")]
+        return tuple(self._resp("nq_orb_resp_back", layout, ins, [self._scratch(O), self._scratch(O, A_S is not None)]))
+
+    def syr2k(self, Rt0: torch.Tensor, Rt1: Optional[torch.Tensor], layout):
+        """``X = 1/2 sum_{i < n_occ} (r_i c_i^T + c_i r_i^T)`` (``nq_orb_syr2k``) -> ``(X0, X1 or None)``, packed float64 [P], exactly symmetric."""
+        O, P = layout[2], self.state.P
+        ins = [self._f64(Rt0, O, "Rt0"), None if Rt1 is None else self._f64(Rt1, O, "Rt1")]
+        return tuple(self._resp("nq_orb_syr2k", layout, ins, [self._scratch(P), self._scratch(P, Rt1 is not None)]))
+
+    def density_response(self, G: torch.Tensor, n_occ_or_layout, overlap: bool = True):
+        """``dL/dH`` and (``overlap``) ``dL/dS`` of a loss with ``dL/dD = G`` on the density ``density(n_occ)`` of the last solve: the four launches above ->
+        ``(gH, gS or None)``, packed float64 [P], symmetric matrices in the convention of ``weighted_gram``.  Nothing is read back."""
+        layout = n_occ_or_layout if isinstance(n_occ_or_layout, tuple) else self.occupied_layout(n_occ_or_layout)
+        A_H, A_S = self.resp_mo(self.resp_project(G, layout), layout, overlap)
+        return self.syr2k(*self.resp_back(A_H, A_S, layout), layout)
+
+    def populations_backward(self, plan, g_pop, g_nelec, g_eband, D=None, S_packed=None, H_packed=None, want_s: bool = False, want_h: bool = False):
+        """The reverse of ``populations`` (``nq_orb_population_backward``): upstream gradients (float64, each may be None) -> ``(gD, gS or None, gH or None)``,
+        packed float64 [P], with respect to symmetric ``D``, ``S`` and ``H``."""
+        st, dev = self.state, self.state.buf.device
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        H = None if H_packed is None else _packed(H_packed, st.P, "H_packed")
+        Dp = None if D is None else self._f64(D, st.P, "D")
+        N = int(plan.N)
+        gs = [None if g is None else self._f64(g, n, name) for g, n, name in ((g_pop, N, "g_pop"), (g_nelec, st.B, "g_nelec"), (g_eband, st.B, "g_eband"))]
+        mol_ptr = plan.mol_ptr.to(device=dev, dtype=torch.int32).contiguous()
+        atom_ptr = plan.orb_ptr.to(device=dev, dtype=torch.int64).contiguous()
+        if int(plan.B) != st.B or int(plan.m_total) != st.M or int(plan.total) != st.P or mol_ptr.numel() != st.B + 1 or atom_ptr.numel() != N + 1:
+            raise ValueError("the plan belongs to another batch")
+        outs = [self._scratch(st.P), self._scratch(st.P, want_s), self._scratch(st.P, want_h)]
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().nq_orb_population_backward(_lib.ptr(st.buf), *st._dims, *[_lib.ptr(g) for g in gs], _lib.ptr(Dp), _lib.ptr(H),
+                                                              int(H is not None and H.dtype == torch.float64), _lib.ptr(S),
+                                                              int(S is not None and S.dtype == torch.float64), N, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
+                                                              *[_lib.ptr(o) for o in outs], _lib.stream_ptr()))
+        return tuple(outs)
 
     def check(self) -> "BatchedOrbitals":
         st = self.state
