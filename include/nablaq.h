@@ -827,6 +827,24 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  *   out_gD_ij = ((g_A(i) + g_A(j)) / 2 + g_nelec) S_ij + g_eband H_ij (S = NULL: the identity), and on request (NULL: skipped)
  *   out_gS_ij = ((g_A(i) + g_nelec) D_ij + (g_A(j) + g_nelec) D_ji) / 2 (needs S and D) and out_gH_ij = g_eband (D_ij + D_ji) / 2 (needs H and D):
  *   the gradients with respect to symmetric D, S and H, spread over both triangles; like the forward kernel only the lower triangles of S and H are read.
+ * Fermi-Dirac smearing (csrc/orbsmear.hip, csrc/orbsmear_math.h; entry points added, ABI 17 unchanged): occupations F_k = 2 / (1 + exp((eps_k - mu) / kT)) with
+ * mu fixed by sum_k F_k = n_elec, the density D = sum_k F_k c_k c_k^T (nq_orb_wgram with w0 = F) and its response to H and S over ALL orbital pairs, evaluated
+ * without dividing by a difference of orbital energies: finite where levels coincide or cross.  n_elec, kT, mu, entropy float64 [B]; occ, docc, wdiag,
+ * g_eps, g_occ float64 [M]; T, A_H, A_S, Rt_H, Rt_S float64 [P], packed like coeff ([m_b][m_b] row-major at pack_ptr[b]); all on the device.
+ *   nq_orb_fermi: mu by a bracketed Newton iteration (bisection where Newton leaves the bracket; ends when the bracket is one ulp wide or sum F == n_elec),
+ *     out_occ = F, out_docc = dF_k / d eps_k at fixed mu (<= 0), out_entropy = -2 sum (f ln f + (1 - f) ln(1 - f)), f = F / 2, 0 ln 0 = 0.  out_info int32 [B]:
+ *     0 ok; 1: n_elec outside (0, 2 m), kT not a positive finite number (or >= 1e300), a non-finite eps or status != 0 -- that molecule's outputs are NaN.
+ *   T = Gs C is nq_orb_resp_project with n_occ = m_b, occ_ptr = pack_ptr, O = P.
+ *   nq_orb_smear_mo: W = C^T T [m][m]; off the diagonal A_H = K o W and A_S (NULL: skipped) = KS o W from the same accumulator, K_ij = (F_i - F_j) / (eps_i -
+ *     eps_j) written as -(1 / (2 kT)) sinhc((x_i - x_j) / 2) / (cosh(x_i / 2) cosh(x_j / 2)), KS_ij = -((F_i + F_j) / 2 + (eps_i + eps_j) / 2 K_ij); wdiag = W_kk.
+ *     The diagonals of A_H / A_S are not written.
+ *   nq_orb_smear_diag: from wdiag, occ, docc and the upstream gradients g_eps [M], g_occ [M], g_mu [B], g_ent [B] (each NULL: zero):
+ *     gF_k = g_occ_k + g_ent x_k + W_kk, e_k = g_eps_k + F'_k (gF_k - sum_j p_j gF_j) + p_k g_mu with p_k = F'_k / sum_j F'_j (evaluated as a softmax of
+ *     -|x|: a sum of derivatives that underflows inside a wide gap divides nothing); A_H[k][k] = e_k, A_S[k][k] (NULL: skipped) = -eps_k e_k - F_k W_kk.
+ *   nq_orb_smear_back: Rt_H[i][mu] = sum_k A_H[k][i] C[mu][k] over all k, and Rt_S from A_S (NULL: skipped) out of the same loads of the coefficients.
+ *   dL/dH = C A_H C^T and dL/dS = C A_S C^T are nq_orb_syr2k on Rt_H / Rt_S with n_occ = m_b, occ_ptr = pack_ptr, O = P: exactly symmetric.
+ * The products run on v_mfma_f64_16x16x4_f64 like the closed-shell chain's; no atomics, fixed summation orders, bitwise reproducible and independent of the
+ * rest of the batch; status != 0: NaN in the molecule's own blocks.  A second input without a second output is refused.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
 size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P);
 int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host);
@@ -852,6 +870,15 @@ int nq_orb_population_backward(void* state, int32_t B, int32_t M, int64_t P, con
                                const double* g_eband_or_null, const double* D_or_null, const void* H_or_null, int32_t h_f64, const void* S_or_null, int32_t s_f64,
                                int32_t N, const int32_t* mol_ptr, const int64_t* atom_orb_ptr, double* out_gD, double* out_gS_or_null, double* out_gH_or_null,
                                void* stream);
+int nq_orb_fermi(void* state, int32_t B, int32_t M, int64_t P, const double* n_elec, const double* kT, double* out_mu, double* out_occ, double* out_docc,
+                 double* out_entropy, int32_t* out_info, void* stream);
+int nq_orb_smear_mo(void* state, int32_t B, int32_t M, int64_t P, const double* mu, const double* kT, const double* T, double* A_H, double* A_S_or_null,
+                    double* wdiag, void* stream);
+int nq_orb_smear_diag(void* state, int32_t B, int32_t M, int64_t P, const double* mu, const double* kT, const double* occ, const double* docc,
+                      const double* wdiag, const double* g_eps_or_null, const double* g_occ_or_null, const double* g_mu_or_null, const double* g_ent_or_null,
+                      double* A_H, double* A_S_or_null, void* stream);
+int nq_orb_smear_back(void* state, int32_t B, int32_t M, int64_t P, const double* A_H, const double* A_S_or_null, double* Rt_H, double* Rt_S_or_null,
+                      void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

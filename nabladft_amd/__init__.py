@@ -44,10 +44,11 @@ from .md import BatchedMD, PYGAseInterface  # noqa: F401
 from . import vibrations  # noqa: F401
 from .vibrations import BatchedVibrations  # noqa: F401
 from . import orbitals  # noqa: F401
-from .orbitals import BatchedOrbitals, OrbitalErrors, OrbitalState, mulliken_charges, occupied_counts  # noqa: F401
-from .orbital_loss import (DensityMatrixLoss, MullikenChargeLoss, OrbitalEnergyLoss, QHNetDensityLightning, QHNetOrbitalLightning, density_matrix,  # noqa: F401
-                           orbital_energies, orbital_solution, populations)
+from .orbitals import BatchedOrbitals, FermiResult, OrbitalErrors, OrbitalState, electron_counts, mulliken_charges, occupied_counts  # noqa: F401
+from .orbital_loss import (DensityMatrixLoss, MullikenChargeLoss, OrbitalEnergyLoss, QHNetDensityLightning, QHNetOrbitalLightning,  # noqa: F401
+                           QHNetSmearedDensityLightning, SmearedSolution, density_matrix, orbital_energies, orbital_solution, populations,
+                           smeared_density_matrix, smeared_solution)
 from .data import ArenaLoader, ConformerArena, HamiltonianBatch, HamiltonianDatabase, HamiltonianDataset, hamiltonian_batch, read_energy_database  # noqa: F401
 
 __all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "DimeNetPlusPlusForceLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
-           "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "BatchedVibrations", "PYGAseInterface", "BatchedOrbitals", "OrbitalState", "OrbitalErrors", "orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "occupied_counts", "orbital_solution", "density_matrix", "populations", "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning"]
+           "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "BatchedVibrations", "PYGAseInterface", "BatchedOrbitals", "OrbitalState", "OrbitalErrors", "orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "occupied_counts", "orbital_solution", "density_matrix", "populations", "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "FermiResult", "SmearedSolution", "smeared_solution", "smeared_density_matrix", "QHNetSmearedDensityLightning"]

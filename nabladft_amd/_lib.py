@@ -237,6 +237,10 @@ SYMBOLS = {
     "nq_orb_resp_back": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "nq_orb_syr2k": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _I64, _P, _P, _P, _P, _P]),
     "nq_orb_population_backward": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "nq_orb_fermi": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nq_orb_smear_mo": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "nq_orb_smear_diag": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nq_orb_smear_back": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P]),
     "nq_g3d_max_mol_atoms": (C.c_int32, []),
     "nq_g3d_pair_forward": (C.c_int, [_P] * 9 + [_I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "nq_g3d_pair_scratch_floats": (_SZ, [_I32, _I64, _I32]),

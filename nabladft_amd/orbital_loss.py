@@ -34,8 +34,20 @@ Only occupied-virtual differences are divided by: equal levels inside the occupi
 ``BatchedOrbitals.frontier`` gives the gap to watch.  Tested against ``torch.linalg`` autograd of Cholesky -> reduce -> ``eigh`` -> ``D`` and against the
 closed form on a permuted copy (tests/orbital_density_ref.py).
 
-Limits (each raises, nothing degrades silently): what ``BatchedOrbitals`` has -- 1..1024 orbitals per molecule, closed shells, MI355X only, no CPU path.
+**Smearing.**  ``smeared_solution`` / ``smeared_density_matrix`` replace the closed shell by Fermi-Dirac occupations ``F_k = 2 / (1 + exp((eps_k - mu) / kT))``
+with ``mu`` fixed by the electron count (any count in (0, 2m): odd ones too).  ``D = sum_k F_k c_k c_k^T`` is then a smooth function of ``H`` and ``S`` also
+where levels coincide or cross, and its response is ``C (K o W) C^T`` over ALL orbital pairs with the divided differences
+``K_ij = (F_i - F_j) / (eps_i - eps_j)``, ``K_kk = F'_k``, which csrc/orbsmear.hip evaluates as
+``-(1 / (2 kT)) sinhc((x_i - x_j) / 2) / (cosh(x_i / 2) cosh(x_j / 2))``: without dividing by a difference of orbital energies anywhere in the chain.  What IS
+divided by: ``kT`` (which must be positive), ``(x_i - x_j) / 2`` inside sinhc (its limit 1 is taken at equal levels), the ``1 + e^-|x|`` factors of the Fermi
+function, and the sum of the weights ``F'_k / sum F'`` that carry the gradient of ``mu`` (a softmax, never zero).  A vanishing or crossed HOMO-LUMO gap gives
+finite gradients; with a gap much larger than ``kT`` the chain becomes that of ``orbital_solution``, which is unchanged, as is its behaviour at a vanishing
+gap.  Tested against ``torch.linalg`` autograd, the closed form on a permuted copy and finite differences (tests/orbital_smearing_ref.py).
+
+Limits (each raises, nothing degrades silently): what ``BatchedOrbitals`` has -- 1..1024 orbitals per molecule, closed shells or Fermi occupations (no spin
+polarisation), MI355X only, no CPU path.
 """
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -43,7 +55,7 @@ import torch
 from torch import nn
 
 from .lightning import QHNetLightning
-from .orbitals import BatchedOrbitals, _orb_ptr_of, _require_gpu, check_occupied, mulliken_charges, occupied_counts  # noqa: F401
+from .orbitals import BatchedOrbitals, _orb_ptr_of, _require_gpu, check_occupied, electron_counts, mulliken_charges, occupied_counts  # noqa: F401
 
 
 class _OrbitalEnergies(torch.autograd.Function):
@@ -375,5 +387,114 @@ class QHNetDensityLightning(QHNetOrbitalLightning):
         return total
 
 
+SmearedSolution = namedtuple("SmearedSolution", "eps D occ mu entropy")
+SmearedSolution.__doc__ = """What ``smeared_solution`` returns, float64 on the device: ``eps`` [M], ``D`` [P], ``occ`` = F [M], ``mu`` [B], ``entropy`` [B] (units of k_B)."""
+
+
+class _SmearedSolution(torch.autograd.Function):
+    """Forward: ONE ``BatchedOrbitals.solve``, ``fermi`` and the density of its occupations.  Backward: the chain of ``BatchedOrbitals.smeared_response`` for
+    whatever upstream gradients there are -- ``nq_orb_wgram`` alone where only ``eps`` has one; the two launches that serve ``D`` are skipped without one for
+    ``D``; nothing is launched without any, and the ``S`` half is skipped when ``S`` asks for nothing."""
+
+    @staticmethod
+    def forward(ctx, orb, H, S, n_elec, kT):
+        orb.solve(H, S)
+        ctx.set_materialize_grads(False)
+        fr = orb.fermi(n_elec, kT)
+        ctx.orb, ctx.fermi = orb, fr
+        ctx.h = (H.shape, H.dtype)
+        ctx.s = None if S is None else (S.shape, S.dtype)
+        return orb.energies.clone(), orb.smeared_density(fr.occ), fr.occ.clone(), fr.mu.clone(), fr.entropy.clone()
+
+    @staticmethod
+    def backward(ctx, g_eps, g_D, g_occ, g_mu, g_ent):
+        orb = ctx.orb
+        want_h = ctx.needs_input_grad[1]
+        want_s = ctx.s is not None and ctx.needs_input_grad[2]
+        gs = [g_eps, g_D, g_occ, g_mu, g_ent]
+        if all(g is None for g in gs) or not (want_h or want_s):
+            return None, None, None, None, None
+        g_eps, g_D, g_occ, g_mu, g_ent = [None if g is None else g.to(torch.float64).reshape(-1).contiguous() for g in gs]
+        if g_D is None and g_occ is None and g_mu is None and g_ent is None:           # the energies alone: the eigenvalue term, one launch
+            gH, gS = orb.weighted_gram(g_eps, -(orb.energies * g_eps)) if want_s else (orb.weighted_gram(g_eps), None)
+        else:
+            gH, gS = orb.smeared_response(g_D, ctx.fermi, g_eps, g_occ, g_mu, g_ent, overlap=want_s)
+        return (None, gH.to(ctx.h[1]).view(ctx.h[0]) if want_h else None, gS.to(ctx.s[1]).view(ctx.s[0]) if want_s else None, None, None)
+
+
+def smeared_solution(H_packed: torch.Tensor, S_packed: Optional[torch.Tensor], plan_or_orb_ptr, n_elec, kT, return_solution: bool = False):
+    """Orbital energies, the Fermi-smeared density matrix, the occupations, the chemical potential and the electronic entropy of every molecule from ONE
+    solve -> ``SmearedSolution(eps [M], D [P], occ [M], mu [B], entropy [B])``, float64 on the device (``return_solution=True``:
+    ``(SmearedSolution, BatchedOrbitals)``); every member is differentiable with respect to ``H_packed`` and ``S_packed``.
+
+    Arguments as for ``orbital_energies``; ``n_elec``: electrons per molecule (``electron_counts``; any number in (0, 2m), odd counts too), ``kT`` > 0: the
+    smearing temperature in the energy unit of ``H``; each one number or one per molecule.  ``occ_k = 2 / (1 + exp((eps_k - mu) / kT))`` with ``mu`` fixed by
+    ``sum occ = n_elec``, ``D = sum_k occ_k c_k c_k^T`` (packed like the input, exactly symmetric), ``entropy = -2 sum (f ln f + (1 - f) ln(1 - f))`` with
+    ``f = occ / 2``; the band energy is ``populations(D, plan, S, H)[2]``.  The backward is ``C (K o W) C^T`` over all orbital pairs with the divided
+    differences of the occupations, evaluated without dividing by a difference of orbital energies (module text): coincident and crossed levels, a vanishing
+    HOMO-LUMO gap included, give finite gradients.  A member without an upstream gradient costs nothing, the ``S`` half is skipped when ``S`` is None or requires
+    no gradient, and the gradients are cast to the inputs' dtypes in the symmetric-matrix convention of ``orbital_energies``.  Per-level losses on ``eps_k`` or
+    ``occ_k`` are not differentiable where levels cross (the labels swap); losses on ``D``, ``mu``, ``entropy`` and symmetric functions of the levels are.  A
+    molecule the solver fails on, or with ``n_elec`` outside (0, 2m) or ``kT`` not positive, yields NaN in its own blocks only
+    (``BatchedOrbitals.check()`` reports both)."""
+    _require_gpu(H_packed)
+    if S_packed is not None:
+        _require_gpu(S_packed)
+    orb = BatchedOrbitals(plan_or_orb_ptr, H_packed.device)
+    ne, kt = orb._per_molecule(n_elec, "n_elec"), orb._per_molecule(kT, "kT")
+    out = SmearedSolution(*_SmearedSolution.apply(orb, H_packed, S_packed, ne, kt))
+    return (out, orb) if return_solution else out
+
+
+def smeared_density_matrix(H_packed: torch.Tensor, S_packed: Optional[torch.Tensor], plan_or_orb_ptr, n_elec, kT, return_solution: bool = False):
+    """``smeared_solution`` without the rest -> ``D`` float64 [P] (``return_solution=True``: ``(D, BatchedOrbitals)``).  Like it, the backward is evaluated
+    without dividing by a difference of orbital energies."""
+    out = smeared_solution(H_packed, S_packed, plan_or_orb_ptr, n_elec, kT, return_solution)
+    return (out[0].D, out[1]) if return_solution else out.D
+
+
+class QHNetSmearedDensityLightning(QHNetDensityLightning):
+    """``QHNetDensityLightning`` with Fermi-smeared occupations at the temperature ``kT`` (attribute; class default 0.01 Hartree, settable on the instance):
+    the same keys, losses and constructor.  Prediction AND detached target are evaluated at the same ``kT`` (``smeared_solution`` / ``BatchedOrbitals.fermi``),
+    so a perfect prediction has zero loss; electrons are counted with ``electron_counts`` and the ``charge`` of the active losses, odd counts included.  The
+    gradients stay finite where the predicted HOMO and LUMO come close or cross, which is what lets training start from scratch; prefer the parent for
+    fine-tuning a prediction whose gap is safely open.  ``OrbitalEnergyLoss`` selects "occupied" / "frontier" with ``ceil(n_elec / 2)`` levels.  With all three
+    coefficients at 0 (or without the keys) nothing is solved and the step is ``QHNetLightning``'s."""
+
+    kT = 0.01
+
+    def _evaluate(self, batch):
+        if not self._packed():
+            raise ValueError("QHNetSmearedDensityLightning needs packed losses (HamiltonianLoss, OrbitalEnergyLoss, DensityMatrixLoss, MullikenChargeLoss)")
+        preds, targets, loss_args = QHNetLightning._evaluate(self, batch)
+        active = self._active()
+        if not active:
+            return preds, targets, loss_args
+        charges = [getattr(self.hparams.losses[k], "charge", 0) for k in active]
+        if any(not np.array_equal(np.asarray(c), np.asarray(charges[0])) for c in charges[1:]):
+            raise ValueError("the orbital losses count the electrons with different charges")
+        plan, asm = self.net.last_plan, self.net._asm
+        overlap = getattr(batch, "overlap", None)
+        S = None if overlap is None else asm.pack_targets(plan, overlap)
+        op = _orb_ptr_of(plan)
+        n_elec = electron_counts(batch.z, batch.ptr, charges[0], op)
+        n_occ = torch.minimum(torch.ceil(n_elec / 2.0), torch.from_numpy(np.diff(op).astype(np.float64))).to(torch.int32)
+        Hp, Ht = preds["hamiltonian"], targets["hamiltonian"]
+        sol_t = BatchedOrbitals(op, Hp.device).solve(Ht, S)
+        D_t = sol_t.smeared_density(sol_t.fermi(n_elec, self.kT).occ)
+        sm, sol_p = smeared_solution(Hp, S, op, n_elec, self.kT, return_solution=True)
+        for k in active:
+            if k == "orbital_energies":
+                preds[k], targets[k], preds[k + "_args"] = sm.eps, sol_t.energies, (n_occ, op)
+            elif k == "density_matrix":
+                preds[k], targets[k], preds[k + "_args"] = sm.D, D_t, (op,)
+            else:
+                preds[k] = mulliken_charges(batch.z, populations(sm.D, plan, S, None, sol_p)[0])
+                targets[k] = mulliken_charges(batch.z, sol_t.populations(D_t, plan, S)[0])
+                preds[k + "_args"] = (batch.ptr,)
+        return preds, targets, loss_args
+
+
 __all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "orbital_solution", "density_matrix", "populations",
-           "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning"]
+           "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "SmearedSolution", "smeared_solution", "smeared_density_matrix",
+           "QHNetSmearedDensityLightning"]

@@ -19,10 +19,16 @@ on densities or populations the response of the occupied subspace: both are ``na
 After a solve, ``density(n_occ)`` gives the closed-shell density matrix ``D = 2 sum_occ c_k c_k^T`` (and the energy-weighted one) and ``populations(D, plan, S)``
 the Mulliken populations per atom, the electron count ``Tr(D S)`` and the band energy ``Tr(D H)`` (csrc/orbdens.hip), all on the device.
 
-Limits (each raises, nothing degrades silently): 1..``MAX_ORBITALS`` = 1024 orbitals per molecule; closed shells only (``occupied_counts`` refuses an odd
-electron count); MI355X only, no CPU path.
+**Smearing.**  ``fermi(n_elec, kT)`` gives Fermi-Dirac occupations ``F_k = 2 / (1 + exp((eps_k - mu) / kT))`` with the chemical potential fixed by the electron
+count (``electron_counts``: odd counts and fractions are fine), ``smeared_density(occ)`` the density ``sum_k F_k c_k c_k^T`` and ``smeared_response`` its
+gradient chain over all orbital pairs, evaluated without dividing by a difference of orbital energies (csrc/orbsmear.hip;
+``nabladft_amd.orbital_loss.smeared_solution`` is the differentiable call).
+
+Limits (each raises, nothing degrades silently): 1..``MAX_ORBITALS`` = 1024 orbitals per molecule; closed shells only in ``occupied_counts`` / ``density``
+(``occupied_counts`` refuses an odd electron count; the smeared calls take any count in (0, 2m)); MI355X only, no CPU path.
 """
 import ctypes as C
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
@@ -68,6 +74,34 @@ def occupied_counts(z, ptr, charge=0, orb_ptr=None) -> torch.Tensor:
     if orb_ptr is not None:
         check_occupied(no, _orb_ptr_of(orb_ptr))
     return torch.from_numpy(no)
+
+
+def electron_counts(z, ptr, charge=0, orb_ptr=None) -> torch.Tensor:
+    """Electrons per molecule, float64 [B] on the host: ``sum Z - charge`` (``charge``: one number or one per molecule; fractions allowed).  Odd counts are
+    fine: this is what ``BatchedOrbitals.fermi`` / ``smeared_solution`` count with.  Raises ``ValueError`` (on the host, before any device work) for a count
+    <= 0 and, given the batch's ``orb_ptr`` (or a plan), for a count >= 2 m: Fermi occupations need ``0 < n_elec < 2 m``."""
+    zz, pp = _host_ptr(z), _host_ptr(ptr)
+    B = pp.shape[0] - 1
+    if B < 1 or np.any(np.diff(pp) < 1):
+        raise ValueError("electron_counts: a molecule without atoms")
+    ne = np.add.reduceat(zz, pp[:-1])[:B].astype(np.float64) - np.broadcast_to(np.asarray(charge, dtype=np.float64), (B,))
+    if np.any(~(ne > 0)):
+        b = int(np.nonzero(~(ne > 0))[0][0])
+        raise ValueError(f"electron_counts: molecule {b} has {ne[b]:g} electrons: n_elec must be in (0, 2m)")
+    if orb_ptr is not None:
+        m = np.diff(_orb_ptr_of(orb_ptr))
+        if m.shape != ne.shape:
+            raise ValueError(f"orb_ptr counts {m.shape[0]} molecules, ptr {B}")
+        bad = np.nonzero(ne >= 2.0 * m)[0]
+        if bad.size:
+            b = int(bad[0])
+            raise ValueError(f"electron_counts: molecule {b} has {ne[b]:g} electrons for m={int(m[b])} orbitals: n_elec must be in (0, 2m)")
+    return torch.from_numpy(np.ascontiguousarray(ne))
+
+
+FermiResult = namedtuple("FermiResult", "mu occ docc entropy info n_elec kT")
+FermiResult.__doc__ = """What ``BatchedOrbitals.fermi`` returns, all on the device: ``mu`` [B], ``occ`` = F [M], ``docc`` = dF/d eps at fixed mu [M] (<= 0), ``entropy`` [B]
+(units of k_B), ``info`` int32 [B] (0 ok, 1: NaN outputs), and the ``n_elec`` / ``kT`` float64 [B] the call was made with."""
 
 
 def check_occupied(n_occ, orb_ptr) -> np.ndarray:
@@ -164,7 +198,9 @@ class BatchedOrbitals:
     orbitals as columns).  ``frontier(n_occ)`` -> (homo, lumo, gap), float64 [B] on the device.  ``check()`` reads the status once (a host synchronisation)
     and raises ``RuntimeError`` naming the molecule and the pivot where S was not positive definite.  Inputs are detached: no gradient flows through
     (``nabladft_amd.orbital_loss.orbital_energies`` is the differentiable call).  ``density(n_occ)`` / ``populations(D, plan, S, H)`` / ``weighted_gram(w)``:
-    density matrices, Mulliken populations and weighted Gram products of the solved coefficients, on the device."""
+    density matrices, Mulliken populations and weighted Gram products of the solved coefficients, on the device.  ``fermi(n_elec, kT)`` /
+    ``smeared_density(occ)`` / ``smeared_response(G, fermi_result, ...)``: Fermi-Dirac occupations, their density and its gradient chain; ``check()`` also
+    reports the ``info`` of the last ``fermi``."""
 
     def __init__(self, orb_ptr, device="cuda"):
         self.state = OrbitalState(orb_ptr, device)
@@ -333,6 +369,98 @@ class BatchedOrbitals:
         A_H, A_S = self.resp_mo(self.resp_project(G, layout), layout, overlap)
         return self.syr2k(*self.resp_back(A_H, A_S, layout), layout)
 
+    # ---- Fermi-Dirac smearing (csrc/orbsmear.hip) ------------------------------------------------------------------------------------------------------------
+    def _per_molecule(self, v, name: str) -> torch.Tensor:
+        st, dev = self.state, self.state.buf.device
+        if isinstance(v, torch.Tensor):
+            t = v.detach().to(device=dev, dtype=torch.float64).reshape(-1)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))).to(dev)
+        if t.numel() == 1:
+            t = t.expand(st.B)
+        if t.numel() != st.B:
+            raise ValueError(f"{name} must be one number or one per molecule ({st.B}), not {t.numel()}")
+        return t.contiguous()
+
+    def fermi(self, n_elec, kT) -> FermiResult:
+        """Fermi-Dirac occupations of the last solve (``nq_orb_fermi``): ``n_elec`` electrons per molecule (``electron_counts``; any number in (0, 2m)) and
+        the temperature ``kT`` > 0 in the energy unit of H, each one number or one per molecule -> ``FermiResult``.  Nothing is read back: a molecule with
+        ``n_elec`` outside (0, 2m), ``kT`` not a positive finite number (or >= 1e300) or a failed solve gets ``info = 1`` and NaN, which ``check()`` reports."""
+        st, dev = self.state, self.state.buf.device
+        ne, kt = self._per_molecule(n_elec, "n_elec"), self._per_molecule(kT, "kT")
+        mu, ent = self._scratch(st.B), self._scratch(st.B)
+        occ, docc = self._scratch(st.M), self._scratch(st.M)
+        info = torch.empty(st.B, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().nq_orb_fermi(_lib.ptr(st.buf), *st._dims, _lib.ptr(ne), _lib.ptr(kt), _lib.ptr(mu), _lib.ptr(occ), _lib.ptr(docc), _lib.ptr(ent),
+                                                _lib.ptr(info), _lib.stream_ptr()))
+        self._fermi_info = info
+        return FermiResult(mu, occ, docc, ent, info, ne, kt)
+
+    def smeared_density(self, occ: torch.Tensor, energy_weighted: bool = False):
+        """``D = sum_k F_k c_k c_k^T`` over ALL orbitals for the occupations ``occ`` [M] of ``fermi`` (one ``nq_orb_wgram`` launch), packed float64 [P], exactly
+        symmetric; with ``energy_weighted`` also ``sum_k F_k eps_k c_k c_k^T`` -> ``(D, W)``."""
+        F = self._f64(occ, self.state.M, "occ")
+        return self.weighted_gram(F, F * self.state.eps if energy_weighted else None)
+
+    def full_layout(self):
+        """The layout that makes the closed-shell launches run over all orbitals: ``(n_occ = m, occ_ptr = pack_ptr, O = P)``."""
+        st = self.state
+        if getattr(self, "_full", None) is None:
+            self._full = (torch.from_numpy(st.m.astype(np.int32)).to(st.buf.device), st.pack_ptr, st.P)
+        return self._full
+
+    def _smear(self, name, args):
+        st = self.state
+        with torch.cuda.device(st.buf.device):
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(st.buf), *st._dims, *[_lib.ptr(t) for t in args], _lib.stream_ptr()))
+
+    def smear_mo(self, T: torch.Tensor, fermi_result: FermiResult, overlap: bool = True):
+        """``W = C^T T`` times the divided differences of F (``nq_orb_smear_mo``) -> ``(A_H, A_S or None, wdiag)``: packed [m][m] without their diagonals, which
+        ``smear_diag`` writes, and ``wdiag`` [M] = ``W_kk``."""
+        st = self.state
+        out = [self._scratch(st.P), self._scratch(st.P, overlap), self._scratch(st.M)]
+        self._smear("nq_orb_smear_mo", [fermi_result.mu, fermi_result.kT, self._f64(T, st.P, "T")] + out)
+        return tuple(out)
+
+    def smear_diag(self, A_H: torch.Tensor, A_S: Optional[torch.Tensor], wdiag: torch.Tensor, fermi_result: FermiResult, g_eps=None, g_occ=None, g_mu=None, g_ent=None):
+        """The diagonals of ``A_H`` / ``A_S`` in place (``nq_orb_smear_diag``) from ``wdiag`` and the upstream gradients of ``eps`` [M], ``occ`` [M], ``mu`` [B] and
+        ``entropy`` [B] (each may be None) -> ``(A_H, A_S)``."""
+        st, fr = self.state, fermi_result
+        gs = [None if g is None else self._f64(g, n, name) for g, n, name in ((g_eps, st.M, "g_eps"), (g_occ, st.M, "g_occ"), (g_mu, st.B, "g_mu"), (g_ent, st.B, "g_ent"))]
+        self._smear("nq_orb_smear_diag", [fr.mu, fr.kT, fr.occ, fr.docc, self._f64(wdiag, st.M, "wdiag")] + gs +
+                    [self._f64(A_H, st.P, "A_H"), None if A_S is None else self._f64(A_S, st.P, "A_S")])
+        return A_H, A_S
+
+    def smear_back(self, A_H: torch.Tensor, A_S: Optional[torch.Tensor]):
+        """``Rt_X = A_X^T C^T`` over all orbitals (``nq_orb_smear_back``) -> ``(Rt_H, Rt_S or None)``, packed [m][m]; both from the same loads of the coefficients."""
+        P = self.state.P
+        out = [self._scratch(P), self._scratch(P, A_S is not None)]
+        self._smear("nq_orb_smear_back", [self._f64(A_H, P, "A_H"), None if A_S is None else self._f64(A_S, P, "A_S")] + out)
+        return tuple(out)
+
+    def smeared_response(self, G: Optional[torch.Tensor], fermi_result: FermiResult, g_eps=None, g_occ=None, g_mu=None, g_ent=None, overlap: bool = True):
+        """``dL/dH`` and (``overlap``) ``dL/dS`` of a loss with upstream gradients ``G = dL/dD`` [P] (any matrix), ``g_eps`` [M], ``g_occ`` [M], ``g_mu`` [B],
+        ``g_ent`` [B] (each may be None) on the results of ``fermi`` / ``smeared_density`` of the last solve -> ``(gH, gS or None)``, packed float64 [P],
+        symmetric matrices in the convention of ``weighted_gram``.  ``T = Gs C`` (``nq_orb_resp_project`` over all orbitals), ``A = K o (C^T T)``
+        (``nq_orb_smear_mo``), its diagonal (``nq_orb_smear_diag``), ``A^T C^T`` (``nq_orb_smear_back``) and ``C A C^T`` (``nq_orb_syr2k`` over all orbitals):
+        ``K`` holds the divided differences of F, evaluated without dividing by a difference of orbital energies, so coincident and crossed levels give finite
+        gradients.  Without ``G`` the matrix ``A`` is diagonal and the result ``sum_k A_kk c_k c_k^T``: ``nq_orb_smear_diag`` and ONE ``nq_orb_wgram`` launch.
+        Nothing is read back."""
+        st, layout = self.state, self.full_layout()
+        if G is None:
+            if getattr(self, "_diag_index", None) is None:       # where element (k, k) of every block sits in a packed array
+                k = np.arange(st.M) - np.repeat(st.orb_ptr_host[:-1], st.m)
+                self._diag_index = torch.from_numpy(np.repeat(st.pack_ptr_host[:-1], st.m) + k * (np.repeat(st.m, st.m) + 1)).to(st.buf.device)
+            A_H, A_S = self._scratch(st.P), self._scratch(st.P, overlap)
+            self.smear_diag(A_H, A_S, torch.zeros(st.M, dtype=torch.float64, device=st.buf.device), fermi_result, g_eps, g_occ, g_mu, g_ent)
+            if not overlap:
+                return self.weighted_gram(A_H[self._diag_index]), None
+            return self.weighted_gram(A_H[self._diag_index], A_S[self._diag_index])
+        A_H, A_S, wdiag = self.smear_mo(self.resp_project(G, layout), fermi_result, overlap)
+        self.smear_diag(A_H, A_S, wdiag, fermi_result, g_eps, g_occ, g_mu, g_ent)
+        return self.syr2k(*self.smear_back(A_H, A_S), layout)
+
     def populations_backward(self, plan, g_pop, g_nelec, g_eband, D=None, S_packed=None, H_packed=None, want_s: bool = False, want_h: bool = False):
         """The reverse of ``populations`` (``nq_orb_population_backward``): upstream gradients (float64, each may be None) -> ``(gD, gS or None, gH or None)``,
         packed float64 [P], with respect to symmetric ``D``, ``S`` and ``H``."""
@@ -362,6 +490,12 @@ class BatchedOrbitals:
         if bad.size:
             b = int(bad[0])
             raise RuntimeError(_failure_text(b, int(status[b]), int(st.info[b]), int(st.m[b])))
+        info = getattr(self, "_fermi_info", None)
+        if info is not None:
+            bad = np.nonzero(info.cpu().numpy())[0]
+            if bad.size:
+                raise RuntimeError(f"molecule {int(bad[0])}: no Fermi occupations (info 1): n_elec outside (0, 2m), kT not a positive finite number or "
+                                   "non-finite orbital energies")
         return self
 
 
@@ -426,4 +560,4 @@ def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
     return zz.to(device=atom_pop.device, dtype=torch.float64).reshape(-1) - atom_pop.to(torch.float64)
 
 
-__all__ = ["BatchedOrbitals", "OrbitalState", "OrbitalErrors", "occupied_counts", "check_occupied", "mulliken_charges", "MAX_ORBITALS", "FIGURES"]
+__all__ = ["BatchedOrbitals", "OrbitalState", "OrbitalErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "MAX_ORBITALS", "FIGURES"]
