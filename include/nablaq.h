@@ -779,7 +779,8 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  * (the standard problem; the Cholesky and both triangular stages are skipped).  Every other array is float64 unless said otherwise.
  * `state` is ONE caller-owned device buffer of nq_orb_state_bytes(B, M, P) bytes, 16-byte aligned (0 = bad dimensions, see nq_last_error).
  * nq_orb_state_layout fills offsets_host[11] with the byte offsets of: header int32[16] = {B, M, P low word, P high word, status (-2: a call came with other
- * dimensions than nq_orb_init and did nothing), largest m}; orb_ptr int32[B+1]; pack_ptr int64[B+1]; order int32[B] (largest molecule first); status int32[B]
+ * dimensions than nq_orb_init and did nothing; -3: a purification state met a call that reads coefficients, or the reverse), largest m, 2 once the state
+ * holds a purification (below)}; orb_ptr int32[B+1]; pack_ptr int64[B+1]; order int32[B] (largest molecule first); status int32[B]
  * (0 solved, 1 S is not positive definite, 2 QL reached 60 sweeps on one eigenvalue, 3 the molecule's orb_ptr entries in the state are no longer within
  * 1..1024 orbitals -- the buffer was overwritten after nq_orb_init, which refuses such a batch; nothing else of that molecule is touched); info int32[B] (status 1: the 1-based index of the pivot that was <= 0
  * or not finite); iters int32[B] (QL sweeps); eps [M] (ascending inside each molecule); coeff [P] (ROW k of a molecule's block = orbital k, C^T S C = I, the
@@ -845,6 +846,39 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  *   dL/dH = C A_H C^T and dL/dS = C A_S C^T are nq_orb_syr2k on Rt_H / Rt_S with n_occ = m_b, occ_ptr = pack_ptr, O = P: exactly symmetric.
  * The products run on v_mfma_f64_16x16x4_f64 like the closed-shell chain's; no atomics, fixed summation orders, bitwise reproducible and independent of the
  * rest of the batch; status != 0: NaN in the molecule's own blocks.  A second input without a second output is refused.
+ * Purification (csrc/orbpurify.hip; entry points added, ABI 17 unchanged): the closed-shell density D = 2 Z^T X Z and its gradients WITHOUT a solve, for the
+ * quantities that need the occupied subspace only.  Z = L^-1 of S = L L^T, Ht = sym(Z H Z^T), X the projector on the n_occ lowest levels of Ht by second-order
+ * spectral-projection purification (SP2): X_0 = (e_max I - Ht) / (e_max - e_min) from Gershgorin bounds, iteration k: Y = X X, t = tr X, t2 = tr Y,
+ * delta_k = t - t2; stop with X = X_k when delta_k = 0, or when k >= 2 and |delta_k| >= |delta_k-1| and |delta_k-1| < 1e-6 max(1, n_occ); else X = Y if
+ * |t2 - n_occ| <= |2 t - t2 - n_occ| (log entry 1), else X = 2 X - Y (log entry 2); the stopping iteration logs 3.  n_occ <= 0: X = 0; n_occ >= m or
+ * e_max = e_min: X = I; neither iterates.  Not stopped after max_iter (1..10000) iterations: status 4, X = NaN.  Needs an open gap: a level shared by the
+ * occupied and the virtual side does not converge.  No energies, no smearing, closed shells only.
+ * Where things live: the state of nq_orb_init, whose parts `coeff` / `work` / `chol` hold X / Ht / Y (status 0, 1: the orthogonaliser failed on this
+ * molecule, info = the 1-based pivot, 4: not converged; iters = the updates applied).  Caller-owned, float64 on the device: Z [P] (one orthogonaliser serves
+ * any number of states of the same batch), X1, Q, tmp, Gt [P], ctl [B][40 + max_iter] = {e_min, e_max, kind (0 iterates, 1 X = 0, 2 X = I), n_occ, tr X and
+ * tr Y of the last iteration, 0, 0, 16 slots (partial tr X, partial tr Y) of the diagonal 64 x 64 tiles, delta_k of every iteration} and log int32
+ * [B][max_iter].  The first call of nq_orb_pur_orthogonalizer / nq_orb_pur_init marks the state for good (header word 6 = 2): from then on nq_orb_wgram, the
+ * response and the smear families refuse it, and the step / run / response entry points below refuse a state without the mark: header status -3, nothing touched.
+ *   nq_orb_pur_orthogonalizer: S (lower triangle, float32 or float64) -> Z [P], lower triangular, the upper triangle written as zero; the Cholesky stage has
+ *     the arithmetic and the pivot rule of nq_orb_solve; a failed molecule: status 1, info, its block of Z NaN, the others intact.  Latency-bound; call it once
+ *     per batch and reuse Z.
+ *   nq_orb_pur_congruence: out = alpha sym(Z A Z^T) (trans = 0) or alpha sym(Z^T A Z) (trans != 0) as two triangular products on the matrix cores, contraction
+ *     ranges cut to the non-zero part of Z; "sym": the lower-triangle 64 x 64 tiles are computed and mirrored.  A [P] float32 / float64 (a_f64) is first made
+ *     symmetric: its lower triangle mirrored (a_sym = 0) or (A + A^T) / 2 (a_sym != 0).  tmp [P]: the first product (A Z^T or A Z).  Z = NULL: out = alpha A
+ *     made symmetric, tmp unused.  Uses the layout of the state only.  A, Z, tmp and out must be different arrays.
+ *   nq_orb_pur_gemm: out = alpha A B + beta C (C = NULL: skipped), full m x m blocks [P]; the general products of the S half of the gradient.
+ *   nq_orb_pur_init: Ht [P] (lower triangle, float32 / float64; NULL: what nq_orb_pur_congruence left in the `work` part) -> the bounds, X_0 and the trivial
+ *     cases; clears ctl and log.  Z (NULL: none): a molecule whose block of Z starts with NaN gets status 1.  n_occ int32 [B] on the device.
+ *   nq_orb_pur_step: exactly one iteration, number k (0-based, in order); nq_orb_pur_run: iterations 0 .. max_iter - 1 and the status-4 sweep, enqueued with
+ *     no host round trip; the workgroups of a finished, trivial or failed molecule exit at once.
+ *   Gradient for an upstream G = dL/dD: Gt = nq_orb_pur_congruence(Z, trans = 0, G, a_sym = 1, alpha = 2), then
+ *   nq_orb_pur_response_init: X = X_0 again, X1 = -Gt / (e_max - e_min) (trivial molecule: X1 = 0, failed: NaN);
+ *   nq_orb_pur_response_step / _run: along the logged branches Y = X X and Q = X1 X + X X1 from the same staged tiles, (X, X1) = (Y, Q) or
+ *     (2 X - Y, 2 X1 - Q): the X sequence is the forward's bit for bit, nothing is decided and nothing divided.  With g = the final X1:
+ *     dL/dH = sym(Z^T g Z) and dL/dS = -sym(Z^T (M + M^T + X Gt X) Z), M = g X Ht (nq_orb_pur_gemm, nq_orb_pur_congruence with a_sym = 1, alpha = -1),
+ *     symmetric matrices in the convention of nq_orb_wgram.  X1 without Q (the second output) is refused.
+ * float64 throughout on v_mfma_f64_16x16x4_f64 through the tile routine of the response kernels (K tile 16, no deeper prefetch); no atomics, fixed summation
+ * orders, bitwise reproducible and independent of the rest of the batch.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
 size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P);
 int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host);
@@ -879,6 +913,19 @@ int nq_orb_smear_diag(void* state, int32_t B, int32_t M, int64_t P, const double
                       double* A_H, double* A_S_or_null, void* stream);
 int nq_orb_smear_back(void* state, int32_t B, int32_t M, int64_t P, const double* A_H, const double* A_S_or_null, double* Rt_H, double* Rt_S_or_null,
                       void* stream);
+int nq_orb_pur_orthogonalizer(void* state, int32_t B, int32_t M, int64_t P, const void* S, int32_t s_f64, double* Z, void* stream);
+int nq_orb_pur_congruence(void* state, int32_t B, int32_t M, int64_t P, const double* Z_or_null, int32_t trans, const void* A, int32_t a_f64, int32_t a_sym,
+                          double alpha, double* tmp_or_null, double* out, void* stream);
+int nq_orb_pur_gemm(void* state, int32_t B, int32_t M, int64_t P, const double* A, const double* Bm, const double* C_or_null, double alpha, double beta,
+                    double* out, void* stream);
+int nq_orb_pur_init(void* state, int32_t B, int32_t M, int64_t P, const void* Ht_or_null, int32_t h_f64, const double* Z_or_null, const int32_t* n_occ,
+                    int32_t max_iter, double* ctl, int32_t* log, void* stream);
+int nq_orb_pur_step(void* state, int32_t B, int32_t M, int64_t P, int32_t k, int32_t max_iter, double* ctl, int32_t* log, void* stream);
+int nq_orb_pur_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, double* ctl, int32_t* log, void* stream);
+int nq_orb_pur_response_init(void* state, int32_t B, int32_t M, int64_t P, const double* Gt, int32_t max_iter, const double* ctl, double* X1, void* stream);
+int nq_orb_pur_response_step(void* state, int32_t B, int32_t M, int64_t P, int32_t k, int32_t max_iter, const int32_t* log, double* Q, double* X1,
+                             void* stream);
+int nq_orb_pur_response_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, const int32_t* log, double* Q, double* X1, void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

@@ -241,6 +241,15 @@ SYMBOLS = {
     "nq_orb_smear_mo": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P]),
     "nq_orb_smear_diag": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nq_orb_smear_back": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P]),
+    "nq_orb_pur_orthogonalizer": (C.c_int, [_P, _I32, _I32, _I64, _P, _I32, _P, _P]),
+    "nq_orb_pur_congruence": (C.c_int, [_P, _I32, _I32, _I64, _P, _I32, _P, _I32, _I32, _D, _P, _P, _P]),
+    "nq_orb_pur_gemm": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _D, _D, _P, _P]),
+    "nq_orb_pur_init": (C.c_int, [_P, _I32, _I32, _I64, _P, _I32, _P, _P, _I32, _P, _P, _P]),
+    "nq_orb_pur_step": (C.c_int, [_P, _I32, _I32, _I64, _I32, _I32, _P, _P, _P]),
+    "nq_orb_pur_run": (C.c_int, [_P, _I32, _I32, _I64, _I32, _P, _P, _P]),
+    "nq_orb_pur_response_init": (C.c_int, [_P, _I32, _I32, _I64, _P, _I32, _P, _P, _P]),
+    "nq_orb_pur_response_step": (C.c_int, [_P, _I32, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "nq_orb_pur_response_run": (C.c_int, [_P, _I32, _I32, _I64, _I32, _P, _P, _P, _P]),
     "nq_g3d_max_mol_atoms": (C.c_int32, []),
     "nq_g3d_pair_forward": (C.c_int, [_P] * 9 + [_I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "nq_g3d_pair_scratch_floats": (_SZ, [_I32, _I64, _I32]),

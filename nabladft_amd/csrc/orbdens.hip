@@ -36,7 +36,7 @@ struct WgOperands {
 template <bool TWO>
 __global__ __launch_bounds__(NQ_WG_NT) void k_orb_wgram(OrbArgs a, int nt, const double* w0, const double* w1, const int* k_lo, const int* k_hi, double* out0,
                                                         double* out1) {
-  if (!orb_dims_ok(a)) return;
+  if (!orb_kind_ok(a, false)) return;
   const int b = blockIdx.x / nt, t = blockIdx.x - b * nt;
   if (b >= a.B) return;
   const int o0 = a.orb_ptr[b], m = a.orb_ptr[b + 1] - o0;

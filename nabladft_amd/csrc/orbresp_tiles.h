@@ -97,7 +97,7 @@ struct RsMol {
 };
 
 __device__ __forceinline__ bool rs_mol(const OrbArgs& a, int nt, const int* n_occ, const long long* occ_ptr, long long O, RsMol& q) {
-  if (!orb_dims_ok(a)) return false;
+  if (!orb_kind_ok(a, false)) return false;
   q.b = blockIdx.x / nt;
   q.t = blockIdx.x - q.b * nt;
   if (q.b >= a.B) return false;

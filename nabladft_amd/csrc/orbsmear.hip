@@ -49,7 +49,7 @@ __device__ __forceinline__ bool sm_block_mol(const OrbArgs& a, int b, int& o0, i
 __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_fermi(OrbArgs a, const double* n_elec, const double* kT_in, double* out_mu, double* out_occ, double* out_docc,
                                                          double* out_ent, int* out_info) {
   __shared__ double red[NQ_ORB_NW];
-  if (!orb_dims_ok(a)) return;
+  if (!orb_kind_ok(a, false)) return;
   const int b = blockIdx.x, tid = threadIdx.x;
   int o0, m;
   long long base;
@@ -142,7 +142,7 @@ struct SmMol {
 };
 
 __device__ __forceinline__ bool sm_mol(const OrbArgs& a, int tr, SmMol& q) {
-  if (!orb_dims_ok(a)) return false;
+  if (!orb_kind_ok(a, false)) return false;
   q.b = blockIdx.x / tr;
   q.t = blockIdx.x - q.b * tr;
   if (q.b >= a.B) return false;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_smear_diag(OrbArgs a, const d
                                                               const double* wdiag, const double* g_eps, const double* g_occ, const double* g_mu,
                                                               const double* g_ent, double* A_H, double* A_S) {
   __shared__ double red[NQ_ORB_NW];
-  if (!orb_dims_ok(a)) return;
+  if (!orb_kind_ok(a, false)) return;
   const int b = blockIdx.x, tid = threadIdx.x;
   int o0, m;
   long long base;

@@ -14,7 +14,8 @@
 #define NQ_ORB_HDR 16
 #define NQ_ORB_TILE 64        // edge of a workgroup's output tile in k_orb_wgram: 4 x 4 MFMA tiles of 16 x 16
 
-enum { OH_B = 0, OH_M, OH_PLO, OH_PHI, OH_STATUS, OH_MAXM };
+enum { OH_B = 0, OH_M, OH_PLO, OH_PHI, OH_STATUS, OH_MAXM, OH_KIND };
+#define NQ_ORB_KIND_PURIFY 2  // OH_KIND once orbpurify.hip has used the state: coeff / work / chol hold X, Ht, Y, not coefficients, A and L (0: as nq_orb_init left it)
 enum { OP_HDR = 0, OP_ORB_PTR, OP_PACK_PTR, OP_ORDER, OP_STATUS, OP_INFO, OP_ITERS, OP_EPS, OP_COEFF, OP_WORK, OP_CHOL, OP_PARTS };
 typedef NqStateLayout<OP_PARTS> OrbLayout;
 
@@ -33,6 +34,15 @@ struct OrbArgs {
 __device__ __forceinline__ bool orb_dims_ok(const OrbArgs& a) {
   const bool ok = a.hdr[OH_B] == a.B && a.hdr[OH_M] == a.M && nq_split64_is(a.hdr + OH_PLO, a.P);
   if (!ok && blockIdx.x == 0 && threadIdx.x == 0) a.hdr[OH_STATUS] = -2;   // not the state nq_orb_init prepared: touch nothing else
+  return ok;
+}
+
+// The entry points that read orbital coefficients or energies (nq_orb_wgram, the response and the smear families) refuse a state that holds a purification,
+// the purification entry points every other state: header status -3, nothing else is touched.
+__device__ __forceinline__ bool orb_kind_ok(const OrbArgs& a, bool purify) {
+  if (!orb_dims_ok(a)) return false;
+  const bool ok = (a.hdr[OH_KIND] == NQ_ORB_KIND_PURIFY) == purify;
+  if (!ok && blockIdx.x == 0 && threadIdx.x == 0) a.hdr[OH_STATUS] = -3;
   return ok;
 }
 

@@ -44,6 +44,16 @@ function, and the sum of the weights ``F'_k / sum F'`` that carry the gradient o
 finite gradients; with a gap much larger than ``kT`` the chain becomes that of ``orbital_solution``, which is unchanged, as is its behaviour at a vanishing
 gap.  Tested against ``torch.linalg`` autograd, the closed form on a permuted copy and finite differences (tests/orbital_smearing_ref.py).
 
+**Without a solve.**  ``purified_density_matrix`` gives the same closed-shell ``D`` and the same gradients from symmetric matrix products alone
+(csrc/orbpurify.hip, ``BatchedPurification``): ``Z = L^-1`` of ``S = L L^T``, ``X`` the projector on the ``n_occ`` lowest levels of ``Z H Z^T`` by second-order
+spectral-projection purification (SP2), ``D = 2 Z^T X Z``.  The response of a spectral projector is a self-adjoint map on symmetric matrices, so its
+vector-Jacobian product is the density-matrix-perturbation recursion run with the upstream gradient as the perturbation, alongside the same SP2 iterates:
+``X1_0 = -Gt / (e_max - e_min)``, ``X1 <- P + P^T`` or ``2 X1 - (P + P^T)`` with ``P = X X1`` by the branch the forward logged; then ``dL/dH = Z^T g Z`` and
+``dL/dS = -Z^T (M + M^T + X Gt X) Z`` with ``M = g X Ht``.  No eigenpairs, no stored iterates, nothing divided.  It needs an open gap (a level shared by the
+occupied and the virtual side does not converge: status 4, NaN in that molecule's blocks) and has no energies and no smearing: ``orbital_solution`` /
+``smeared_solution`` stay the route for those.  ``QHNetPurifiedDensityLightning`` is ``QHNetDensityLightning`` on it.  Tested against the same yardsticks as
+``orbital_solution`` and against ``orbital_solution`` itself (tests/orbital_purify_ref.py).
+
 Limits (each raises, nothing degrades silently): what ``BatchedOrbitals`` has -- 1..1024 orbitals per molecule, closed shells or Fermi occupations (no spin
 polarisation), MI355X only, no CPU path.
 """
@@ -55,7 +65,7 @@ import torch
 from torch import nn
 
 from .lightning import QHNetLightning
-from .orbitals import BatchedOrbitals, _orb_ptr_of, _require_gpu, check_occupied, electron_counts, mulliken_charges, occupied_counts  # noqa: F401
+from .orbitals import BatchedOrbitals, BatchedPurification, Orthogonalizer, _orb_ptr_of, _require_gpu, check_occupied, electron_counts, mulliken_charges, occupied_counts  # noqa: F401
 
 
 class _OrbitalEnergies(torch.autograd.Function):
@@ -495,6 +505,96 @@ class QHNetSmearedDensityLightning(QHNetDensityLightning):
         return preds, targets, loss_args
 
 
+class _PurifiedDensity(torch.autograd.Function):
+    """Forward: ``BatchedPurification.purify`` and ``density``.  Backward: ``BatchedPurification.response``; nothing is launched without an upstream gradient,
+    and the ``S`` half is skipped when ``S`` asks for nothing."""
+
+    @staticmethod
+    def forward(ctx, pur, H, S, n_occ, orth, max_iter):
+        pur.purify(H, n_occ, max_iter, orth)
+        ctx.set_materialize_grads(False)
+        ctx.pur = pur
+        ctx.h = (H.shape, H.dtype)
+        ctx.s = None if S is None else (S.shape, S.dtype)
+        return pur.density()
+
+    @staticmethod
+    def backward(ctx, g_D):
+        want_h = ctx.needs_input_grad[1]
+        want_s = ctx.s is not None and ctx.needs_input_grad[2]
+        if g_D is None or not (want_h or want_s):
+            return None, None, None, None, None, None
+        gH, gS = ctx.pur.response(g_D.to(torch.float64).reshape(-1).contiguous(), want_s)
+        return (None, gH.to(ctx.h[1]).view(ctx.h[0]) if want_h else None, gS.to(ctx.s[1]).view(ctx.s[0]) if want_s else None, None, None, None)
+
+
+def purified_density_matrix(H_packed: torch.Tensor, S_packed: Optional[torch.Tensor], plan_or_orb_ptr, n_occ, orthogonalizer: Optional[Orthogonalizer] = None,
+                            max_iter: int = 100, return_solution: bool = False):
+    """The closed-shell density matrix of every molecule WITHOUT a solve -> ``D`` float64 [P] on the device (``return_solution=True``:
+    ``(D, BatchedPurification)``), differentiable with respect to ``H_packed`` and ``S_packed``: the ``D`` of ``density_matrix`` to rounding, from symmetric
+    float64 matrix products alone (module text, "Without a solve").
+
+    Arguments as for ``density_matrix``.  ``orthogonalizer``: what ``BatchedPurification.orthogonalize(S_packed)`` returned for this batch (it must be the
+    one of ``S_packed``: the gradient of ``S_packed`` is evaluated through it); None: one is made here, one latency-bound launch.  Prediction and target of a
+    step share ``S`` and so the orthogonalizer.  ``S_packed = None``: the standard problem, no orthogonalizer.  ``max_iter``: the iteration cap (11..49
+    iterations were needed at gaps of 1e-3..0.3 of a 20-unit spectrum).  The backward runs the recursion of the module text along the logged branches; the
+    upstream gradient need not be symmetric; nothing is launched without one, the ``S`` half is skipped when ``S`` is None or requires no gradient, and the
+    gradients are cast to the inputs' dtypes in the symmetric-matrix convention of ``orbital_energies``.  **Needs an open gap**: a molecule whose
+    purification does not converge in ``max_iter`` iterations (status 4) or whose overlap is not positive definite (status 1) yields NaN in its own blocks
+    only; ``BatchedPurification.check()`` reports both.  No energies and no smearing.  ``populations(D, plan, S, H, orbitals=solution)`` works on the result."""
+    _require_gpu(H_packed)
+    if S_packed is not None:
+        _require_gpu(S_packed)
+    elif orthogonalizer is not None:
+        raise ValueError("purified_density_matrix: an orthogonalizer without S_packed")
+    pur = BatchedPurification(plan_or_orb_ptr, H_packed.device)
+    if S_packed is not None and orthogonalizer is None:
+        orthogonalizer = pur.orthogonalize(S_packed)
+    D = _PurifiedDensity.apply(pur, H_packed, S_packed, n_occ, orthogonalizer, max_iter)
+    return (D, pur) if return_solution else D
+
+
+class QHNetPurifiedDensityLightning(QHNetDensityLightning):
+    """``QHNetDensityLightning`` without a solve: ``"density_matrix"`` and ``"mulliken_charges"`` come from ``purified_density_matrix`` of the packed prediction
+    and a detached ``BatchedPurification`` of the packed target, both through ONE orthogonalizer of ``batch.overlap`` per step.  Purification has no orbital
+    energies: an active ``"orbital_energies"`` key raises ``ValueError`` (use the parent).  ``max_iter`` (attribute; class default 100) caps the iterations.
+    Prefer it where the gaps are safely open; a molecule without a gap gets NaN, which the parent's solver does not need.  With both coefficients at 0 (or
+    without the keys) nothing is purified and the step is ``QHNetLightning``'s."""
+
+    max_iter = 100
+
+    def _evaluate(self, batch):
+        if not self._packed():
+            raise ValueError("QHNetPurifiedDensityLightning needs packed losses (HamiltonianLoss, DensityMatrixLoss, MullikenChargeLoss)")
+        active = self._active()
+        if "orbital_energies" in active:
+            raise ValueError("QHNetPurifiedDensityLightning: purification has no orbital energies; use QHNetDensityLightning for an \"orbital_energies\" term")
+        preds, targets, loss_args = QHNetLightning._evaluate(self, batch)
+        if not active:
+            return preds, targets, loss_args
+        charges = [getattr(self.hparams.losses[k], "charge", 0) for k in active]
+        if any(not np.array_equal(np.asarray(c), np.asarray(charges[0])) for c in charges[1:]):
+            raise ValueError("the orbital losses count the occupied orbitals with different charges")
+        plan, asm = self.net.last_plan, self.net._asm
+        overlap = getattr(batch, "overlap", None)
+        S = None if overlap is None else asm.pack_targets(plan, overlap)
+        op = _orb_ptr_of(plan)
+        n_occ = occupied_counts(batch.z, batch.ptr, charges[0], op)
+        Hp, Ht = preds["hamiltonian"], targets["hamiltonian"]
+        pur_t = BatchedPurification(op, Hp.device)
+        orth = None if S is None else pur_t.orthogonalize(S)
+        D_t = pur_t.purify(Ht, n_occ, self.max_iter, orth).density()
+        D, pur_p = purified_density_matrix(Hp, S, op, n_occ, orth, self.max_iter, return_solution=True)
+        for k in active:
+            if k == "density_matrix":
+                preds[k], targets[k], preds[k + "_args"] = D, D_t, (op,)
+            else:
+                preds[k] = mulliken_charges(batch.z, populations(D, plan, S, None, pur_p)[0])
+                targets[k] = mulliken_charges(batch.z, pur_t.populations(D_t, plan, S)[0])
+                preds[k + "_args"] = (batch.ptr,)
+        return preds, targets, loss_args
+
+
 __all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "orbital_solution", "density_matrix", "populations",
            "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "SmearedSolution", "smeared_solution", "smeared_density_matrix",
-           "QHNetSmearedDensityLightning"]
+           "QHNetSmearedDensityLightning", "purified_density_matrix", "QHNetPurifiedDensityLightning"]

@@ -24,6 +24,11 @@ count (``electron_counts``: odd counts and fractions are fine), ``smeared_densit
 gradient chain over all orbital pairs, evaluated without dividing by a difference of orbital energies (csrc/orbsmear.hip;
 ``nabladft_amd.orbital_loss.smeared_solution`` is the differentiable call).
 
+**Without a solve.**  ``BatchedPurification`` gives the closed-shell density ``D = 2 Z^T X Z`` and its gradients from symmetric matrix products alone
+(csrc/orbpurify.hip): ``Z = L^-1`` of ``S = L L^T`` (``orthogonalize``; one serves prediction and target), ``X`` the projector on the ``n_occ`` lowest levels of
+``Z H Z^T`` by second-order spectral-projection purification, the gradient by the density-matrix-perturbation recursion along the same iterates
+(``nabladft_amd.orbital_loss.purified_density_matrix`` is the differentiable call).  Closed shells only, needs an open gap, no energies, no smearing.
+
 Limits (each raises, nothing degrades silently): 1..``MAX_ORBITALS`` = 1024 orbitals per molecule; closed shells only in ``occupied_counts`` / ``density``
 (``occupied_counts`` refuses an odd electron count; the smeared calls take any count in (0, 2m)); MI355X only, no CPU path.
 """
@@ -123,6 +128,8 @@ def _failure_text(b: int, status: int, info: int, m: int) -> str:
         return f"molecule {b}: the overlap matrix is not positive definite (Cholesky pivot {info} of {m} is <= 0 or not finite)"
     if status == 2:
         return f"molecule {b}: the QL iteration did not converge in {MAX_QL_SWEEPS} sweeps on one eigenvalue"
+    if status == 4:
+        return f"molecule {b}: the purification did not converge in {info} iterations (no gap between the occupied and the virtual levels?)"
     return f"molecule {b}: the state buffer no longer holds the batch nq_orb_init prepared (status {status}): it was overwritten"
 
 
@@ -186,6 +193,8 @@ class OrbitalState(DeviceState):
         h = self._read_header()
         if h[4] == -2:
             raise RuntimeError("an nq_orb call came with other dimensions than nq_orb_init prepared the state for")
+        if h[4] == -3:
+            raise RuntimeError("a state that holds a purification was passed to a call that reads orbital coefficients, or the reverse")
         return dict(B=h[0], M=h[1], P=(h[2] & 0xffffffff) + (h[3] << 32), status=h[4], max_m=h[5])
 
 
@@ -499,6 +508,175 @@ class BatchedOrbitals:
         return self
 
 
+Orthogonalizer = namedtuple("Orthogonalizer", "Z status info orb_ptr")
+Orthogonalizer.__doc__ = """What ``BatchedPurification.orthogonalize`` returns, reusable for any purification of the same batch: ``Z`` float64 [P] on the device
+(``L^-1`` of ``S = L L^T`` per molecule, lower triangular), ``status`` / ``info`` int32 [B] copies (1: the overlap is not positive definite, ``info`` = the
+1-based Cholesky pivot; that molecule's block of ``Z`` is NaN) and the host ``orb_ptr`` it was built for."""
+
+
+class BatchedPurification:
+    """Closed-shell density matrices of every molecule of a batch and their gradients WITHOUT a solve (csrc/orbpurify.hip).
+
+    ``BatchedPurification(orb_ptr)`` as ``BatchedOrbitals``.  ``orthogonalize(S_packed)`` -> ``Orthogonalizer`` (one latency-bound launch; the object is
+    reusable, also by other ``BatchedPurification`` objects of the same batch, and is remembered by this one).  ``purify(H_packed, n_occ, max_iter=100,
+    orthogonalizer=None)`` enqueues the congruence ``Z H Z^T``, the bounds and ``max_iter`` SP2 iterations on the current stream and returns ``self``; nothing
+    is read back (``orthogonalizer=None``: the one this object made, or the standard problem if it made none).  ``n_occ`` [B] in ``0..m``.  ``density()`` ->
+    ``D = 2 Z^T X Z`` packed float64 [P], exactly symmetric.  ``response(G, overlap=True)`` -> ``(dL/dH, dL/dS or None)`` for ``G = dL/dD`` (any matrix), packed
+    float64 [P], symmetric matrices in the convention of ``BatchedOrbitals.weighted_gram``; it runs the same ``X`` sequence again along the logged branches
+    with no stored iterates, no eigenpairs and no division.  ``iterations`` int32 [B] on the device.  ``check()`` reads the status once (a host
+    synchronisation) and raises ``RuntimeError`` naming the molecule whose overlap was not positive definite (status 1) or whose purification did not
+    converge (status 4: needs an open gap).  A failed molecule has NaN in its own blocks only.  ``populations`` / ``populations_backward`` are
+    ``BatchedOrbitals``'.  No energies, no smearing, closed shells only."""
+
+    def __init__(self, orb_ptr, device="cuda"):
+        self.state = OrbitalState(orb_ptr, device)
+        self.orthogonalizer = None
+        self._orth = None          # the one the last purify used
+        self._max_iter = None
+
+    status = property(lambda self: self.state.status)
+    info = property(lambda self: self.state.info)
+    iterations = property(lambda self: self.state.iters)
+    orb_ptr = property(lambda self: self.state.orb_ptr_host)
+    pack_ptr = property(lambda self: self.state.pack_ptr_host)
+    projector = property(lambda self: self.state.coeff)            # X [P]
+    _f64 = BatchedOrbitals._f64
+    _scratch = BatchedOrbitals._scratch
+    populations = BatchedOrbitals.populations
+    populations_backward = BatchedOrbitals.populations_backward
+
+    def _call(self, name, *args):
+        st = self.state
+        with torch.cuda.device(st.buf.device):
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(st.buf), *st._dims, *args, _lib.stream_ptr()))
+
+    def orthogonalize(self, S_packed: torch.Tensor) -> Orthogonalizer:
+        st = self.state
+        S = _packed(S_packed, st.P, "S_packed")
+        if S.device != st.buf.device:
+            raise ValueError(f"the matrices must live on {st.buf.device}")
+        Z = self._scratch(st.P)
+        self._call("nq_orb_pur_orthogonalizer", _lib.ptr(S), int(S.dtype == torch.float64), _lib.ptr(Z))
+        self.orthogonalizer = Orthogonalizer(Z, st.status.clone(), st.info.clone(), st.orb_ptr_host)
+        return self.orthogonalizer
+
+    def congruence(self, Z: Optional[torch.Tensor], A: torch.Tensor, trans: bool, alpha: float = 1.0, symmetrize: bool = False, out: Optional[torch.Tensor] = None):
+        """``alpha sym(Z A Z^T)`` (``trans`` False) or ``alpha sym(Z^T A Z)`` (``nq_orb_pur_congruence``) -> packed float64 [P], exactly symmetric.  ``A``: float32 or
+        float64 [P]; its lower triangle is read, or ``(A + A^T) / 2`` with ``symmetrize``.  ``Z = None``: ``alpha A`` made symmetric."""
+        st = self.state
+        Ap = _packed(A, st.P, "A")
+        out = self._scratch(st.P) if out is None else out
+        tmp = None if Z is None else self._scratch(st.P)
+        self._call("nq_orb_pur_congruence", _lib.ptr(Z), int(bool(trans)), _lib.ptr(Ap), int(Ap.dtype == torch.float64), int(bool(symmetrize)), float(alpha),
+                   _lib.ptr(tmp), _lib.ptr(out))
+        return out
+
+    def gemm(self, A: torch.Tensor, Bm: torch.Tensor, C: Optional[torch.Tensor] = None, alpha: float = 1.0, beta: float = 1.0) -> torch.Tensor:
+        """``alpha A B + beta C`` per molecule (``nq_orb_pur_gemm``), packed float64 [P]."""
+        P = self.state.P
+        out = self._scratch(P)
+        self._call("nq_orb_pur_gemm", _lib.ptr(self._f64(A, P, "A")), _lib.ptr(self._f64(Bm, P, "B")), _lib.ptr(None if C is None else self._f64(C, P, "C")),
+                   float(alpha), float(beta), _lib.ptr(out))
+        return out
+
+    def _occupied(self, n_occ) -> torch.Tensor:
+        st = self.state
+        no = _host_ptr(n_occ).astype(np.int32)
+        if no.shape != st.m.shape:
+            raise ValueError(f"n_occ has {no.shape[0]} entries for {st.m.shape[0]} molecules")
+        bad = np.nonzero((no < 0) | (no > st.m))[0]
+        if bad.size:
+            b = int(bad[0])
+            raise ValueError(f"molecule {b}: n_occ={int(no[b])} outside 0..m={int(st.m[b])}")
+        return torch.from_numpy(no).to(st.buf.device)
+
+    def _orthogonalizer(self, orth):
+        orth = self.orthogonalizer if orth is None else orth
+        if orth is not None and (not np.array_equal(orth.orb_ptr, self.state.orb_ptr_host) or orth.Z.device != self.state.buf.device):
+            raise ValueError("the orthogonalizer belongs to another batch")
+        return orth
+
+    def prepare(self, H_packed: torch.Tensor, n_occ, max_iter: int = 100, orthogonalizer: Optional[Orthogonalizer] = None) -> "BatchedPurification":
+        """What ``purify`` does before the iterations (``nq_orb_pur_congruence``, ``nq_orb_pur_init``): ``Ht`` into the state, the bounds, ``X_0``, the trivial
+        cases, cleared ``ctl`` / ``log``."""
+        st, dev = self.state, self.state.buf.device
+        H = _packed(H_packed, st.P, "H_packed")
+        if H.device != dev:
+            raise ValueError(f"the matrices must live on {dev}")
+        max_iter = int(max_iter)
+        if not 1 <= max_iter <= 10000:
+            raise ValueError(f"max_iter={max_iter} outside 1..10000")
+        orth = self._orthogonalizer(orthogonalizer)
+        no = self._occupied(n_occ)
+        self._orth, self._max_iter, self._n_occ = orth, max_iter, no
+        self.ctl = torch.empty(st.B, 40 + max_iter, dtype=torch.float64, device=dev)
+        self.log = torch.empty(st.B, max_iter, dtype=torch.int32, device=dev)
+        if orth is None:
+            self._call("nq_orb_pur_init", _lib.ptr(H), int(H.dtype == torch.float64), None, _lib.ptr(no), max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
+        else:
+            self.congruence(orth.Z, H, False, out=st.work)
+            self._call("nq_orb_pur_init", None, 1, _lib.ptr(orth.Z), _lib.ptr(no), max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
+        return self
+
+    def step(self, k: int) -> "BatchedPurification":
+        """Exactly one iteration, number ``k`` (``nq_orb_pur_step``; for tests: call them in order from 0)."""
+        self._call("nq_orb_pur_step", int(k), self._max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
+        return self
+
+    def purify(self, H_packed: torch.Tensor, n_occ, max_iter: int = 100, orthogonalizer: Optional[Orthogonalizer] = None) -> "BatchedPurification":
+        self.prepare(H_packed, n_occ, max_iter, orthogonalizer)
+        self._call("nq_orb_pur_run", self._max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
+        return self
+
+    def _purified(self):
+        if self._max_iter is None:
+            raise RuntimeError("BatchedPurification: purify() first")
+
+    def density(self) -> torch.Tensor:
+        self._purified()
+        return self.congruence(None if self._orth is None else self._orth.Z, self.state.coeff, True, 2.0)
+
+    def response_start(self, G: torch.Tensor):
+        """``Gt = 2 Z (G + G^T) / 2 Z^T`` and the start of the recursion (``nq_orb_pur_response_init``) -> ``(Gt, X1, Q)``; ``response_step(k, X1, Q)`` is one
+        iteration (for tests)."""
+        self._purified()
+        P = self.state.P
+        Gt = self.congruence(None if self._orth is None else self._orth.Z, self._f64(G, P, "G"), False, 2.0, symmetrize=True)
+        X1, Q = self._scratch(P), self._scratch(P)
+        self._call("nq_orb_pur_response_init", _lib.ptr(Gt), self._max_iter, _lib.ptr(self.ctl), _lib.ptr(X1))
+        return Gt, X1, Q
+
+    def response_step(self, k: int, X1: torch.Tensor, Q: torch.Tensor):
+        self._call("nq_orb_pur_response_step", int(k), self._max_iter, _lib.ptr(self.log), _lib.ptr(Q), _lib.ptr(X1))
+
+    def response(self, G: torch.Tensor, overlap: bool = True):
+        Gt, X1, Q = self.response_start(G)
+        self._call("nq_orb_pur_response_run", self._max_iter, _lib.ptr(self.log), _lib.ptr(Q), _lib.ptr(X1))
+        st = self.state
+        Z = None if self._orth is None else self._orth.Z
+        gH = self.congruence(Z, X1, True)
+        if not overlap or Z is None:
+            return gH, None
+        M2 = self.gemm(X1, self.gemm(st.coeff, st.work), alpha=2.0)                        # 2 g X Ht
+        A = self.gemm(st.coeff, self.gemm(Gt, st.coeff), M2)                               # X Gt X + 2 M; its symmetric part is M + M^T + X Gt X
+        return gH, self.congruence(Z, A, True, -1.0, symmetrize=True)
+
+    def check(self) -> "BatchedPurification":
+        st = self.state
+        st.header()
+        status = st.status.cpu().numpy()
+        bad = np.nonzero(status)[0]
+        if bad.size:
+            b = int(bad[0])
+            info = int(st.info[b])
+            if status[b] == 1 and self._orth is not None:
+                info = int(self._orth.info[b])
+            if status[b] == 4:
+                info = int(self._max_iter)
+            raise RuntimeError(_failure_text(b, int(status[b]), info, int(st.m[b])))
+        return self
+
+
 class OrbitalErrors:
     """The orbital figures of a test loop, accumulated over batches: for QHNet ``update(net(batch, packed=True), asm.pack_targets(plan, batch.hamiltonian),
     asm.pack_targets(plan, batch.overlap), plan, batch.z, batch.ptr)``; for PhiSNet the ``*_packed`` results and targets with ``results["plan"]``.
@@ -560,4 +738,4 @@ def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
     return zz.to(device=atom_pop.device, dtype=torch.float64).reshape(-1) - atom_pop.to(torch.float64)
 
 
-__all__ = ["BatchedOrbitals", "OrbitalState", "OrbitalErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "MAX_ORBITALS", "FIGURES"]
+__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "OrbitalState", "OrbitalErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "MAX_ORBITALS", "FIGURES"]
