@@ -879,6 +879,22 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  *     symmetric matrices in the convention of nq_orb_wgram.  X1 without Q (the second output) is refused.
  * float64 throughout on v_mfma_f64_16x16x4_f64 through the tile routine of the response kernels (K tile 16, no deeper prefetch); no atomics, fixed summation
  * orders, bitwise reproducible and independent of the rest of the batch.
+ * Bond orders (csrc/orbbond.hip; entry points added, ABI 17 unchanged): the Mayer bond-order table and the atomic valences of a closed-shell density D [P]
+ * (carrying the factor 2) under S, and their reverse.  Atoms own contiguous orbital ranges: mol_ptr int32 [B+1] and atom_orb_ptr int64 [N+1] as for
+ * nq_orb_population; molecule b owns the n_b^2 ordered atom pairs (A, B), A = B included, row-major at bond_ptr[b] (int64 [B+1] on the device, Q =
+ * bond_ptr[B]: the ragged layout of the Graphormer3D pair_ptr).  Only the layout of the state is read: a solver state and a purification state serve alike.
+ *   nq_orb_bond_product: out_P [P] = D S per molecule, the general m x m product (P is not symmetric); only the lower triangles of D and of S (float32 or
+ *     float64 by s_f64) are read.  S = NULL: P = D made symmetric from its lower triangle (the Wiberg index of an orthogonal basis).
+ *   nq_orb_bond_reduce: out_bond [Q], B_AB = sum_{mu in A, nu in B} P[mu][nu] P[nu][mu], one wavefront per pair A >= B, (A, B) and (B, A) written from the same
+ *     number: exactly symmetric; out_valence [N] (NULL: skipped), V_A = sum_{B != A} B_AB.  An atom whose orbital range leaves its molecule or that has more than
+ *     32 orbitals gives NaN for its row and column.  A molecule whose entries of mol_ptr / bond_ptr do not describe n_b^2 entries inside [0, Q) is not touched.
+ *   nq_orb_bond_backward: gB [Q], gV [N] (each NULL: zero) -> E [P] (caller-owned scratch, written first by an elementwise launch):
+ *     E[mu][nu] = (Gamma_A(mu)A(nu) + Gamma_A(nu)A(mu)) P[nu][mu] = dL/dP with Gamma_AB = gB_AB + (A != B ? gV_A : 0); then out_gD = sym(E S) = 1/2 (E S + S E^T)
+ *     (S = NULL: sym(E)) and out_gS = sym(D E) = 1/2 (D E + E^T D) (each NULL: skipped; out_gS needs S and D, and D is passed only with out_gS), the gradients
+ *     with respect to symmetric D and S spread over both triangles, lower-triangle 64 x 64 tiles mirrored: exactly symmetric.  An orbital no valid atom owns
+ *     carries NaN.
+ * All float64 on v_mfma_f64_16x16x4_f64 through the tile routine of the response kernels, the grids sized from (B, M, P), no atomics, fixed summation orders:
+ * bitwise reproducible and independent of the rest of the batch.  status != 0: NaN in the molecule's own blocks of every output.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
 size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P);
 int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host);
@@ -926,6 +942,12 @@ int nq_orb_pur_response_init(void* state, int32_t B, int32_t M, int64_t P, const
 int nq_orb_pur_response_step(void* state, int32_t B, int32_t M, int64_t P, int32_t k, int32_t max_iter, const int32_t* log, double* Q, double* X1,
                              void* stream);
 int nq_orb_pur_response_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, const int32_t* log, double* Q, double* X1, void* stream);
+int nq_orb_bond_product(void* state, int32_t B, int32_t M, int64_t P, const double* D, const void* S_or_null, int32_t s_f64, double* out_P, void* stream);
+int nq_orb_bond_reduce(void* state, int32_t B, int32_t M, int64_t P, const double* Pm, int32_t N, int64_t Q, const int32_t* mol_ptr, const int64_t* atom_orb_ptr,
+                       const int64_t* bond_ptr, double* out_bond, double* out_valence_or_null, void* stream);
+int nq_orb_bond_backward(void* state, int32_t B, int32_t M, int64_t P, const double* gB_or_null, const double* gV_or_null, const double* Pm,
+                         const double* D_or_null, const void* S_or_null, int32_t s_f64, int32_t N, int64_t Q, const int32_t* mol_ptr, const int64_t* atom_orb_ptr,
+                         const int64_t* bond_ptr_or_null, double* E, double* out_gD_or_null, double* out_gS_or_null, void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

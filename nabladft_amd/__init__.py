@@ -26,6 +26,8 @@ Public surface mirrors the reference plugin classes for this path:
                                     batched generalized symmetric eigensolver on the device (orbitals.py; no reference code, tested against numpy)
   nabladft_amd.BatchedPurification / purified_density_matrix <-> the same slots, for the density alone: SP2 purification and its gradient from float64 matrix
                                     products, no solve (orbitals.py, orbital_loss.py; no reference code, tested against numpy and the solver route)
+  nabladft_amd.bond_orders / BondOrderLoss / QHNetBondOrderLightning <-> the same slots: Mayer bond orders and atomic valences of a density matrix and their
+                                    gradients (orbitals.py, orbital_loss.py; no reference code, tested against numpy and torch autograd)
   nabladft_amd.spk.*            <-> the schnetpack classes config/model/{painn,schnet}.yaml instantiate (parity unpinned)
   nabladft_amd.read_energy_database / ArenaLoader <-> PyGNablaDFT.process + DataLoader collate (dataset/pyg_datasets.py:101-109)
 """
@@ -46,11 +48,13 @@ from .md import BatchedMD, PYGAseInterface  # noqa: F401
 from . import vibrations  # noqa: F401
 from .vibrations import BatchedVibrations  # noqa: F401
 from . import orbitals  # noqa: F401
-from .orbitals import BatchedOrbitals, BatchedPurification, FermiResult, OrbitalErrors, OrbitalState, electron_counts, mulliken_charges, occupied_counts  # noqa: F401
+from .orbitals import BatchedOrbitals, BatchedPurification, FermiResult, OrbitalErrors, OrbitalState, electron_counts, mulliken_charges, occupied_counts, bond_layout, dense_bond_orders  # noqa: F401
 from .orbital_loss import (DensityMatrixLoss, MullikenChargeLoss, OrbitalEnergyLoss, QHNetDensityLightning, QHNetOrbitalLightning,  # noqa: F401
                            QHNetSmearedDensityLightning, SmearedSolution, density_matrix, orbital_energies, orbital_solution, populations,
-                           smeared_density_matrix, smeared_solution, purified_density_matrix, QHNetPurifiedDensityLightning)
+                           smeared_density_matrix, smeared_solution, purified_density_matrix, QHNetPurifiedDensityLightning, bond_orders, BondOrderLoss,
+                           QHNetBondOrderLightning)
 from .data import ArenaLoader, ConformerArena, HamiltonianBatch, HamiltonianDatabase, HamiltonianDataset, hamiltonian_batch, read_energy_database  # noqa: F401
 
 __all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "DimeNetPlusPlusForceLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
-           "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "BatchedVibrations", "PYGAseInterface", "BatchedOrbitals", "OrbitalState", "OrbitalErrors", "orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "occupied_counts", "orbital_solution", "density_matrix", "populations", "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "FermiResult", "SmearedSolution", "smeared_solution", "smeared_density_matrix", "QHNetSmearedDensityLightning", "BatchedPurification", "purified_density_matrix", "QHNetPurifiedDensityLightning"]
+           "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "BatchedVibrations", "PYGAseInterface", "BatchedOrbitals", "OrbitalState", "OrbitalErrors", "orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "occupied_counts", "orbital_solution", "density_matrix", "populations", "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "FermiResult", "SmearedSolution", "smeared_solution", "smeared_density_matrix", "QHNetSmearedDensityLightning", "BatchedPurification", "purified_density_matrix", "QHNetPurifiedDensityLightning", "bond_orders", "BondOrderLoss", "QHNetBondOrderLightning",
+           "bond_layout", "dense_bond_orders"]

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libnablaq.so")
-SOURCES = ["graph.hip", "gemm.hip", "gemm_bf16.hip", "edge.hip", "molpair.hip", "updfuse.hip", "node.hip", "schnet.hip", "hblock.hip", "so3.hip", "qhnet.hip", "qhgen.hip", "gemnet_graph.hip", "gemnet.hip", "escn.hip", "equiformer.hip", "geobasis.hip", "graphormer.hip", "dimenet.hip", "lbfgs.hip", "md.hip", "vib.hip", "orbitals.hip", "orbdens.hip", "orbresp.hip", "orbsmear.hip", "orbpurify.hip", "rccl.hip", "engine.hip"]
+SOURCES = ["graph.hip", "gemm.hip", "gemm_bf16.hip", "edge.hip", "molpair.hip", "updfuse.hip", "node.hip", "schnet.hip", "hblock.hip", "so3.hip", "qhnet.hip", "qhgen.hip", "gemnet_graph.hip", "gemnet.hip", "escn.hip", "equiformer.hip", "geobasis.hip", "graphormer.hip", "dimenet.hip", "lbfgs.hip", "md.hip", "vib.hip", "orbitals.hip", "orbdens.hip", "orbresp.hip", "orbsmear.hip", "orbpurify.hip", "orbbond.hip", "rccl.hip", "engine.hip"]
 # molpair.hip: the SLP vectoriser packs neighbouring scalar f32 operations into v_pk_* beside the matrix instructions, which costs more than it saves there
 # (MI355X_MICROARCH.md, "packed f32 VALU beside MFMAs"; measured 6.51 -> 6.18 ms per step, profiles/r06_gwr_mol_variants.txt)
 # md.hip: no contraction of a * b + c, so that the float64 integrator rounds like the operation-by-operation restatement it is tested against (tests/md_ref.py)
@@ -25,7 +25,8 @@ SOURCES = ["graph.hip", "gemm.hip", "gemm_bf16.hip", "edge.hip", "molpair.hip", 
 # orbresp.hip: the same, for the density response that follows both
 # orbsmear.hip: the same, for the smeared occupations and their response (it shares orbresp_tiles.h with orbresp.hip)
 # orbpurify.hip: the same, for the purification and its response: 2 X - Y and the mirrored tiles keep X exactly symmetric (it shares orbresp_tiles.h too)
-EXTRA = {"molpair.hip": ["-fno-slp-vectorize"], "md.hip": ["-ffp-contract=off"], "vib.hip": ["-ffp-contract=off"], "orbitals.hip": ["-ffp-contract=off"], "orbdens.hip": ["-ffp-contract=off"], "orbresp.hip": ["-ffp-contract=off"], "orbsmear.hip": ["-ffp-contract=off"], "orbpurify.hip": ["-ffp-contract=off"]}
+# orbbond.hip: the same, for the bond orders that follow a density: its pair sums are written with fma() and the matrix instruction (orbresp_tiles.h again)
+EXTRA = {"molpair.hip": ["-fno-slp-vectorize"], "md.hip": ["-ffp-contract=off"], "vib.hip": ["-ffp-contract=off"], "orbitals.hip": ["-ffp-contract=off"], "orbdens.hip": ["-ffp-contract=off"], "orbresp.hip": ["-ffp-contract=off"], "orbsmear.hip": ["-ffp-contract=off"], "orbpurify.hip": ["-ffp-contract=off"], "orbbond.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=on", "-Wall", "-Wno-unused-function"]
 
 

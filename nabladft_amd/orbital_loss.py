@@ -54,6 +54,14 @@ occupied and the virtual side does not converge: status 4, NaN in that molecule'
 ``smeared_solution`` stay the route for those.  ``QHNetPurifiedDensityLightning`` is ``QHNetDensityLightning`` on it.  Tested against the same yardsticks as
 ``orbital_solution`` and against ``orbital_solution`` itself (tests/orbital_purify_ref.py).
 
+**Bond orders.**  ``bond_orders`` gives the Mayer bond-order table and the atomic valences of a closed-shell density under ``S``: with ``P = D S``,
+``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` and ``V_A = sum_{B != A} B_AB`` (``S = None``: the Wiberg index of an orthogonal basis).  The reverse forms
+``E = dL/dP`` elementwise (``E_mu,nu = (Gamma_AB + Gamma_BA) P_nu,mu``, ``Gamma_AB = gB_AB + (A != B) gV_A``) and then ``dL/dD = sym(E S)``, ``dL/dS = sym(D E)`` as
+float64 matrix-instruction products (csrc/orbbond.hip), exactly symmetric and bitwise reproducible.  For an idempotent density, ``(DS)^2 = 2 DS``, the rows sum
+to twice the Mulliken populations: ``sum_B B_AB = 2 pop_A``.  ``BondOrderLoss`` and ``QHNetBondOrderLightning`` put the table beside the other targets.  Closed
+shells only (no spin-density term), at most 32 orbitals per atom, no Löwdin analysis (it needs ``S^(1/2)`` and its derivative).  Tested against a numpy
+restatement and ``torch`` autograd (tests/orbital_bond_ref.py).
+
 Limits (each raises, nothing degrades silently): what ``BatchedOrbitals`` has -- 1..1024 orbitals per molecule, closed shells or Fermi occupations (no spin
 polarisation), MI355X only, no CPU path.
 """
@@ -65,7 +73,8 @@ import torch
 from torch import nn
 
 from .lightning import QHNetLightning
-from .orbitals import BatchedOrbitals, BatchedPurification, Orthogonalizer, _orb_ptr_of, _require_gpu, check_occupied, electron_counts, mulliken_charges, occupied_counts  # noqa: F401
+from .orbitals import (BatchedOrbitals, BatchedPurification, Orthogonalizer, _orb_ptr_of, _require_gpu, bond_layout, check_occupied, dense_bond_orders,  # noqa: F401
+                       electron_counts, mulliken_charges, occupied_counts)
 
 
 class _OrbitalEnergies(torch.autograd.Function):
@@ -397,6 +406,96 @@ class QHNetDensityLightning(QHNetOrbitalLightning):
         return total
 
 
+class _BondOrders(torch.autograd.Function):
+    """Forward: ``nq_orb_bond_product`` and ``nq_orb_bond_reduce``.  Backward: ``nq_orb_bond_backward`` (``E`` elementwise, then ``sym(E S)`` and, where ``S``
+    asks for it, ``sym(D E)`` in one launch); nothing is launched without an upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, orb, plan, D, S):
+        ctx.set_materialize_grads(False)
+        bond, valence, Pm = orb.bond_orders(D, plan, S)
+        ctx.orb, ctx.plan = orb, plan
+        ctx.save_for_backward(D, S, Pm)
+        ctx.s = None if S is None else (S.shape, S.dtype)
+        return bond, valence
+
+    @staticmethod
+    def backward(ctx, g_bond, g_valence):
+        D, S, Pm = ctx.saved_tensors
+        want_d = ctx.needs_input_grad[2]
+        want_s = ctx.s is not None and ctx.needs_input_grad[3]
+        if (g_bond is None and g_valence is None) or not (want_d or want_s):
+            return None, None, None, None
+        f64 = lambda g: None if g is None else g.to(torch.float64).reshape(-1).contiguous()
+        gD, gS = ctx.orb.bond_orders_backward(ctx.plan, f64(g_bond), f64(g_valence), Pm, D if want_s else None, S, want_d, want_s)
+        return None, None, gD.view(D.shape) if want_d else None, gS.to(ctx.s[1]).view(ctx.s[0]) if want_s else None
+
+
+def bond_orders(D: torch.Tensor, plan, S_packed: Optional[torch.Tensor] = None, orbitals: Optional[BatchedOrbitals] = None):
+    """Differentiable Mayer bond orders and atomic valences of a packed float64 closed-shell density (carrying the factor 2) -> ``(bond [Q], valence [N])``,
+    float64 on the device: with ``P = D S``, ``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` over the ``n^2`` ordered atom pairs of every molecule, ``B_AA``
+    included (``bond_layout`` / ``dense_bond_orders`` give a molecule's ``[n, n]`` table, exactly symmetric), and ``V_A = sum_{B != A} B_AB``.  ``S_packed = None``:
+    the Wiberg index of an orthogonal basis.  Gradients for ``D`` and, where it requires one, ``S_packed`` (a float32 ``S`` gets a float32 gradient), with respect
+    to SYMMETRIC matrices, spread over both triangles (the convention of this module): ``dL/dD = sym(E S)``, ``dL/dS = sym(D E)`` with
+    ``E_mu,nu = (Gamma_AB + Gamma_BA) P_nu,mu`` and ``Gamma_AB = g_bond_AB + (A != B) g_valence_A``.  On the ``D`` of ``orbital_solution`` / ``smeared_solution``
+    / ``purified_density_matrix`` the gradients flow on to ``H`` and ``S`` through their response chains.  ``orbitals``: the solution (or purification) of the
+    same batch, whose state the kernels read the layout from (None: one is prepared, which synchronises the stream once).  Limits: closed shells, at most 32
+    orbitals per atom (NaN in that atom's row and column), 1..1024 orbitals per molecule; no Löwdin analysis."""
+    _require_gpu(D)
+    orb = BatchedOrbitals(plan, D.device) if orbitals is None else orbitals
+    return _BondOrders.apply(orb, plan, D, S_packed)
+
+
+class BondOrderLoss(_PackedMeanLoss):
+    """``kind`` "mae" | "mse" of bond-order tables: the mean over the ``n^2`` entries of each molecule, then the mean over the molecules.  ``mol_ptr`` [B+1]: the
+    atoms of every molecule (the batch's ``ptr``).  ``charge`` is what ``QHNetBondOrderLightning`` counts the occupied orbitals with."""
+
+    def forward(self, b_pred: torch.Tensor, b_target: torch.Tensor, mol_ptr) -> torch.Tensor:
+        n = np.diff(_orb_ptr_of(mol_ptr))
+        return self._mean(b_pred, b_target, n * n)
+
+
+class QHNetBondOrderLightning(QHNetDensityLightning):
+    """``QHNetDensityLightning`` with a term on the Mayer bond orders: ``losses`` / ``loss_coefs`` take ``"bond_orders"`` (a ``BondOrderLoss``) beside the parent's
+    keys.  The bond orders of the prediction (``bond_orders`` of the density of ``orbital_solution``, under ``batch.overlap``) and of the detached target come
+    from the SAME single solve of each that serves the parent's keys.  With the coefficient at 0 (or without the key) the step is the parent's."""
+
+    BOND = "bond_orders"
+    KEYS = QHNetDensityLightning.KEYS + (BOND,)
+
+    def _evaluate(self, batch):
+        active = self._active()
+        if self.BOND not in active:
+            return super()._evaluate(batch)
+        if not self._packed():
+            raise ValueError("QHNetBondOrderLightning needs packed losses (HamiltonianLoss, OrbitalEnergyLoss, DensityMatrixLoss, MullikenChargeLoss, BondOrderLoss)")
+        preds, targets, loss_args = QHNetLightning._evaluate(self, batch)
+        charges = [getattr(self.hparams.losses[k], "charge", 0) for k in active]
+        if any(not np.array_equal(np.asarray(c), np.asarray(charges[0])) for c in charges[1:]):
+            raise ValueError("the orbital losses count the occupied orbitals with different charges")
+        plan, asm = self.net.last_plan, self.net._asm
+        overlap = getattr(batch, "overlap", None)
+        S = None if overlap is None else asm.pack_targets(plan, overlap)
+        op = _orb_ptr_of(plan)
+        n_occ = occupied_counts(batch.z, batch.ptr, charges[0], op)
+        Hp, Ht = preds["hamiltonian"], targets["hamiltonian"]
+        sol_t = BatchedOrbitals(op, Hp.device).solve(Ht, S)
+        eps, D, sol_p = orbital_solution(Hp, S, op, n_occ, return_solution=True)
+        D_t = sol_t.density(n_occ)
+        for k in active:
+            if k == "orbital_energies":
+                preds[k], targets[k], preds[k + "_args"] = eps, sol_t.energies, (n_occ, op)
+            elif k == "density_matrix":
+                preds[k], targets[k], preds[k + "_args"] = D, D_t, (op,)
+            elif k == "mulliken_charges":
+                preds[k] = mulliken_charges(batch.z, populations(D, plan, S, None, sol_p)[0])
+                targets[k] = mulliken_charges(batch.z, sol_t.populations(D_t, plan, S)[0])
+                preds[k + "_args"] = (batch.ptr,)
+            else:
+                preds[k], targets[k], preds[k + "_args"] = bond_orders(D, plan, S, sol_p)[0], sol_t.bond_orders(D_t, plan, S)[0], (batch.ptr,)
+        return preds, targets, loss_args
+
+
 SmearedSolution = namedtuple("SmearedSolution", "eps D occ mu entropy")
 SmearedSolution.__doc__ = """What ``smeared_solution`` returns, float64 on the device: ``eps`` [M], ``D`` [P], ``occ`` = F [M], ``mu`` [B], ``entropy`` [B] (units of k_B)."""
 
@@ -597,4 +696,5 @@ class QHNetPurifiedDensityLightning(QHNetDensityLightning):
 
 __all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "orbital_solution", "density_matrix", "populations",
            "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "SmearedSolution", "smeared_solution", "smeared_density_matrix",
-           "QHNetSmearedDensityLightning", "purified_density_matrix", "QHNetPurifiedDensityLightning"]
+           "QHNetSmearedDensityLightning", "purified_density_matrix", "QHNetPurifiedDensityLightning", "bond_orders", "BondOrderLoss", "QHNetBondOrderLightning",
+           "bond_layout", "dense_bond_orders"]

@@ -19,6 +19,10 @@ on densities or populations the response of the occupied subspace: both are ``na
 After a solve, ``density(n_occ)`` gives the closed-shell density matrix ``D = 2 sum_occ c_k c_k^T`` (and the energy-weighted one) and ``populations(D, plan, S)``
 the Mulliken populations per atom, the electron count ``Tr(D S)`` and the band energy ``Tr(D H)`` (csrc/orbdens.hip), all on the device.
 
+**Bond orders.**  ``bond_orders(D, plan, S)`` gives the Mayer bond-order table ``B_AB = sum_{mu in A, nu in B} (DS)_mu,nu (DS)_nu,mu`` of every molecule (the Wiberg
+index without ``S``) and the atomic valences ``V_A = sum_{B != A} B_AB``, ``bond_orders_backward`` their reverse (csrc/orbbond.hip;
+``nabladft_amd.orbital_loss.bond_orders`` is the differentiable call).  Closed shells only, at most ``MAX_ATOM_ORBITALS`` = 32 orbitals per atom, no Löwdin analysis.
+
 **Smearing.**  ``fermi(n_elec, kT)`` gives Fermi-Dirac occupations ``F_k = 2 / (1 + exp((eps_k - mu) / kT))`` with the chemical potential fixed by the electron
 count (``electron_counts``: odd counts and fractions are fine), ``smeared_density(occ)`` the density ``sum_k F_k c_k c_k^T`` and ``smeared_response`` its
 gradient chain over all orbital pairs, evaluated without dividing by a difference of orbital energies (csrc/orbsmear.hip;
@@ -43,6 +47,7 @@ from . import _lib
 from ._devstate import DeviceState
 
 MAX_ORBITALS = 1024
+MAX_ATOM_ORBITALS = 32        # per atom in the bond-order kernels (NQ_BD_MAX_ATOM_ORB of csrc/orbbond.hip)
 MAX_QL_SWEEPS = 60            # per eigenvalue (NQ_ORB_MAX_ITER of csrc/orbitals.hip)
 FIGURES = ("eps_mae_occ", "eps_mae_all", "psi_sim_occ", "homo_abs_err", "lumo_abs_err", "gap_abs_err", "psi_sim_min_occ")
 
@@ -120,6 +125,28 @@ def check_occupied(n_occ, orb_ptr) -> np.ndarray:
         b = int(bad[0])
         raise ValueError(f"molecule {b}: n_occ={int(no[b])} outside 1..m={int(m[b])}")
     return no
+
+
+def bond_layout(mol_ptr) -> np.ndarray:
+    """``bond_ptr`` int64 [B+1] on the host from the atoms' ``mol_ptr`` [B+1]: molecule b owns the ``n_b^2`` ordered atom pairs ``(A, B)``, ``A = B`` included,
+    row-major at ``bond_ptr[b]``; ``Q = bond_ptr[B]`` (the ragged layout of the Graphormer3D ``pair_ptr``)."""
+    mp = _host_ptr(mol_ptr)
+    if mp.shape[0] < 2 or np.any(np.diff(mp) < 1):
+        raise ValueError("bond_layout: mol_ptr needs at least one molecule and one atom in each")
+    n = np.diff(mp)
+    return np.concatenate([[0], np.cumsum(n * n)]).astype(np.int64)
+
+
+def dense_bond_orders(bond, mol_ptr, b: int):
+    """Molecule ``b``'s ``[n_b, n_b]`` table as a view of the flat ``bond`` [Q] (a tensor or an array; ``mol_ptr`` [B+1]: the atoms of every molecule)."""
+    mp = _host_ptr(mol_ptr)
+    bp = bond_layout(mp)
+    if not 0 <= b < mp.shape[0] - 1:
+        raise IndexError(f"molecule {b} of {mp.shape[0] - 1}")
+    if bond.shape[0] != int(bp[-1]) or len(bond.shape) != 1:
+        raise ValueError(f"bond has {tuple(bond.shape)} entries, mol_ptr counts {int(bp[-1])}")
+    n = int(mp[b + 1] - mp[b])
+    return bond[int(bp[b]):int(bp[b + 1])].reshape(n, n)
 
 
 def _failure_text(b: int, status: int, info: int, m: int) -> str:
@@ -491,6 +518,82 @@ class BatchedOrbitals:
                                                               *[_lib.ptr(o) for o in outs], _lib.stream_ptr()))
         return tuple(outs)
 
+    # ---- bond orders (csrc/orbbond.hip) ------------------------------------------------------------------------------------------------------------------------
+    def _bond_tables(self, plan):
+        """``(N, Q, mol_ptr int32, atom_orb_ptr int64, bond_ptr int64)`` of a plan, the three tables on the device; one small device -> host copy of ``mol_ptr``,
+        remembered per plan."""
+        st, dev = self.state, self.state.buf.device
+        cached = getattr(self, "_bond_cache", None)
+        if cached is not None and cached[0] is plan:
+            return cached[1]
+        if int(plan.B) != st.B or int(plan.m_total) != st.M or int(plan.total) != st.P:
+            raise ValueError("the plan belongs to another batch")
+        N = int(plan.N)
+        mp = _host_ptr(plan.mol_ptr)
+        if mp.shape[0] != st.B + 1 or plan.orb_ptr.numel() != N + 1 or int(mp[0]) != 0 or int(mp[-1]) != N:
+            raise ValueError("the plan's mol_ptr / orb_ptr do not have B + 1 / N + 1 entries")
+        bp = bond_layout(mp)
+        out = (N, int(bp[-1]), plan.mol_ptr.to(device=dev, dtype=torch.int32).contiguous(), plan.orb_ptr.to(device=dev, dtype=torch.int64).contiguous(),
+               torch.from_numpy(bp).to(dev))
+        self._bond_cache = (plan, out)
+        return out
+
+    def bond_product(self, D: torch.Tensor, S_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``P = D S`` per molecule (``nq_orb_bond_product``), packed float64 [P], not symmetric; only the lower triangles of ``D`` and ``S`` are read.
+        ``S_packed = None``: ``D`` made symmetric from its lower triangle."""
+        st = self.state
+        Dp = self._f64(D, st.P, "D")
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        out = self._scratch(st.P)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_bond_product(_lib.ptr(st.buf), *st._dims, _lib.ptr(Dp), _lib.ptr(S), int(S is not None and S.dtype == torch.float64),
+                                                       _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def bond_reduce(self, Pm: torch.Tensor, plan, valence: bool = True):
+        """``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` and (``valence``) ``V_A = sum_{B != A} B_AB`` (``nq_orb_bond_reduce``) -> ``(bond [Q], valence [N] or
+        None)``, float64 on the device; ``bond`` is exactly symmetric inside each molecule's ``[n, n]`` block (``bond_layout``)."""
+        st, dev = self.state, self.state.buf.device
+        N, Q, mol_ptr, atom_ptr, bond_ptr = self._bond_tables(plan)
+        bond = self._scratch(Q)
+        val = torch.empty(N, dtype=torch.float64, device=dev) if valence else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().nq_orb_bond_reduce(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(Pm, st.P, "P")), N, Q, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
+                                                      _lib.ptr(bond_ptr), _lib.ptr(bond), _lib.ptr(val), _lib.stream_ptr()))
+        return bond, val
+
+    def bond_orders(self, D: torch.Tensor, plan, S_packed: Optional[torch.Tensor] = None):
+        """Mayer bond orders and valences of a packed closed-shell density ``D`` (float64 [P], carrying the factor 2: what ``density()`` returns) ->
+        ``(bond [Q], valence [N], P [P])``, float64 on the device: ``P = D S``, ``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` (``B_AA`` included; molecule b's
+        table is ``dense_bond_orders(bond, plan.mol_ptr, b)``), ``V_A = sum_{B != A} B_AB``.  ``plan``: the ``BlockAssembler`` / ``IrrepsAssembler`` plan of the batch
+        (its ``mol_ptr`` and per-atom ``orb_ptr``).  ``S_packed = None``: the Wiberg index of an orthogonal basis.  An atom with more than 32 orbitals gets NaN
+        in its row and column, a molecule the solver failed on NaN in all its entries.  Two launches (three with the valences); nothing is read back."""
+        Pm = self.bond_product(D, S_packed)
+        bond, val = self.bond_reduce(Pm, plan)
+        return bond, val, Pm
+
+    def bond_orders_backward(self, plan, g_bond, g_valence, Pm: torch.Tensor, D=None, S_packed=None, want_d: bool = True, want_s: bool = False, return_e: bool = False):
+        """The reverse of ``bond_orders`` (``nq_orb_bond_backward``): upstream gradients ``g_bond`` [Q] and ``g_valence`` [N] (float64, each may be None) and the
+        ``P`` of the forward -> ``(gD or None, gS or None)``, packed float64 [P], exactly symmetric, with respect to symmetric ``D`` and ``S``:
+        ``sym(E S)`` and ``sym(D E)`` with ``E_mu,nu = (Gamma_AB + Gamma_BA) P_nu,mu``, ``Gamma_AB = g_bond_AB + (A != B) g_valence_A``.  ``want_s`` needs ``D`` and
+        ``S_packed``.  ``return_e``: ``E`` as a third member (for tests)."""
+        st, dev = self.state, self.state.buf.device
+        N, Q, mol_ptr, atom_ptr, bond_ptr = self._bond_tables(plan)
+        if not (want_d or want_s):
+            raise ValueError("bond_orders_backward: neither gradient is asked for")
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        if want_s and (S is None or D is None):
+            raise ValueError("bond_orders_backward: the gradient of S needs S_packed and D")
+        Dp = self._f64(D, st.P, "D") if want_s else None
+        gb = None if g_bond is None else self._f64(g_bond, Q, "g_bond")
+        gv = None if g_valence is None else self._f64(g_valence, N, "g_valence")
+        E, gD, gS = self._scratch(st.P), self._scratch(st.P, want_d), self._scratch(st.P, want_s)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().nq_orb_bond_backward(_lib.ptr(st.buf), *st._dims, _lib.ptr(gb), _lib.ptr(gv), _lib.ptr(self._f64(Pm, st.P, "P")), _lib.ptr(Dp),
+                                                        _lib.ptr(S), int(S is not None and S.dtype == torch.float64), N, Q, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
+                                                        _lib.ptr(bond_ptr), _lib.ptr(E), _lib.ptr(gD), _lib.ptr(gS), _lib.stream_ptr()))
+        return (gD, gS, E) if return_e else (gD, gS)
+
     def check(self) -> "BatchedOrbitals":
         st = self.state
         st.header()
@@ -525,8 +628,8 @@ class BatchedPurification:
     float64 [P], symmetric matrices in the convention of ``BatchedOrbitals.weighted_gram``; it runs the same ``X`` sequence again along the logged branches
     with no stored iterates, no eigenpairs and no division.  ``iterations`` int32 [B] on the device.  ``check()`` reads the status once (a host
     synchronisation) and raises ``RuntimeError`` naming the molecule whose overlap was not positive definite (status 1) or whose purification did not
-    converge (status 4: needs an open gap).  A failed molecule has NaN in its own blocks only.  ``populations`` / ``populations_backward`` are
-    ``BatchedOrbitals``'.  No energies, no smearing, closed shells only."""
+    converge (status 4: needs an open gap).  A failed molecule has NaN in its own blocks only.  ``populations`` / ``populations_backward`` / ``bond_orders`` /
+    ``bond_orders_backward`` are ``BatchedOrbitals``'.  No energies, no smearing, closed shells only."""
 
     def __init__(self, orb_ptr, device="cuda"):
         self.state = OrbitalState(orb_ptr, device)
@@ -544,6 +647,11 @@ class BatchedPurification:
     _scratch = BatchedOrbitals._scratch
     populations = BatchedOrbitals.populations
     populations_backward = BatchedOrbitals.populations_backward
+    _bond_tables = BatchedOrbitals._bond_tables
+    bond_product = BatchedOrbitals.bond_product
+    bond_reduce = BatchedOrbitals.bond_reduce
+    bond_orders = BatchedOrbitals.bond_orders
+    bond_orders_backward = BatchedOrbitals.bond_orders_backward
 
     def _call(self, name, *args):
         st = self.state
@@ -738,4 +846,4 @@ def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
     return zz.to(device=atom_pop.device, dtype=torch.float64).reshape(-1) - atom_pop.to(torch.float64)
 
 
-__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "OrbitalState", "OrbitalErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "MAX_ORBITALS", "FIGURES"]
+__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "OrbitalState", "OrbitalErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
