@@ -893,6 +893,22 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  *     (S = NULL: sym(E)) and out_gS = sym(D E) = 1/2 (D E + E^T D) (each NULL: skipped; out_gS needs S and D, and D is passed only with out_gS), the gradients
  *     with respect to symmetric D and S spread over both triangles, lower-triangle 64 x 64 tiles mirrored: exactly symmetric.  An orbital no valid atom owns
  *     carries NaN.
+ * Löwdin analysis (csrc/orblowdin.hip; entry points added, ABI 17 unchanged): A = S^(1/2) and A^- = S^(-1/2), the congruences A D A and A^- H A^- and the
+ * reverse of both, after a STANDARD solve of S itself (nq_orb_solve with H = S and S = NULL: eps = s, row k of coeff = u_k, S = U diag(s) U^T).
+ *   nq_orb_low_weights: out_half [M] = a_k = sqrt(s_k), out_inv_half [M] = 1 / a_k, out_cond [B] = s_max / s_min, one workgroup per molecule.  A molecule with
+ *     status != 0, a non-finite s_k or s_min <= 0 gets out_info [B] = 1 and NaN in all of its outputs (0 otherwise).  A and A^- [P] are then ONE nq_orb_wgram
+ *     launch with w0 = out_half and w1 = out_inv_half.  Reads eps: a purification state is refused (header status -3).
+ *   nq_orb_low_product: out_Y [P] = M X per molecule, the general m x m product of two symmetric operands; only the lower triangles of Msym (float32 or float64
+ *     by m_f64) and of X (float64) are read.  The product loop is nq_orb_bond_product's.  Only the layout of the state is read.
+ *   nq_orb_low_symprod: out [P] = alpha sym(X E) = alpha / 2 (X E + E^T X) (side 0) or alpha sym(E X) = alpha / 2 (E X + X E^T) (side 1); E [P] any matrix, X [P]
+ *     symmetric, its lower triangle read; lower-triangle 64 x 64 tiles mirrored: exactly symmetric.  Only the layout of the state is read.  With Y = M X:
+ *     M^L = X M X = symprod(Y, X, 0, 1); for a symmetric G = dL/dM^L: dL/dM = symprod(G X, X, 0, 1), dL/dX = Y G + G Y^T = symprod(Y, G, 1, 2).
+ *   nq_orb_low_symmetrize: out [P] = (G + G^T) / 2 per molecule, G [P] any matrix, lower-triangle tiles mirrored: exactly symmetric; what makes an upstream
+ *     gradient fit for the two launches above, on the device.  Only the layout of the state is read.
+ *   nq_orb_low_mo: A_out [P] = K o (U^T T), the diagonal included, T [P] = g U as nq_orb_resp_project leaves it over all orbitals (n_occ = m, occ_ptr =
+ *     pack_ptr, O = P); kind 0: K_ij = 1 / (a_i + a_j) (the reverse of S^(1/2)), kind 1: K_ij = -1 / (a_i a_j (a_i + a_j)) (of S^(-1/2)), a = sqrt(eps)
+ *     recomputed from the state: no difference of eigenvalues is divided.  dL/dS = U A_out U^T is then nq_orb_smear_back (A_S = NULL) and nq_orb_syr2k over all
+ *     orbitals.  A molecule nq_orb_low_weights would flag gets NaN.  Reads eps and coeff: a purification state is refused (header status -3).
  * All float64 on v_mfma_f64_16x16x4_f64 through the tile routine of the response kernels, the grids sized from (B, M, P), no atomics, fixed summation orders:
  * bitwise reproducible and independent of the rest of the batch.  status != 0: NaN in the molecule's own blocks of every output.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
@@ -948,6 +964,11 @@ int nq_orb_bond_reduce(void* state, int32_t B, int32_t M, int64_t P, const doubl
 int nq_orb_bond_backward(void* state, int32_t B, int32_t M, int64_t P, const double* gB_or_null, const double* gV_or_null, const double* Pm,
                          const double* D_or_null, const void* S_or_null, int32_t s_f64, int32_t N, int64_t Q, const int32_t* mol_ptr, const int64_t* atom_orb_ptr,
                          const int64_t* bond_ptr_or_null, double* E, double* out_gD_or_null, double* out_gS_or_null, void* stream);
+int nq_orb_low_weights(void* state, int32_t B, int32_t M, int64_t P, double* out_half, double* out_inv_half, double* out_cond, int32_t* out_info, void* stream);
+int nq_orb_low_product(void* state, int32_t B, int32_t M, int64_t P, const void* Msym, int32_t m_f64, const double* X, double* out_Y, void* stream);
+int nq_orb_low_symprod(void* state, int32_t B, int32_t M, int64_t P, const double* E, const double* X, int32_t side, double alpha, double* out, void* stream);
+int nq_orb_low_symmetrize(void* state, int32_t B, int32_t M, int64_t P, const double* G, double* out, void* stream);
+int nq_orb_low_mo(void* state, int32_t B, int32_t M, int64_t P, int32_t kind, const double* T, double* A_out, void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

@@ -28,6 +28,9 @@ Public surface mirrors the reference plugin classes for this path:
                                     products, no solve (orbitals.py, orbital_loss.py; no reference code, tested against numpy and the solver route)
   nabladft_amd.bond_orders / BondOrderLoss / QHNetBondOrderLightning <-> the same slots: Mayer bond orders and atomic valences of a density matrix and their
                                     gradients (orbitals.py, orbital_loss.py; no reference code, tested against numpy and torch autograd)
+  nabladft_amd.lowdin_basis / lowdin_populations / lowdin_bond_orders / lowdin_hamiltonian / QHNetLowdinLightning <-> the same slots: S^(1/2), S^(-1/2), Löwdin
+                                    populations, Wiberg indices and the orthogonalised Hamiltonian with gradients that divide no difference of levels of S
+                                    (orbitals.py, orbital_loss.py; no reference code, tested against numpy, scipy and torch autograd)
   nabladft_amd.spk.*            <-> the schnetpack classes config/model/{painn,schnet}.yaml instantiate (parity unpinned)
   nabladft_amd.read_energy_database / ArenaLoader <-> PyGNablaDFT.process + DataLoader collate (dataset/pyg_datasets.py:101-109)
 """
@@ -48,13 +51,15 @@ from .md import BatchedMD, PYGAseInterface  # noqa: F401
 from . import vibrations  # noqa: F401
 from .vibrations import BatchedVibrations  # noqa: F401
 from . import orbitals  # noqa: F401
-from .orbitals import BatchedOrbitals, BatchedPurification, FermiResult, OrbitalErrors, OrbitalState, electron_counts, mulliken_charges, occupied_counts, bond_layout, dense_bond_orders  # noqa: F401
+from .orbitals import BatchedOrbitals, BatchedPurification, FermiResult, OrbitalErrors, OrbitalState, electron_counts, mulliken_charges, occupied_counts, bond_layout, dense_bond_orders, LowdinBasis  # noqa: F401
 from .orbital_loss import (DensityMatrixLoss, MullikenChargeLoss, OrbitalEnergyLoss, QHNetDensityLightning, QHNetOrbitalLightning,  # noqa: F401
                            QHNetSmearedDensityLightning, SmearedSolution, density_matrix, orbital_energies, orbital_solution, populations,
                            smeared_density_matrix, smeared_solution, purified_density_matrix, QHNetPurifiedDensityLightning, bond_orders, BondOrderLoss,
-                           QHNetBondOrderLightning)
+                           QHNetBondOrderLightning, lowdin_basis, lowdin_density, lowdin_hamiltonian, lowdin_populations, lowdin_charges, lowdin_bond_orders,
+                           LowdinChargeLoss, QHNetLowdinLightning)
 from .data import ArenaLoader, ConformerArena, HamiltonianBatch, HamiltonianDatabase, HamiltonianDataset, hamiltonian_batch, read_energy_database  # noqa: F401
 
 __all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "DimeNetPlusPlusForceLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
            "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "BatchedVibrations", "PYGAseInterface", "BatchedOrbitals", "OrbitalState", "OrbitalErrors", "orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "occupied_counts", "orbital_solution", "density_matrix", "populations", "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "FermiResult", "SmearedSolution", "smeared_solution", "smeared_density_matrix", "QHNetSmearedDensityLightning", "BatchedPurification", "purified_density_matrix", "QHNetPurifiedDensityLightning", "bond_orders", "BondOrderLoss", "QHNetBondOrderLightning",
-           "bond_layout", "dense_bond_orders"]
+           "bond_layout", "dense_bond_orders", "LowdinBasis", "lowdin_basis", "lowdin_density", "lowdin_hamiltonian", "lowdin_populations", "lowdin_charges",
+           "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning"]

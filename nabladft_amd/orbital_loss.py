@@ -59,8 +59,20 @@ occupied and the virtual side does not converge: status 4, NaN in that molecule'
 ``E = dL/dP`` elementwise (``E_mu,nu = (Gamma_AB + Gamma_BA) P_nu,mu``, ``Gamma_AB = gB_AB + (A != B) gV_A``) and then ``dL/dD = sym(E S)``, ``dL/dS = sym(D E)`` as
 float64 matrix-instruction products (csrc/orbbond.hip), exactly symmetric and bitwise reproducible.  For an idempotent density, ``(DS)^2 = 2 DS``, the rows sum
 to twice the Mulliken populations: ``sum_B B_AB = 2 pop_A``.  ``BondOrderLoss`` and ``QHNetBondOrderLightning`` put the table beside the other targets.  Closed
-shells only (no spin-density term), at most 32 orbitals per atom, no Löwdin analysis (it needs ``S^(1/2)`` and its derivative).  Tested against a numpy
-restatement and ``torch`` autograd (tests/orbital_bond_ref.py).
+shells only (no spin-density term), at most 32 orbitals per atom.  Tested against a numpy restatement and ``torch`` autograd (tests/orbital_bond_ref.py).
+
+**Löwdin analysis.**  With ``S = U diag(s) U^T``, ``a = sqrt(s)``, ``A = S^(1/2) = U diag(a) U^T`` and ``A^- = S^(-1/2)``: ``lowdin_basis`` makes both from ONE
+standard solve of ``S`` and one ``nq_orb_wgram`` launch; ``lowdin_density`` gives ``D^L = A D A``, ``lowdin_hamiltonian`` gives ``H^L = A^- H A^-`` (the matrix
+SchNOrb-style models train on; its eigenvalues are the generalised ``eps``), ``lowdin_populations`` the populations ``q_A = sum_{mu in A} D^L_mu,mu`` (their sum
+is ``Tr(D S)``), ``lowdin_bond_orders`` the Wiberg indices ``W_AB = sum_{mu in A, nu in B} (D^L_mu,nu)^2`` and the valences; for an idempotent closed-shell
+density ``sum_B W_AB = 2 q_A``.  The congruence ``M^L = sym(X Y)``, ``Y = M X``, has the reverse ``dL/dM = sym(X (G X))``, ``dL/dX = Y G + G Y^T``; the matrix
+functions have the Daleckii-Krein reverse ``dL/dS = U [K o (U^T sym(g) U)] U^T`` with ``K_ij = 1 / (a_i + a_j)`` for ``A`` and ``-1 / (a_i a_j (a_i + a_j))`` for
+``A^-``, the diagonal included: NO difference of levels of ``S`` is divided, so equal levels (``S = I``, identical atoms far apart) give finite gradients where
+the backward of ``torch.linalg.eigh`` returns non-finite values (csrc/orblowdin.hip, float64 matrix instructions, exactly symmetric, bitwise reproducible).
+``LowdinChargeLoss`` and ``QHNetLowdinLightning`` put the charges and the table beside the other targets.  ``S`` belongs to the conformer, not to the model: a
+``LowdinBasis`` can be cached across epochs.  Limits: closed shells only, ``S`` positive definite (info 1 and NaN otherwise), 1..1024 orbitals per molecule,
+at most 32 orbitals per atom for the bond table, no ``S^(1/2)`` without a decomposition.  Tested against a numpy restatement, ``scipy.linalg.sqrtm`` and
+``torch`` autograd (tests/orbital_lowdin_ref.py).
 
 Limits (each raises, nothing degrades silently): what ``BatchedOrbitals`` has -- 1..1024 orbitals per molecule, closed shells or Fermi occupations (no spin
 polarisation), MI355X only, no CPU path.
@@ -73,7 +85,7 @@ import torch
 from torch import nn
 
 from .lightning import QHNetLightning
-from .orbitals import (BatchedOrbitals, BatchedPurification, Orthogonalizer, _orb_ptr_of, _require_gpu, bond_layout, check_occupied, dense_bond_orders,  # noqa: F401
+from .orbitals import (BatchedOrbitals, BatchedPurification, LowdinBasis, Orthogonalizer, _orb_ptr_of, _require_gpu, bond_layout, check_occupied, dense_bond_orders,  # noqa: F401
                        electron_counts, mulliken_charges, occupied_counts)
 
 
@@ -440,7 +452,8 @@ def bond_orders(D: torch.Tensor, plan, S_packed: Optional[torch.Tensor] = None, 
     ``E_mu,nu = (Gamma_AB + Gamma_BA) P_nu,mu`` and ``Gamma_AB = g_bond_AB + (A != B) g_valence_A``.  On the ``D`` of ``orbital_solution`` / ``smeared_solution``
     / ``purified_density_matrix`` the gradients flow on to ``H`` and ``S`` through their response chains.  ``orbitals``: the solution (or purification) of the
     same batch, whose state the kernels read the layout from (None: one is prepared, which synchronises the stream once).  Limits: closed shells, at most 32
-    orbitals per atom (NaN in that atom's row and column), 1..1024 orbitals per molecule; no Löwdin analysis."""
+    orbitals per atom (NaN in that atom's row and column), 1..1024 orbitals per molecule.  The Löwdin counterpart (the Wiberg index of the symmetrically
+    orthogonalised density) is ``lowdin_bond_orders``."""
     _require_gpu(D)
     orb = BatchedOrbitals(plan, D.device) if orbitals is None else orbitals
     return _BondOrders.apply(orb, plan, D, S_packed)
@@ -463,18 +476,20 @@ class QHNetBondOrderLightning(QHNetDensityLightning):
     BOND = "bond_orders"
     KEYS = QHNetDensityLightning.KEYS + (BOND,)
 
-    def _evaluate(self, batch):
-        active = self._active()
-        if self.BOND not in active:
-            return super()._evaluate(batch)
+    def _solved_sides(self, batch, active, who: str, packed_names: str, need_overlap: bool = False):
+        """What every step with a density term does once, shared with the subclasses: the parent's packed matrices, the charges check, ONE
+        ``orbital_solution`` of the prediction and ONE detached solve of the target -> ``(preds, targets, loss_args, c)`` with
+        ``c = (plan, S, op, n_occ, eps, D, sol_p, sol_t, D_t)``."""
         if not self._packed():
-            raise ValueError("QHNetBondOrderLightning needs packed losses (HamiltonianLoss, OrbitalEnergyLoss, DensityMatrixLoss, MullikenChargeLoss, BondOrderLoss)")
+            raise ValueError(f"{who} needs packed losses ({packed_names})")
         preds, targets, loss_args = QHNetLightning._evaluate(self, batch)
         charges = [getattr(self.hparams.losses[k], "charge", 0) for k in active]
         if any(not np.array_equal(np.asarray(c), np.asarray(charges[0])) for c in charges[1:]):
             raise ValueError("the orbital losses count the occupied orbitals with different charges")
         plan, asm = self.net.last_plan, self.net._asm
         overlap = getattr(batch, "overlap", None)
+        if overlap is None and need_overlap:
+            raise ValueError(f"{who}: the Löwdin terms need batch.overlap (without an overlap they are the parent's Mulliken and Mayer terms)")
         S = None if overlap is None else asm.pack_targets(plan, overlap)
         op = _orb_ptr_of(plan)
         n_occ = occupied_counts(batch.z, batch.ptr, charges[0], op)
@@ -482,17 +497,170 @@ class QHNetBondOrderLightning(QHNetDensityLightning):
         sol_t = BatchedOrbitals(op, Hp.device).solve(Ht, S)
         eps, D, sol_p = orbital_solution(Hp, S, op, n_occ, return_solution=True)
         D_t = sol_t.density(n_occ)
+        return preds, targets, loss_args, (plan, S, op, n_occ, eps, D, sol_p, sol_t, D_t)
+
+    def _fill(self, k, preds, targets, batch, c):
+        """The entries of one of this class's keys from the two solutions."""
+        plan, S, op, n_occ, eps, D, sol_p, sol_t, D_t = c
+        if k == "orbital_energies":
+            preds[k], targets[k], preds[k + "_args"] = eps, sol_t.energies, (n_occ, op)
+        elif k == "density_matrix":
+            preds[k], targets[k], preds[k + "_args"] = D, D_t, (op,)
+        elif k == "mulliken_charges":
+            preds[k] = mulliken_charges(batch.z, populations(D, plan, S, None, sol_p)[0])
+            targets[k] = mulliken_charges(batch.z, sol_t.populations(D_t, plan, S)[0])
+            preds[k + "_args"] = (batch.ptr,)
+        else:
+            preds[k], targets[k], preds[k + "_args"] = bond_orders(D, plan, S, sol_p)[0], sol_t.bond_orders(D_t, plan, S)[0], (batch.ptr,)
+
+    def _evaluate(self, batch):
+        active = self._active()
+        if self.BOND not in active:
+            return super()._evaluate(batch)
+        preds, targets, loss_args, c = self._solved_sides(batch, active, "QHNetBondOrderLightning",
+                                                          "HamiltonianLoss, OrbitalEnergyLoss, DensityMatrixLoss, MullikenChargeLoss, BondOrderLoss")
         for k in active:
-            if k == "orbital_energies":
-                preds[k], targets[k], preds[k + "_args"] = eps, sol_t.energies, (n_occ, op)
-            elif k == "density_matrix":
-                preds[k], targets[k], preds[k + "_args"] = D, D_t, (op,)
-            elif k == "mulliken_charges":
-                preds[k] = mulliken_charges(batch.z, populations(D, plan, S, None, sol_p)[0])
-                targets[k] = mulliken_charges(batch.z, sol_t.populations(D_t, plan, S)[0])
+            self._fill(k, preds, targets, batch, c)
+        return preds, targets, loss_args
+
+class _LowdinBasis(torch.autograd.Function):
+    """Forward: ONE standard solve of ``S``, ``nq_orb_low_weights`` and ONE ``nq_orb_wgram`` launch.  Backward: per output WITH an upstream gradient the chain
+    ``nq_orb_resp_project`` -> ``nq_orb_low_mo`` -> ``nq_orb_smear_back`` -> ``nq_orb_syr2k`` over all orbital pairs; nothing is launched for an output without."""
+
+    @staticmethod
+    def forward(ctx, orb, S):
+        orb.solve(S)
+        ctx.set_materialize_grads(False)
+        half, inv_half, cond, info = orb.overlap_functions()
+        ctx.orb = orb
+        ctx.s = (S.shape, S.dtype)
+        ctx.mark_non_differentiable(cond, info)
+        return half, inv_half, cond, info
+
+    @staticmethod
+    def backward(ctx, g_half, g_inv, g_cond, g_info):
+        if (g_half is None and g_inv is None) or not ctx.needs_input_grad[1]:
+            return None, None
+        gS = None
+        for kind, g in ((0, g_half), (1, g_inv)):
+            if g is not None:
+                r = ctx.orb.matfun_response(g.to(torch.float64).reshape(-1).contiguous(), kind)
+                gS = r if gS is None else gS + r
+        return None, gS.to(ctx.s[1]).view(ctx.s[0])
+
+
+def lowdin_basis(S_packed: torch.Tensor, plan_or_orb_ptr) -> LowdinBasis:
+    """The symmetric orthogonalisation of every molecule of a batch -> ``LowdinBasis`` whose ``half`` = ``S^(1/2)`` and ``inv_half`` = ``S^(-1/2)`` (packed
+    float64 [P], exactly symmetric) carry gradients back to ``S_packed`` (a float32 ``S`` gets a float32 gradient, a symmetric matrix in the convention of
+    ``orbital_energies``).  One standard solve of ``S`` (latency-bound: the dominant cost), ``nq_orb_low_weights`` and one ``nq_orb_wgram`` launch; the backward
+    is the Daleckii-Krein form of the module text, which divides no difference of levels, and launches nothing for an output without an upstream gradient.
+    ``plan_or_orb_ptr`` as for ``BatchedOrbitals``.  One basis serves prediction and target of a step; ``S`` belongs to the conformer, so it can be cached
+    across epochs (``LowdinBasis.of`` builds one without gradients).  ``S`` must be positive definite: otherwise ``info = 1`` and NaN in that molecule's
+    blocks, which ``check()`` reports.  There is no ``S^(1/2)`` without a decomposition."""
+    _require_gpu(S_packed)
+    orb = BatchedOrbitals(plan_or_orb_ptr, S_packed.device)
+    return LowdinBasis(orb, *_LowdinBasis.apply(orb, S_packed))
+
+
+class _Congruence(torch.autograd.Function):
+    """Forward: ``Y = M X`` (``nq_orb_low_product``) and ``M^L = sym(X Y)`` (``nq_orb_low_symprod``).  Backward for ``G = dL/dM^L``, made symmetric first on the device (``nq_orb_low_symmetrize``):
+    ``dL/dM = sym(X (G X))`` (two launches) and ``dL/dX = 2 sym(Y G)`` (one); a half nobody asks for is skipped, nothing is launched without ``G``."""
+
+    @staticmethod
+    def forward(ctx, orb, M, X):
+        ctx.set_materialize_grads(False)
+        ML, Y = orb.sym_congruence(X, M)
+        ctx.orb = orb
+        ctx.m = (M.shape, M.dtype)
+        ctx.save_for_backward(X, Y)
+        return ML
+
+    @staticmethod
+    def backward(ctx, G):
+        X, Y = ctx.saved_tensors
+        want_m, want_x = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if G is None or not (want_m or want_x):
+            return None, None, None
+        # the products read the lower triangle of a symmetric G: one nq_orb_low_symmetrize launch first, whatever the upstream hands over
+        gM, gX = ctx.orb.sym_congruence_backward(G.to(torch.float64).reshape(-1).contiguous(), X, Y, want_m, want_x, symmetric=False)
+        return None, gM.to(ctx.m[1]).view(ctx.m[0]) if want_m else None, gX.view(X.shape) if want_x else None
+
+
+def _congruence(M, which, basis, name):
+    _require_gpu(M)
+    if not isinstance(basis, LowdinBasis):
+        raise TypeError(f"{name}: basis must be a LowdinBasis (lowdin_basis(S_packed, plan)), not {type(basis).__name__}")
+    P = basis.orbitals.state.P
+    if M.numel() != P:
+        raise ValueError(f"{name}: the matrix has {M.numel()} entries, the basis packs {P}")
+    return _Congruence.apply(basis.orbitals, M, getattr(basis, which))
+
+
+def lowdin_density(D: torch.Tensor, basis: LowdinBasis) -> torch.Tensor:
+    """The Löwdin density ``D^L = S^(1/2) D S^(1/2)`` of a packed symmetric density (float32 or float64; its lower triangle is read) -> packed float64 [P],
+    exactly symmetric, with gradients for ``D`` and, through ``basis.half``, for the ``S`` of ``lowdin_basis``."""
+    return _congruence(D, "half", basis, "lowdin_density")
+
+
+def lowdin_hamiltonian(H: torch.Tensor, basis: LowdinBasis) -> torch.Tensor:
+    """The Löwdin-orthogonalised Hamiltonian ``H^L = S^(-1/2) H S^(-1/2)`` (float32 or float64 ``H``; its lower triangle is read) -> packed float64 [P], exactly
+    symmetric; its eigenvalues are the generalised orbital energies.  Gradients for ``H`` (cast to its dtype) and, through ``basis.inv_half``, for ``S``."""
+    return _congruence(H, "inv_half", basis, "lowdin_hamiltonian")
+
+
+def lowdin_populations(D: torch.Tensor, plan, basis: LowdinBasis):
+    """Löwdin populations of a packed closed-shell density -> ``(atom_pop [N], nelec [B], None)``: ``populations(lowdin_density(D, basis), plan, None)``, that is
+    ``q_A = sum_{mu in A} D^L_mu,mu`` and ``nelec = Tr(D^L) = Tr(D S)``; differentiable with respect to ``D`` and ``S``."""
+    return populations(lowdin_density(D, basis), plan, None, None, basis.orbitals)
+
+
+def lowdin_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
+    """Löwdin charges ``Z_A - q_A`` from ``lowdin_populations`` (the arithmetic of ``mulliken_charges``)."""
+    return mulliken_charges(z, atom_pop)
+
+
+def lowdin_bond_orders(D: torch.Tensor, plan, basis: LowdinBasis):
+    """Wiberg indices in the Löwdin basis and the valences -> ``(bond [Q], valence [N])``: ``bond_orders(lowdin_density(D, basis), plan, None)``, that is
+    ``W_AB = sum_{mu in A, nu in B} (D^L_mu,nu)^2``; for an idempotent closed-shell density ``sum_B W_AB = 2 q_A``.  Differentiable with respect to ``D`` and
+    ``S``.  Limits: closed shells only, at most 32 orbitals per atom (NaN in that atom's row and column), ``S`` positive definite, 1..1024 orbitals."""
+    return bond_orders(lowdin_density(D, basis), plan, None, basis.orbitals)
+
+
+class LowdinChargeLoss(_PackedMeanLoss):
+    """``kind`` "mae" | "mse" of Löwdin charges (or populations) per atom: the mean over the atoms of each molecule, then the mean over the molecules.
+    ``mol_ptr`` [B+1]: the atoms of every molecule (the batch's ``ptr``).  ``charge`` is what ``QHNetLowdinLightning`` counts the occupied orbitals with."""
+
+    def forward(self, q_pred: torch.Tensor, q_target: torch.Tensor, mol_ptr) -> torch.Tensor:
+        return self._mean(q_pred, q_target, np.diff(_orb_ptr_of(mol_ptr)))
+
+
+class QHNetLowdinLightning(QHNetBondOrderLightning):
+    """``QHNetBondOrderLightning`` with terms in the Löwdin basis: ``losses`` / ``loss_coefs`` take ``"lowdin_charges"`` (a ``LowdinChargeLoss``) and
+    ``"lowdin_bond_orders"`` (a ``BondOrderLoss``) beside the parent's keys.  A step makes ONE ``lowdin_basis`` of ``batch.overlap`` (required), shared by the
+    prediction and the detached target; the densities come from the SAME single solve of each that serves the parent's keys.  With both coefficients at 0 (or
+    without the keys) the step is the parent's."""
+
+    LOWDIN = ("lowdin_charges", "lowdin_bond_orders")
+    KEYS = QHNetBondOrderLightning.KEYS + LOWDIN
+
+    def _evaluate(self, batch):
+        active = self._active()
+        if not any(k in active for k in self.LOWDIN):
+            return super()._evaluate(batch)
+        preds, targets, loss_args, c = self._solved_sides(batch, active, "QHNetLowdinLightning",
+                                                          "HamiltonianLoss, OrbitalEnergyLoss, DensityMatrixLoss, MullikenChargeLoss, BondOrderLoss, LowdinChargeLoss",
+                                                          need_overlap=True)
+        plan, S, op, n_occ, eps, D, sol_p, sol_t, D_t = c
+        basis = lowdin_basis(S, op)                                # one decomposition of S per step, for both sides
+        for k in active:
+            if k == "lowdin_charges":
+                preds[k] = lowdin_charges(batch.z, lowdin_populations(D, plan, basis)[0])
+                targets[k] = lowdin_charges(batch.z, lowdin_populations(D_t, plan, basis)[0]).detach()
                 preds[k + "_args"] = (batch.ptr,)
+            elif k == "lowdin_bond_orders":
+                preds[k], targets[k], preds[k + "_args"] = lowdin_bond_orders(D, plan, basis)[0], lowdin_bond_orders(D_t, plan, basis)[0].detach(), (batch.ptr,)
             else:
-                preds[k], targets[k], preds[k + "_args"] = bond_orders(D, plan, S, sol_p)[0], sol_t.bond_orders(D_t, plan, S)[0], (batch.ptr,)
+                self._fill(k, preds, targets, batch, c)
         return preds, targets, loss_args
 
 
@@ -697,4 +865,5 @@ class QHNetPurifiedDensityLightning(QHNetDensityLightning):
 __all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "orbital_solution", "density_matrix", "populations",
            "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "SmearedSolution", "smeared_solution", "smeared_density_matrix",
            "QHNetSmearedDensityLightning", "purified_density_matrix", "QHNetPurifiedDensityLightning", "bond_orders", "BondOrderLoss", "QHNetBondOrderLightning",
-           "bond_layout", "dense_bond_orders"]
+           "bond_layout", "dense_bond_orders", "LowdinBasis", "lowdin_basis", "lowdin_density", "lowdin_hamiltonian", "lowdin_populations", "lowdin_charges",
+           "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning"]

@@ -21,7 +21,14 @@ the Mulliken populations per atom, the electron count ``Tr(D S)`` and the band e
 
 **Bond orders.**  ``bond_orders(D, plan, S)`` gives the Mayer bond-order table ``B_AB = sum_{mu in A, nu in B} (DS)_mu,nu (DS)_nu,mu`` of every molecule (the Wiberg
 index without ``S``) and the atomic valences ``V_A = sum_{B != A} B_AB``, ``bond_orders_backward`` their reverse (csrc/orbbond.hip;
-``nabladft_amd.orbital_loss.bond_orders`` is the differentiable call).  Closed shells only, at most ``MAX_ATOM_ORBITALS`` = 32 orbitals per atom, no Löwdin analysis.
+``nabladft_amd.orbital_loss.bond_orders`` is the differentiable call).  Closed shells only, at most ``MAX_ATOM_ORBITALS`` = 32 orbitals per atom; the Löwdin counterpart is below.
+
+**Löwdin analysis.**  After a standard solve of ``S`` itself, ``overlap_functions()`` gives ``S^(1/2)`` and ``S^(-1/2)`` (``LowdinBasis`` holds them and the
+decomposition; one per batch serves prediction and target, and since ``S`` belongs to the conformer it can be cached across epochs), ``sym_congruence(X, M)``
+the Löwdin density ``S^(1/2) D S^(1/2)`` or the orthogonalised Hamiltonian ``S^(-1/2) H S^(-1/2)``, ``sym_congruence_backward`` / ``matfun_response`` their
+reverse down to ``S``, evaluated without dividing by a difference of levels of ``S`` (csrc/orblowdin.hip; ``nabladft_amd.orbital_loss.lowdin_basis`` /
+``lowdin_density`` / ``lowdin_populations`` / ``lowdin_bond_orders`` / ``lowdin_hamiltonian`` are the differentiable calls).  ``S`` must be positive definite
+(``info = 1`` and NaN otherwise); there is no ``S^(1/2)`` without a decomposition.
 
 **Smearing.**  ``fermi(n_elec, kT)`` gives Fermi-Dirac occupations ``F_k = 2 / (1 + exp((eps_k - mu) / kT))`` with the chemical potential fixed by the electron
 count (``electron_counts``: odd counts and fractions are fine), ``smeared_density(occ)`` the density ``sum_k F_k c_k c_k^T`` and ``smeared_response`` its
@@ -594,6 +601,94 @@ class BatchedOrbitals:
                                                         _lib.ptr(bond_ptr), _lib.ptr(E), _lib.ptr(gD), _lib.ptr(gS), _lib.stream_ptr()))
         return (gD, gS, E) if return_e else (gD, gS)
 
+    # ---- Löwdin analysis (csrc/orblowdin.hip) ------------------------------------------------------------------------------------------------------------------
+    def overlap_weights(self):
+        """After a STANDARD solve of ``S`` itself (``solve(S_packed)``: ``energies`` = the levels ``s`` of ``S``): ``a = sqrt(s)`` and ``1 / a`` float64 [M],
+        ``cond = s_max / s_min`` float64 [B] and ``info`` int32 [B] (``nq_orb_low_weights``) -> ``(w_half, w_inv_half, cond, info)`` on the device.  A molecule
+        the solver failed on, or with a level that is not finite or not positive, gets ``info = 1`` and NaN.  Nothing is read back."""
+        st, dev = self.state, self.state.buf.device
+        half, inv = self._scratch(st.M), self._scratch(st.M)
+        cond = self._scratch(st.B)
+        info = torch.empty(st.B, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().nq_orb_low_weights(_lib.ptr(st.buf), *st._dims, _lib.ptr(half), _lib.ptr(inv), _lib.ptr(cond), _lib.ptr(info), _lib.stream_ptr()))
+        return half, inv, cond, info
+
+    def overlap_functions(self):
+        """``S^(1/2)`` and ``S^(-1/2)`` of every molecule after a standard solve of ``S`` -> ``(half, inv_half, cond, info)``: the two packed float64 [P], exactly
+        symmetric, from ``overlap_weights`` and ONE ``nq_orb_wgram`` launch; ``info = 1``: NaN in that molecule's blocks."""
+        w_half, w_inv, cond, info = self.overlap_weights()
+        half, inv = self.weighted_gram(w_half, w_inv)
+        return half, inv, cond, info
+
+    def low_product(self, Msym: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+        """``Y = M X`` per molecule (``nq_orb_low_product``), packed float64 [P], not symmetric: ``Msym`` float32 or float64 [P] and ``X`` float64 [P] are
+        symmetric and only their lower triangles are read."""
+        st = self.state
+        Mp = _packed(Msym, st.P, "M")
+        out = self._scratch(st.P)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_low_product(_lib.ptr(st.buf), *st._dims, _lib.ptr(Mp), int(Mp.dtype == torch.float64), _lib.ptr(self._f64(X, st.P, "X")),
+                                                      _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def low_symprod(self, E: torch.Tensor, X: torch.Tensor, side: int, alpha: float = 1.0) -> torch.Tensor:
+        """``alpha sym(X E)`` (``side`` 0) or ``alpha sym(E X)`` (``side`` 1) per molecule (``nq_orb_low_symprod``), packed float64 [P], exactly symmetric: ``E``
+        any matrix, ``X`` symmetric, its lower triangle read."""
+        st = self.state
+        if side not in (0, 1):
+            raise ValueError(f"low_symprod: side must be 0 (sym(X E)) or 1 (sym(E X)), not {side!r}")
+        out = self._scratch(st.P)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_low_symprod(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(E, st.P, "E")), _lib.ptr(self._f64(X, st.P, "X")), int(side),
+                                                      float(alpha), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def low_symmetrize(self, G: torch.Tensor) -> torch.Tensor:
+        """``(G + G^T) / 2`` per molecule (``nq_orb_low_symmetrize``), packed float64 [P], exactly symmetric: one elementwise launch on the device."""
+        st = self.state
+        out = self._scratch(st.P)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_low_symmetrize(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(G, st.P, "G")), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def sym_congruence(self, X: torch.Tensor, Msym: torch.Tensor):
+        """``M^L = X M X`` for symmetric ``X`` (``S^(1/2)`` or ``S^(-1/2)``) and symmetric ``M`` (``D`` or ``H``, float32 or float64) -> ``(M_L, Y)``: ``Y = M X``
+        is kept for the reverse, ``M_L = sym(X Y)`` is exactly symmetric.  Two launches."""
+        Y = self.low_product(Msym, X)
+        return self.low_symprod(Y, X, 0), Y
+
+    def sym_congruence_backward(self, G: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, want_m: bool = True, want_x: bool = True, symmetric: bool = True):
+        """The reverse of ``sym_congruence`` for an upstream ``G = dL/dM^L`` -> ``(dL/dM or None, dL/dX or None)``: ``sym(X (G X))`` (two launches) and
+        ``Y G + G Y^T = 2 sym(Y G)`` (one), packed float64 [P], exactly symmetric.  ``symmetric=True`` (the default): ``G`` is symmetric and its lower triangle
+        is read; ``False``: any matrix, made symmetric first by one ``nq_orb_low_symmetrize`` launch."""
+        if not (want_m or want_x):
+            raise ValueError("sym_congruence_backward: neither gradient is asked for")
+        if not symmetric:
+            G = self.low_symmetrize(G)
+        gM = self.low_symprod(self.low_product(G, X), X, 0) if want_m else None
+        gX = self.low_symprod(Y, G, 1, 2.0) if want_x else None
+        return gM, gX
+
+    def low_mo(self, T: torch.Tensor, kind: int) -> torch.Tensor:
+        """``K o (U^T T)``, the diagonal included (``nq_orb_low_mo``), packed float64 [P]; ``kind`` 0: ``K_ij = 1 / (a_i + a_j)``, 1: ``-1 / (a_i a_j (a_i + a_j))``."""
+        st = self.state
+        if kind not in (0, 1):
+            raise ValueError(f"low_mo: kind must be 0 (S^(1/2)) or 1 (S^(-1/2)), not {kind!r}")
+        out = self._scratch(st.P)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_low_mo(_lib.ptr(st.buf), *st._dims, int(kind), _lib.ptr(self._f64(T, st.P, "T")), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def matfun_response(self, g: torch.Tensor, kind: int) -> torch.Tensor:
+        """``dL/dS`` of a loss with ``dL/dX = g`` (any matrix; its symmetric part counts) on ``X = S^(1/2)`` (``kind`` 0) or ``S^(-1/2)`` (``kind`` 1) after a
+        standard solve of ``S``: ``U [K o (U^T sym(g) U)] U^T`` in four launches over all orbital pairs -- ``nq_orb_resp_project``, ``nq_orb_low_mo``,
+        ``nq_orb_smear_back``, ``nq_orb_syr2k`` -> packed float64 [P], exactly symmetric.  No difference of levels is divided: equal levels of ``S`` give
+        finite gradients."""
+        layout = self.full_layout()
+        A = self.low_mo(self.resp_project(g, layout), kind)
+        return self.syr2k(self.smear_back(A, None)[0], None, layout)[0]
+
     def check(self) -> "BatchedOrbitals":
         st = self.state
         st.header()
@@ -608,6 +703,37 @@ class BatchedOrbitals:
             if bad.size:
                 raise RuntimeError(f"molecule {int(bad[0])}: no Fermi occupations (info 1): n_elec outside (0, 2m), kT not a positive finite number or "
                                    "non-finite orbital energies")
+        return self
+
+
+class LowdinBasis:
+    """The symmetric orthogonalisation of a batch, reusable for prediction and target of a step and, since ``S`` belongs to the conformer, across epochs:
+    ``orbitals`` (the ``BatchedOrbitals`` that holds the decomposition ``S = U diag(s) U^T``), ``half`` = ``S^(1/2)`` and ``inv_half`` = ``S^(-1/2)`` packed
+    float64 [P] on the device, ``s`` [M] (ascending inside each molecule), ``cond`` = ``s_max / s_min`` [B] and ``info`` int32 [B] (1: ``S`` is not positive
+    definite or its solve failed; NaN in that molecule's blocks).  ``LowdinBasis.of(S_packed, orb_ptr)`` builds one without gradients
+    (``nabladft_amd.orbital_loss.lowdin_basis`` is the differentiable call).  ``check()`` reads the status once (a host synchronisation) and raises
+    ``RuntimeError`` naming the molecule."""
+
+    def __init__(self, orbitals: "BatchedOrbitals", half: torch.Tensor, inv_half: torch.Tensor, cond: torch.Tensor, info: torch.Tensor):
+        self.orbitals, self.half, self.inv_half, self.cond, self.info = orbitals, half, inv_half, cond, info
+
+    s = property(lambda self: self.orbitals.energies)
+    orb_ptr = property(lambda self: self.orbitals.orb_ptr)
+
+    @classmethod
+    def of(cls, S_packed: torch.Tensor, plan_or_orb_ptr) -> "LowdinBasis":
+        _require_gpu(S_packed)
+        orb = BatchedOrbitals(plan_or_orb_ptr, S_packed.device).solve(S_packed)
+        return cls(orb, *orb.overlap_functions())
+
+    def check(self) -> "LowdinBasis":
+        self.orbitals.check()
+        bad = np.nonzero(self.info.cpu().numpy())[0]
+        if bad.size:
+            b = int(bad[0])
+            st = self.orbitals.state
+            lo = float(st.eps[int(st.orb_ptr_host[b])])
+            raise RuntimeError(f"molecule {b}: the overlap matrix is not positive definite (its lowest level is {lo:g}): no S^(1/2) (info 1)")
         return self
 
 
@@ -629,7 +755,7 @@ class BatchedPurification:
     with no stored iterates, no eigenpairs and no division.  ``iterations`` int32 [B] on the device.  ``check()`` reads the status once (a host
     synchronisation) and raises ``RuntimeError`` naming the molecule whose overlap was not positive definite (status 1) or whose purification did not
     converge (status 4: needs an open gap).  A failed molecule has NaN in its own blocks only.  ``populations`` / ``populations_backward`` / ``bond_orders`` /
-    ``bond_orders_backward`` are ``BatchedOrbitals``'.  No energies, no smearing, closed shells only."""
+    ``bond_orders_backward`` and the layout-only Löwdin launches (``low_product`` / ``low_symprod`` / ``sym_congruence``) are ``BatchedOrbitals``'.  No energies, no smearing, closed shells only."""
 
     def __init__(self, orb_ptr, device="cuda"):
         self.state = OrbitalState(orb_ptr, device)
@@ -652,6 +778,11 @@ class BatchedPurification:
     bond_reduce = BatchedOrbitals.bond_reduce
     bond_orders = BatchedOrbitals.bond_orders
     bond_orders_backward = BatchedOrbitals.bond_orders_backward
+    low_product = BatchedOrbitals.low_product                     # the layout-only launches of csrc/orblowdin.hip
+    low_symprod = BatchedOrbitals.low_symprod
+    low_symmetrize = BatchedOrbitals.low_symmetrize
+    sym_congruence = BatchedOrbitals.sym_congruence
+    sym_congruence_backward = BatchedOrbitals.sym_congruence_backward
 
     def _call(self, name, *args):
         st = self.state
@@ -846,4 +977,4 @@ def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
     return zz.to(device=atom_pop.device, dtype=torch.float64).reshape(-1) - atom_pop.to(torch.float64)
 
 
-__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "OrbitalState", "OrbitalErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
+__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "LowdinBasis", "OrbitalState", "OrbitalErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
