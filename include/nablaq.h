@@ -909,6 +909,16 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  *     pack_ptr, O = P); kind 0: K_ij = 1 / (a_i + a_j) (the reverse of S^(1/2)), kind 1: K_ij = -1 / (a_i a_j (a_i + a_j)) (of S^(-1/2)), a = sqrt(eps)
  *     recomputed from the state: no difference of eigenvalues is divided.  dL/dS = U A_out U^T is then nq_orb_smear_back (A_S = NULL) and nq_orb_syr2k over all
  *     orbitals.  A molecule nq_orb_low_weights would flag gets NaN.  Reads eps and coeff: a purification state is refused (header status -3).
+ * SCF residual (csrc/orbcomm.hip; entry points added, ABI 17 unchanged): the commutator R^L = [H^L, D^L] of the Löwdin Hamiltonian and density above, which is
+ * H D S - S D H in that basis and vanishes exactly when D is a stationary density of H; for an idempotent closed-shell D, sum R^L_ij^2 = 8 sum_{i occ, a virt} h_ia^2.
+ *   nq_orb_comm_product: out [P] = alpha (X Y - Y X) per molecule.  Y [P] symmetric, its lower triangle read.  x_anti 0: X symmetric (lower triangle read), out
+ *     ANTISYMMETRIC with a +0.0 diagonal; x_anti 1: X antisymmetric (STRICT lower triangle read, the mirrored element is the negated one, the stored diagonal
+ *     is ignored), out SYMMETRIC.  Lower-triangle 64 x 64 tiles, each entry computed once and stored twice: exactly (anti)symmetric.  For C = X Y - Y X with
+ *     symmetric X, Y and G_a = antisymmetrize(dL/dC): dL/dX = comm_product(G_a, 1, Y, +1), dL/dY = comm_product(G_a, 1, X, -1), both symmetric.
+ *   nq_orb_comm_antisymmetrize: out [P] = (G - G^T) / 2 per molecule, G [P] any matrix, lower-triangle tiles mirrored: exactly antisymmetric, +0.0 diagonal.
+ *   nq_orb_comm_norms: out_sumsq [B] = sum_ij R_ij^2 and out_maxabs [B] = max_ij |R_ij| (the DIIS error) over the whole m x m block of R [P], one workgroup per
+ *     molecule, fixed order; a NaN entry gives NaN in both.
+ *   All three read only the layout of the state (a solver state and a purification state serve alike) and refuse aliased outputs on the host.
  * All float64 on v_mfma_f64_16x16x4_f64 through the tile routine of the response kernels, the grids sized from (B, M, P), no atomics, fixed summation orders:
  * bitwise reproducible and independent of the rest of the batch.  status != 0: NaN in the molecule's own blocks of every output.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
@@ -969,6 +979,9 @@ int nq_orb_low_product(void* state, int32_t B, int32_t M, int64_t P, const void*
 int nq_orb_low_symprod(void* state, int32_t B, int32_t M, int64_t P, const double* E, const double* X, int32_t side, double alpha, double* out, void* stream);
 int nq_orb_low_symmetrize(void* state, int32_t B, int32_t M, int64_t P, const double* G, double* out, void* stream);
 int nq_orb_low_mo(void* state, int32_t B, int32_t M, int64_t P, int32_t kind, const double* T, double* A_out, void* stream);
+int nq_orb_comm_product(void* state, int32_t B, int32_t M, int64_t P, const double* X, int32_t x_anti, const double* Y, double alpha, double* out, void* stream);
+int nq_orb_comm_antisymmetrize(void* state, int32_t B, int32_t M, int64_t P, const double* G, double* out, void* stream);
+int nq_orb_comm_norms(void* state, int32_t B, int32_t M, int64_t P, const double* R, double* out_sumsq, double* out_maxabs, void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

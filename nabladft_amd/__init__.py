@@ -31,6 +31,9 @@ Public surface mirrors the reference plugin classes for this path:
   nabladft_amd.lowdin_basis / lowdin_populations / lowdin_bond_orders / lowdin_hamiltonian / QHNetLowdinLightning <-> the same slots: S^(1/2), S^(-1/2), Löwdin
                                     populations, Wiberg indices and the orthogonalised Hamiltonian with gradients that divide no difference of levels of S
                                     (orbitals.py, orbital_loss.py; no reference code, tested against numpy, scipy and torch autograd)
+  nabladft_amd.scf_residual / commutator / ScfResidualLoss / scf_target / QHNetCommutatorLightning / ScfResidualErrors <-> the same slots: the SCF residual
+                                    [H^L, D^L] of a predicted Hamiltonian against the target's density, a loss on the occupied subspace that solves nothing
+                                    for the prediction (orbitals.py, orbital_loss.py; no reference code, tested against numpy and torch autograd)
   nabladft_amd.spk.*            <-> the schnetpack classes config/model/{painn,schnet}.yaml instantiate (parity unpinned)
   nabladft_amd.read_energy_database / ArenaLoader <-> PyGNablaDFT.process + DataLoader collate (dataset/pyg_datasets.py:101-109)
 """
@@ -51,15 +54,17 @@ from .md import BatchedMD, PYGAseInterface  # noqa: F401
 from . import vibrations  # noqa: F401
 from .vibrations import BatchedVibrations  # noqa: F401
 from . import orbitals  # noqa: F401
-from .orbitals import BatchedOrbitals, BatchedPurification, FermiResult, OrbitalErrors, OrbitalState, electron_counts, mulliken_charges, occupied_counts, bond_layout, dense_bond_orders, LowdinBasis  # noqa: F401
+from .orbitals import BatchedOrbitals, BatchedPurification, FermiResult, OrbitalErrors, OrbitalState, electron_counts, mulliken_charges, occupied_counts, bond_layout, dense_bond_orders, LowdinBasis, ScfResidualErrors  # noqa: F401
 from .orbital_loss import (DensityMatrixLoss, MullikenChargeLoss, OrbitalEnergyLoss, QHNetDensityLightning, QHNetOrbitalLightning,  # noqa: F401
                            QHNetSmearedDensityLightning, SmearedSolution, density_matrix, orbital_energies, orbital_solution, populations,
                            smeared_density_matrix, smeared_solution, purified_density_matrix, QHNetPurifiedDensityLightning, bond_orders, BondOrderLoss,
                            QHNetBondOrderLightning, lowdin_basis, lowdin_density, lowdin_hamiltonian, lowdin_populations, lowdin_charges, lowdin_bond_orders,
-                           LowdinChargeLoss, QHNetLowdinLightning)
+                           LowdinChargeLoss, QHNetLowdinLightning, commutator, scf_residual, scf_residual_to_target, ScfResidualLoss, ScfTarget, scf_target,
+                           QHNetCommutatorLightning)
 from .data import ArenaLoader, ConformerArena, HamiltonianBatch, HamiltonianDatabase, HamiltonianDataset, hamiltonian_batch, read_energy_database  # noqa: F401
 
 __all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "DimeNetPlusPlusForceLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
            "read_energy_database", "HamiltonianDatabase", "HamiltonianDataset", "HamiltonianBatch", "hamiltonian_batch", "ASEBatchwiseLBFGS", "PyGBatchwiseCalculator", "BatchwiseOptimizeTask", "BatchedMD", "BatchedVibrations", "PYGAseInterface", "BatchedOrbitals", "OrbitalState", "OrbitalErrors", "orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "occupied_counts", "orbital_solution", "density_matrix", "populations", "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "FermiResult", "SmearedSolution", "smeared_solution", "smeared_density_matrix", "QHNetSmearedDensityLightning", "BatchedPurification", "purified_density_matrix", "QHNetPurifiedDensityLightning", "bond_orders", "BondOrderLoss", "QHNetBondOrderLightning",
            "bond_layout", "dense_bond_orders", "LowdinBasis", "lowdin_basis", "lowdin_density", "lowdin_hamiltonian", "lowdin_populations", "lowdin_charges",
-           "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning"]
+           "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning", "commutator", "scf_residual", "scf_residual_to_target", "ScfResidualLoss", "ScfTarget",
+           "scf_target", "QHNetCommutatorLightning", "ScfResidualErrors"]

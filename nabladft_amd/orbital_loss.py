@@ -74,6 +74,19 @@ the backward of ``torch.linalg.eigh`` returns non-finite values (csrc/orblowdin.
 at most 32 orbitals per atom for the bond table, no ``S^(1/2)`` without a decomposition.  Tested against a numpy restatement, ``scipy.linalg.sqrtm`` and
 ``torch`` autograd (tests/orbital_lowdin_ref.py).
 
+**SCF residual.**  ``scf_residual`` gives ``R^L = [H^L, D^L]`` of a Hamiltonian and a density in the Löwdin basis, the DIIS error vector
+``S^(-1/2) (H D S - S D H) S^(-1/2)``.  It vanishes exactly when ``D`` is a stationary density of ``H``; with ``D`` the target's idempotent closed-shell density and
+``H`` the prediction, ``sum_ij (R^L_ij)^2 = 8 sum_{i occ, a virt} h_ia^2`` with ``h_ia`` the occupied-virtual block of the predicted ``H^L`` in the TARGET's
+orbitals: the block that rotates the occupied subspace.  Proof: ``D^L = 2 Q`` with ``Q`` the projector on the occupied space, ``[H^L, Q] = (1 - Q) H^L Q -
+Q H^L (1 - Q)``, two blocks of equal norm ``sum h_ia^2`` that do not overlap, times ``2^2``.  No eigenpairs of the prediction, no ``1 / (eps_i - eps_a)``, no
+iteration: the residual is linear in ``H``, finite at closed and crossed gaps, and its reverse is the same kernel (csrc/orbcomm.hip): for ``C = X Y - Y X`` and
+``G_a`` the antisymmetric part of ``dL/dC``, ``dL/dX = [G_a, Y]`` and ``dL/dY = [X, G_a]``, both symmetric.  ``S`` and the target density belong to the
+conformer: ``scf_target`` builds an ``ScfTarget`` (one target solve, one ``LowdinBasis.of``) that can be cached across epochs, after which a step
+(``scf_residual_to_target``) is two congruence products and one commutator.  ``ScfResidualLoss`` and ``QHNetCommutatorLightning`` put the term beside the other
+targets; ``ScfResidualErrors`` reports its root mean square and maximum.  What it is NOT: it carries no gap weighting, it is not ``D_pred - D_target``, and it
+says nothing about the order of the levels inside the occupied space.  Tested against a numpy restatement and ``torch`` autograd
+(tests/orbital_commutator_ref.py).
+
 Limits (each raises, nothing degrades silently): what ``BatchedOrbitals`` has -- 1..1024 orbitals per molecule, closed shells or Fermi occupations (no spin
 polarisation), MI355X only, no CPU path.
 """
@@ -86,7 +99,7 @@ from torch import nn
 
 from .lightning import QHNetLightning
 from .orbitals import (BatchedOrbitals, BatchedPurification, LowdinBasis, Orthogonalizer, _orb_ptr_of, _require_gpu, bond_layout, check_occupied, dense_bond_orders,  # noqa: F401
-                       electron_counts, mulliken_charges, occupied_counts)
+                       ScfResidualErrors, electron_counts, mulliken_charges, occupied_counts)
 
 
 class _OrbitalEnergies(torch.autograd.Function):
@@ -664,6 +677,157 @@ class QHNetLowdinLightning(QHNetBondOrderLightning):
         return preds, targets, loss_args
 
 
+class _Commutator(torch.autograd.Function):
+    """Forward: ONE ``nq_orb_comm_product`` launch.  Backward for ``G = dL/dC``: ``G_a = (G - G^T) / 2`` (``nq_orb_comm_antisymmetrize``), then
+    ``dL/dX = [G_a, Y]`` and ``dL/dY = [X, G_a]``, the same kernel with an antisymmetric first operand; a half nobody asks for is skipped, nothing is launched
+    without ``G``."""
+
+    @staticmethod
+    def forward(ctx, orb, X, Y):
+        ctx.set_materialize_grads(False)
+        ctx.orb = orb
+        ctx.save_for_backward(X, Y)
+        return orb.commutator(X, Y).view(X.shape)
+
+    @staticmethod
+    def backward(ctx, G):
+        X, Y = ctx.saved_tensors
+        want_x, want_y = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if G is None or not (want_x or want_y):
+            return None, None, None
+        orb = ctx.orb
+        Ga = orb.antisymmetrize(G.to(torch.float64).reshape(-1).contiguous())
+        gX = orb.commutator(Ga, Y, True, 1.0).view(X.shape) if want_x else None
+        gY = orb.commutator(Ga, X, True, -1.0).view(Y.shape) if want_y else None
+        return None, gX, gY
+
+
+def commutator(X: torch.Tensor, Y: torch.Tensor, orbitals) -> torch.Tensor:
+    """``C = X Y - Y X`` per molecule for packed float64 [P] SYMMETRIC ``X`` and ``Y`` (their lower triangles are read) -> packed float64 [P], exactly
+    antisymmetric with a ``+0.0`` diagonal, differentiable with respect to both.  ``orbitals``: a ``BatchedOrbitals`` or ``BatchedPurification`` of the batch;
+    only its layout is read, nothing has to be solved.  The gradients are symmetric matrices (the convention of ``orbital_energies``):
+    ``dL/dX = [G_a, Y]``, ``dL/dY = [X, G_a]`` with ``G_a`` the antisymmetric part of the upstream gradient, whose symmetric part cannot reach a
+    commutator of symmetric matrices.  One launch forward, one plus one per gradient backward (csrc/orbcomm.hip), bitwise reproducible."""
+    if not isinstance(orbitals, (BatchedOrbitals, BatchedPurification)):
+        raise TypeError(f"commutator: orbitals must be a BatchedOrbitals or a BatchedPurification of the batch, not {type(orbitals).__name__}")
+    _require_gpu(X)
+    _require_gpu(Y)
+    P = orbitals.state.P
+    for name, t in (("X", X), ("Y", Y)):
+        if t.dtype != torch.float64:
+            raise TypeError(f"commutator: {name} must be float64, not {t.dtype}")
+        if t.numel() != P:
+            raise ValueError(f"commutator: {name} has {t.numel()} entries, the batch packs {P}")
+    return _Commutator.apply(orbitals, X, Y)
+
+
+def scf_residual(H: torch.Tensor, D: torch.Tensor, basis: LowdinBasis) -> torch.Tensor:
+    """The SCF residual (the DIIS error vector) of a Hamiltonian and a density in the Löwdin basis, ``R^L = [H^L, D^L]`` with ``H^L = S^(-1/2) H S^(-1/2)`` and
+    ``D^L = S^(1/2) D S^(1/2)``, which is ``S^(-1/2) (H D S - S D H) S^(-1/2)``: ``commutator(lowdin_hamiltonian(H, basis), lowdin_density(D, basis),
+    basis.orbitals)`` -> packed float64 [P], exactly antisymmetric.  ``H`` and ``D`` packed symmetric, float32 or float64 (their lower triangles are read);
+    ``basis`` a ``LowdinBasis``.  Differentiable with respect to ``H`` and ``D``, and to ``S`` when the basis came from ``lowdin_basis``.
+
+    ``R^L = 0`` holds exactly when ``D`` is a stationary density of ``H``.  For an idempotent closed-shell ``D`` (``D^L = 2 Q``, ``Q`` a projector) and any
+    ``H``: ``sum_ij (R^L_ij)^2 = 8 sum_{i occ, a virt} h_ia^2`` with ``h_ia`` the occupied-virtual block of ``H^L`` in the orbitals of ``D``: the block that
+    rotates the occupied subspace.  Nothing is solved, iterated or divided for ``H``: the residual is linear in ``H``, its gradient is one more commutator,
+    and it stays finite where the HOMO and LUMO of ``H`` coincide or cross, where ``orbital_solution`` does not.
+
+    Limits: ``S`` must be positive definite (``info = 1`` and NaN in that molecule's blocks otherwise); 1..1024 orbitals per molecule; the raw AO form
+    ``H D S - S D H`` without a basis is out of scope.  The residual measures the occupied-virtual coupling WITHOUT gap weighting: it is not
+    ``D_pred - D_target``, and it says nothing about the order of the levels inside the occupied space."""
+    HL = _congruence(H, "inv_half", basis, "scf_residual")
+    DL = _congruence(D, "half", basis, "scf_residual")
+    return commutator(HL, DL, basis.orbitals)
+
+
+def scf_residual_to_target(H: torch.Tensor, target) -> torch.Tensor:
+    """``scf_residual`` of ``H`` against a cached ``ScfTarget``: ``commutator(lowdin_hamiltonian(H, target.basis), target.DL, target.basis.orbitals)``: the
+    target's half is already in the Löwdin basis, so a step is two congruence products and one commutator; differentiable with respect to ``H``."""
+    basis, DL = target
+    return commutator(_congruence(H, "inv_half", basis, "scf_residual_to_target"), DL, basis.orbitals)
+
+
+class ScfResidualLoss(_PackedMeanLoss):
+    """``kind`` "mse" | "mae" of a packed SCF residual against zero: the mean over the ``m^2`` entries of each molecule, then the mean over the molecules.
+    ``R_target``: None (zero: the stationary density) or a packed residual.  ``charge`` is what ``QHNetCommutatorLightning`` counts the occupied orbitals of
+    the target with."""
+
+    def forward(self, R_pred: torch.Tensor, R_target: Optional[torch.Tensor], orb_ptr) -> torch.Tensor:
+        m = np.diff(_orb_ptr_of(orb_ptr))
+        return self._mean(R_pred, torch.zeros_like(R_pred) if R_target is None else R_target, m * m)
+
+
+ScfTarget = namedtuple("ScfTarget", "basis DL")
+ScfTarget.__doc__ = """What the residual term needs of a batch beside the prediction, detached, cacheable across epochs (both belong to the conformer): ``basis``, the
+``LowdinBasis`` of its overlap, and ``DL``, the target's Löwdin density ``S^(1/2) D S^(1/2)`` packed float64 [P]."""
+
+
+def scf_target(H_target: torch.Tensor, S: torch.Tensor, plan, n_occ) -> ScfTarget:
+    """``ScfTarget`` of a batch from ONE solve of the target Hamiltonian under ``S`` (its closed-shell density of ``n_occ`` [B] doubly occupied orbitals) and ONE
+    ``LowdinBasis.of(S, plan)``; no gradient flows through.  ``plan``: a plan or ``orb_ptr`` as for ``BatchedOrbitals``."""
+    _require_gpu(H_target)
+    _require_gpu(S)
+    op = _orb_ptr_of(plan)
+    basis = LowdinBasis.of(S.detach(), op)
+    D = BatchedOrbitals(op, H_target.device).solve(H_target.detach(), S.detach()).density(n_occ)
+    return ScfTarget(basis, basis.orbitals.sym_congruence(basis.half, D)[0])
+
+
+def _pack_f64(blocks, P: int, device, name: str) -> torch.Tensor:
+    flat = np.concatenate([np.asarray(b.detach().cpu() if isinstance(b, torch.Tensor) else b, dtype=np.float64).reshape(-1) for b in blocks])
+    if flat.size != P:
+        raise ValueError(f"batch.{name} holds {flat.size} elements, the batch packs {P}")
+    return torch.from_numpy(flat).to(device)
+
+
+class QHNetCommutatorLightning(QHNetLowdinLightning):
+    """``QHNetLowdinLightning`` with a term on the SCF residual: ``losses`` / ``loss_coefs`` take ``"scf_residual"`` (an ``ScfResidualLoss``) beside the parent's
+    keys: ``scf_residual`` of the packed prediction against the target's Löwdin density, against zero.  When that key is the only active orbital key the step
+    solves NOTHING for the prediction.  If the batch carries ``batch.lowdin_inv_half``, ``batch.lowdin_half`` and ``batch.target_density_lowdin`` (lists of
+    per-molecule float64 matrices like ``batch.hamiltonian``: what ``scf_target`` computes, cached with the conformer), they are packed and used, and the step
+    launches no solve at all; otherwise it computes ``scf_target`` from ``batch.hamiltonian`` and ``batch.overlap`` (required): one target solve and one
+    decomposition of ``S``, both detached.  Beside other active keys the parent's step runs unchanged and the residual term is added to it.  With the
+    coefficient at 0 (or without the key) the step is the parent's."""
+
+    SCF = "scf_residual"
+    KEYS = QHNetLowdinLightning.KEYS + (SCF,)
+    CACHED = ("lowdin_inv_half", "lowdin_half", "target_density_lowdin")
+    _scf_hidden = False
+
+    def _active(self):
+        active = super()._active()
+        return [k for k in active if k != self.SCF] if self._scf_hidden else active
+
+    def _evaluate(self, batch):
+        if self.SCF not in self._active():
+            return super()._evaluate(batch)
+        if not self._packed():
+            raise ValueError("QHNetCommutatorLightning needs packed losses (HamiltonianLoss, ScfResidualLoss and the parent's)")
+        self._scf_hidden = True                                    # the parent's step sees its own keys only (none: QHNetLightning's step, nothing solved)
+        try:
+            preds, targets, loss_args = super()._evaluate(batch)
+        finally:
+            self._scf_hidden = False
+        plan, asm = self.net.last_plan, self.net._asm
+        op = _orb_ptr_of(plan)
+        Hp = preds["hamiltonian"]
+        cached = [getattr(batch, n, None) for n in self.CACHED]
+        if all(c is not None for c in cached):
+            P = Hp.numel()
+            inv_half, half, DL = (_pack_f64(c, P, Hp.device, n) for c, n in zip(cached, self.CACHED))
+            target = ScfTarget(LowdinBasis(BatchedOrbitals(op, Hp.device), half, inv_half, None, None), DL)
+        else:
+            overlap = getattr(batch, "overlap", None)
+            if overlap is None:
+                raise ValueError("QHNetCommutatorLightning: the residual term needs batch.overlap, or the cached batch.lowdin_inv_half / lowdin_half / "
+                                 "target_density_lowdin")
+            charge = getattr(self.hparams.losses[self.SCF], "charge", 0)
+            target = scf_target(targets["hamiltonian"], asm.pack_targets(plan, overlap), op, occupied_counts(batch.z, batch.ptr, charge, op))
+        k = self.SCF
+        preds[k], targets[k], preds[k + "_args"] = scf_residual_to_target(Hp, target), None, (op,)
+        return preds, targets, loss_args
+
+
 SmearedSolution = namedtuple("SmearedSolution", "eps D occ mu entropy")
 SmearedSolution.__doc__ = """What ``smeared_solution`` returns, float64 on the device: ``eps`` [M], ``D`` [P], ``occ`` = F [M], ``mu`` [B], ``entropy`` [B] (units of k_B)."""
 
@@ -866,4 +1030,5 @@ __all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mu
            "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "SmearedSolution", "smeared_solution", "smeared_density_matrix",
            "QHNetSmearedDensityLightning", "purified_density_matrix", "QHNetPurifiedDensityLightning", "bond_orders", "BondOrderLoss", "QHNetBondOrderLightning",
            "bond_layout", "dense_bond_orders", "LowdinBasis", "lowdin_basis", "lowdin_density", "lowdin_hamiltonian", "lowdin_populations", "lowdin_charges",
-           "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning"]
+           "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning", "commutator", "scf_residual", "scf_residual_to_target", "ScfResidualLoss", "ScfTarget",
+           "scf_target", "QHNetCommutatorLightning", "ScfResidualErrors"]

@@ -30,6 +30,11 @@ reverse down to ``S``, evaluated without dividing by a difference of levels of `
 ``lowdin_density`` / ``lowdin_populations`` / ``lowdin_bond_orders`` / ``lowdin_hamiltonian`` are the differentiable calls).  ``S`` must be positive definite
 (``info = 1`` and NaN otherwise); there is no ``S^(1/2)`` without a decomposition.
 
+**SCF residual.**  ``commutator(X, Y, x_anti, alpha)`` gives ``alpha (X Y - Y X)`` of packed symmetric matrices (``x_anti``: an antisymmetric ``X``, the form of
+its own reverse), ``antisymmetrize(G)`` the antisymmetric part of an upstream gradient, ``commutator_norms(R)`` the sum of squares and the largest magnitude (the
+DIIS error) per molecule (csrc/orbcomm.hip); they read the layout of the state alone, nothing has to be solved.  ``nabladft_amd.orbital_loss.commutator`` /
+``scf_residual`` are the differentiable calls, ``ScfResidualErrors`` accumulates the figures of a test loop.
+
 **Smearing.**  ``fermi(n_elec, kT)`` gives Fermi-Dirac occupations ``F_k = 2 / (1 + exp((eps_k - mu) / kT))`` with the chemical potential fixed by the electron
 count (``electron_counts``: odd counts and fractions are fine), ``smeared_density(occ)`` the density ``sum_k F_k c_k c_k^T`` and ``smeared_response`` its
 gradient chain over all orbital pairs, evaluated without dividing by a difference of orbital energies (csrc/orbsmear.hip;
@@ -689,6 +694,37 @@ class BatchedOrbitals:
         A = self.low_mo(self.resp_project(g, layout), kind)
         return self.syr2k(self.smear_back(A, None)[0], None, layout)[0]
 
+    # ---- SCF residual (csrc/orbcomm.hip) -------------------------------------------------------------------------------------------------------------------------
+    def commutator(self, X: torch.Tensor, Y: torch.Tensor, x_anti: bool = False, alpha: float = 1.0) -> torch.Tensor:
+        """``alpha (X Y - Y X)`` per molecule (``nq_orb_comm_product``), packed float64 [P].  ``Y`` is symmetric, its lower triangle is read.  ``x_anti=False``:
+        ``X`` symmetric (lower triangle read), the result exactly antisymmetric with a ``+0.0`` diagonal; ``x_anti=True``: ``X`` antisymmetric (strict lower
+        triangle read, the mirrored element is the negated one, the stored diagonal is ignored), the result exactly symmetric.  Only the layout of the state
+        is read: no solve is needed."""
+        st = self.state
+        out = self._scratch(st.P)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_comm_product(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(X, st.P, "X")), int(bool(x_anti)),
+                                                       _lib.ptr(self._f64(Y, st.P, "Y")), float(alpha), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def antisymmetrize(self, G: torch.Tensor) -> torch.Tensor:
+        """``(G - G^T) / 2`` per molecule (``nq_orb_comm_antisymmetrize``), packed float64 [P], exactly antisymmetric with a ``+0.0`` diagonal."""
+        st = self.state
+        out = self._scratch(st.P)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_comm_antisymmetrize(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(G, st.P, "G")), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def commutator_norms(self, R: torch.Tensor):
+        """``(sum_ij R_ij^2, max_ij |R_ij|)`` per molecule over the whole block (``nq_orb_comm_norms``), float64 [B] each on the device; the maximum of an SCF
+        residual is the DIIS error.  A molecule with ``status != 0`` or a NaN entry gets NaN in both."""
+        st = self.state
+        sumsq, maxabs = self._scratch(st.B), self._scratch(st.B)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_comm_norms(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(R, st.P, "R")), _lib.ptr(sumsq), _lib.ptr(maxabs),
+                                                     _lib.stream_ptr()))
+        return sumsq, maxabs
+
     def check(self) -> "BatchedOrbitals":
         st = self.state
         st.header()
@@ -783,6 +819,9 @@ class BatchedPurification:
     low_symmetrize = BatchedOrbitals.low_symmetrize
     sym_congruence = BatchedOrbitals.sym_congruence
     sym_congruence_backward = BatchedOrbitals.sym_congruence_backward
+    commutator = BatchedOrbitals.commutator                       # the layout-only launches of csrc/orbcomm.hip
+    antisymmetrize = BatchedOrbitals.antisymmetrize
+    commutator_norms = BatchedOrbitals.commutator_norms
 
     def _call(self, name, *args):
         st = self.state
@@ -969,6 +1008,47 @@ class OrbitalErrors:
         return dict(zip(FIGURES, mean))
 
 
+class ScfResidualErrors:
+    """The SCF residual of a test loop, accumulated over batches: ``update(pred_packed, target)`` with ``target`` an ``ScfTarget`` (``(basis, DL)``: the
+    ``LowdinBasis`` of the conformers and the target's Löwdin density, ``nabladft_amd.orbital_loss.scf_target``) forms ``R^L = [S^(-1/2) H S^(-1/2), D^L]`` of
+    the predicted ``H`` -- three product launches, nothing is solved -- and adds the per-molecule root mean square ``sqrt(sum R_ij^2 / m^2)`` and maximum
+    ``max |R_ij|`` (the DIIS error) from ``commutator_norms`` to running sums on the device; nothing is read back.  A molecule whose figures are not finite
+    (an overlap that is not positive definite, a failed decomposition, NaN in the prediction) is counted and left out of the means.  ``compute()`` -> dict
+    ``scf_residual_rms``, ``scf_residual_max`` (means over the molecules kept), ``molecules`` and ``failed`` (one host read); it raises ``RuntimeError`` before
+    any ``update()``.  No gradient flows through."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self._sum = None          # float64 [4] on the device: sum of rms, sum of max, molecules kept, molecules left out
+
+    def update(self, pred_packed: torch.Tensor, target):
+        basis, DL = target
+        if not isinstance(basis, LowdinBasis):
+            raise TypeError(f"ScfResidualErrors.update: target must be an ScfTarget (basis, DL), its basis a LowdinBasis, not {type(basis).__name__}")
+        _require_gpu(pred_packed)
+        orb = basis.orbitals
+        P = orb.state.P
+        HL = orb.sym_congruence(basis.inv_half.detach(), _packed(pred_packed, P, "pred_packed"))[0]
+        sumsq, top = orb.commutator_norms(orb.commutator(HL, DL.detach()))
+        m = torch.from_numpy(orb.state.m.astype(np.float64)).to(sumsq.device)
+        rms = torch.sqrt(sumsq) / m
+        ok = torch.isfinite(rms) & torch.isfinite(top)
+        zero = torch.zeros_like(rms)
+        okf = ok.to(torch.float64)
+        add = torch.stack([torch.where(ok, rms, zero).sum(), torch.where(ok, top, zero).sum(), okf.sum(), (1.0 - okf).sum()])
+        self._sum = add if self._sum is None else self._sum + add
+        return self
+
+    def compute(self) -> dict:
+        if self._sum is None:
+            raise RuntimeError("ScfResidualErrors.compute() before any update()")
+        s_rms, s_max, kept, failed = self._sum.cpu().tolist()
+        nan = float("nan")
+        return {"scf_residual_rms": s_rms / kept if kept else nan, "scf_residual_max": s_max / kept if kept else nan, "molecules": int(kept), "failed": int(failed)}
+
+
 def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
     """Mulliken charges ``q_A = Z_A - pop_A`` (float64 [N], on the device of ``atom_pop``) from the populations of ``BatchedOrbitals.populations``."""
     zz = z if isinstance(z, torch.Tensor) else torch.as_tensor(np.asarray(z))
@@ -977,4 +1057,4 @@ def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
     return zz.to(device=atom_pop.device, dtype=torch.float64).reshape(-1) - atom_pop.to(torch.float64)
 
 
-__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "LowdinBasis", "OrbitalState", "OrbitalErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
+__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "LowdinBasis", "OrbitalState", "OrbitalErrors", "ScfResidualErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
