@@ -921,6 +921,26 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  *   All three read only the layout of the state (a solver state and a purification state serve alike) and refuse aliased outputs on the host.
  * All float64 on v_mfma_f64_16x16x4_f64 through the tile routine of the response kernels, the grids sized from (B, M, P), no atomics, fixed summation orders:
  * bitwise reproducible and independent of the rest of the batch.  status != 0: NaN in the molecule's own blocks of every output.
+ * Square roots without a decomposition (csrc/orbsqrt.hip; entry points added, ABI 17 unchanged): A = S^(1/2) and A^- = S^(-1/2) by the coupled Newton-Schulz
+ * iteration.  c = the largest absolute row sum of S (>= s_max), Y_0 = S / c, Z_0 = I; iteration k: T = (3 I - sym(Z Y)) / 2 (lower-triangle tiles of Z Y
+ * mirrored), delta_k = m - tr(Z Y); stop with (Y, Z) = (Y_k, Z_k) when delta_k = 0, or when k >= 1 and |delta_k| < 1e-9 m and |delta_k| >= |delta_k-1|; else
+ * Y' = Y T, Z' = T Z as full general products (log entry 1; the stopping iteration logs 3).  Y and Z are NOT symmetrised between iterations: doing so makes
+ * the iteration diverge once it has reached its rounding floor.  A = sqrt(c) Y, A^- = Z / sqrt(c), the lower triangles mirrored.  About 18 iterations at
+ * kappa_2(S) = 1e4, 32 at 1e8, which is the limit the stopping rule is meant for; an indefinite S never stops.
+ * Where things live: the state of nq_orb_init supplies the layout and the words status (0, 1: c not finite or <= 0, 4: not stopped after max_iter
+ * iterations, info = 1), info and iters (the updates applied); its P-sized parts are neither read nor written, so the state is not marked and any state of the
+ * batch serves.  Caller-owned, float64 on the device: Y, Z, T, Y2, Z2 [P each; iteration k reads the pair k & 1 -- (Y, Z) is pair 0 -- and writes the other, so
+ * an output never aliases an operand of its launch], ctl [B][24 + max_iter] = {c, sqrt(c), tr(Z Y) of the last iteration, 0 x 5, 16 slots (partial tr(Z Y) of
+ * the diagonal 64 x 64 tiles), delta_k of every iteration} and log int32 [B][max_iter].
+ *   nq_orb_sqrt_init: S (lower triangle, float32 or float64; the upper triangle is not read) -> c, Y_0, Z_0 into (Y, Z); clears ctl and log, sets status.
+ *   nq_orb_sqrt_step: exactly one iteration, number k (0-based, in order: iteration k of a molecule runs only if k = 0 or log[k - 1] is an update), two
+ *     launches; nq_orb_sqrt_run: iterations 0 .. max_iter - 1 (1..10000) enqueued with no host round trip; the workgroups of a finished or failed molecule
+ *     exit at once.
+ *   nq_orb_sqrt_finish: half [P] = sqrt(c) Y and inv_half [P] = Z / sqrt(c) from the pair the last update wrote, lower triangles mirrored: exactly symmetric.
+ *     A molecule with status 1, or whose last log entry is an update (status 4, info 1 from here on), gets NaN in its own blocks of both; the others are
+ *     untouched by it.
+ *   NULL or aliased arrays, max_iter or k out of range and impossible dimensions are refused on the host and touch nothing.  float64 on
+ *   v_mfma_f64_16x16x4_f64, no atomics, fixed summation orders: bitwise reproducible and independent of the rest of the batch; m = 1 .. 1024.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
 size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P);
 int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host);
@@ -982,6 +1002,14 @@ int nq_orb_low_mo(void* state, int32_t B, int32_t M, int64_t P, int32_t kind, co
 int nq_orb_comm_product(void* state, int32_t B, int32_t M, int64_t P, const double* X, int32_t x_anti, const double* Y, double alpha, double* out, void* stream);
 int nq_orb_comm_antisymmetrize(void* state, int32_t B, int32_t M, int64_t P, const double* G, double* out, void* stream);
 int nq_orb_comm_norms(void* state, int32_t B, int32_t M, int64_t P, const double* R, double* out_sumsq, double* out_maxabs, void* stream);
+int nq_orb_sqrt_init(void* state, int32_t B, int32_t M, int64_t P, const void* S, int32_t s_f64, int32_t max_iter, double* Y, double* Z, double* ctl, int32_t* log,
+                     void* stream);
+int nq_orb_sqrt_step(void* state, int32_t B, int32_t M, int64_t P, int32_t k, int32_t max_iter, double* Y, double* Z, double* T, double* Y2, double* Z2, double* ctl,
+                     int32_t* log, void* stream);
+int nq_orb_sqrt_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, double* Y, double* Z, double* T, double* Y2, double* Z2, double* ctl, int32_t* log,
+                    void* stream);
+int nq_orb_sqrt_finish(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, const double* Y, const double* Z, const double* Y2, const double* Z2,
+                       const double* ctl, const int32_t* log, double* half, double* inv_half, void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

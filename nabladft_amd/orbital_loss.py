@@ -81,7 +81,8 @@ orbitals: the block that rotates the occupied subspace.  Proof: ``D^L = 2 Q`` wi
 Q H^L (1 - Q)``, two blocks of equal norm ``sum h_ia^2`` that do not overlap, times ``2^2``.  No eigenpairs of the prediction, no ``1 / (eps_i - eps_a)``, no
 iteration: the residual is linear in ``H``, finite at closed and crossed gaps, and its reverse is the same kernel (csrc/orbcomm.hip): for ``C = X Y - Y X`` and
 ``G_a`` the antisymmetric part of ``dL/dC``, ``dL/dX = [G_a, Y]`` and ``dL/dY = [X, G_a]``, both symmetric.  ``S`` and the target density belong to the
-conformer: ``scf_target`` builds an ``ScfTarget`` (one target solve, one ``LowdinBasis.of``) that can be cached across epochs, after which a step
+conformer: ``scf_target`` builds an ``ScfTarget`` (one target solve and one ``LowdinBasis.of``, or with ``scf_target_iterative`` Newton-Schulz square roots and an
+SP2 purification of the Löwdin Hamiltonian: no solve at all) that can be cached across epochs (``scf_target_blocks`` gives the fields to store), after which a step
 (``scf_residual_to_target``) is two congruence products and one commutator.  ``ScfResidualLoss`` and ``QHNetCommutatorLightning`` put the term beside the other
 targets; ``ScfResidualErrors`` reports its root mean square and maximum.  What it is NOT: it carries no gap weighting, it is not ``D_pred - D_target``, and it
 says nothing about the order of the levels inside the occupied space.  Tested against a numpy restatement and ``torch`` autograd
@@ -98,7 +99,7 @@ import torch
 from torch import nn
 
 from .lightning import QHNetLightning
-from .orbitals import (BatchedOrbitals, BatchedPurification, LowdinBasis, Orthogonalizer, _orb_ptr_of, _require_gpu, bond_layout, check_occupied, dense_bond_orders,  # noqa: F401
+from .orbitals import (BatchedMatrixRoot, BatchedOrbitals, BatchedPurification, LowdinBasis, Orthogonalizer, _orb_ptr_of, _require_gpu, bond_layout, check_occupied, dense_bond_orders,  # noqa: F401
                        ScfResidualErrors, electron_counts, mulliken_charges, occupied_counts)
 
 
@@ -569,7 +570,8 @@ def lowdin_basis(S_packed: torch.Tensor, plan_or_orb_ptr) -> LowdinBasis:
     is the Daleckii-Krein form of the module text, which divides no difference of levels, and launches nothing for an output without an upstream gradient.
     ``plan_or_orb_ptr`` as for ``BatchedOrbitals``.  One basis serves prediction and target of a step; ``S`` belongs to the conformer, so it can be cached
     across epochs (``LowdinBasis.of`` builds one without gradients).  ``S`` must be positive definite: otherwise ``info = 1`` and NaN in that molecule's
-    blocks, which ``check()`` reports.  There is no ``S^(1/2)`` without a decomposition."""
+    blocks, which ``check()`` reports.  The gradient of ``S`` needs the decomposition; without one, and without that gradient, ``LowdinBasis.of(...,
+    method="newton_schulz")`` gives the two functions from matrix products alone."""
     _require_gpu(S_packed)
     orb = BatchedOrbitals(plan_or_orb_ptr, S_packed.device)
     return LowdinBasis(orb, *_LowdinBasis.apply(orb, S_packed))
@@ -750,27 +752,76 @@ def scf_residual_to_target(H: torch.Tensor, target) -> torch.Tensor:
 class ScfResidualLoss(_PackedMeanLoss):
     """``kind`` "mse" | "mae" of a packed SCF residual against zero: the mean over the ``m^2`` entries of each molecule, then the mean over the molecules.
     ``R_target``: None (zero: the stationary density) or a packed residual.  ``charge`` is what ``QHNetCommutatorLightning`` counts the occupied orbitals of
-    the target with."""
+    the target with, ``target_method`` ("solve" | "iterative") whether it builds an uncached target by ``scf_target`` or ``scf_target_iterative``."""
+
+    def __init__(self, kind: str = "mae", charge=0, target_method: str = "solve"):
+        super().__init__(kind, charge)
+        if target_method not in ("solve", "iterative"):
+            raise ValueError(f"target_method must be 'solve' or 'iterative', not {target_method!r}")
+        self.target_method = target_method
 
     def forward(self, R_pred: torch.Tensor, R_target: Optional[torch.Tensor], orb_ptr) -> torch.Tensor:
         m = np.diff(_orb_ptr_of(orb_ptr))
         return self._mean(R_pred, torch.zeros_like(R_pred) if R_target is None else R_target, m * m)
 
 
-ScfTarget = namedtuple("ScfTarget", "basis DL")
-ScfTarget.__doc__ = """What the residual term needs of a batch beside the prediction, detached, cacheable across epochs (both belong to the conformer): ``basis``, the
-``LowdinBasis`` of its overlap, and ``DL``, the target's Löwdin density ``S^(1/2) D S^(1/2)`` packed float64 [P]."""
+class ScfTarget(namedtuple("ScfTarget", "basis DL")):
+    """What the residual term needs of a batch beside the prediction, detached, cacheable across epochs (both belong to the conformer): ``basis``, the
+    ``LowdinBasis`` of its overlap, and ``DL``, the target's Löwdin density ``S^(1/2) D S^(1/2)`` packed float64 [P].  ``purification``: the
+    ``BatchedPurification`` behind ``DL`` for ``scf_target_iterative``, else None.  ``check()`` reads the status words once (a host synchronisation)
+    and raises ``RuntimeError`` naming the molecule whose overlap is not positive definite or whose target has no gap."""
+
+    purification = None
+
+    def check(self) -> "ScfTarget":
+        if self.basis.info is not None or self.basis.root is not None:
+            self.basis.check()
+        if self.purification is not None:
+            self.purification.check()
+        return self
 
 
 def scf_target(H_target: torch.Tensor, S: torch.Tensor, plan, n_occ) -> ScfTarget:
     """``ScfTarget`` of a batch from ONE solve of the target Hamiltonian under ``S`` (its closed-shell density of ``n_occ`` [B] doubly occupied orbitals) and ONE
-    ``LowdinBasis.of(S, plan)``; no gradient flows through.  ``plan``: a plan or ``orb_ptr`` as for ``BatchedOrbitals``."""
+    ``LowdinBasis.of(S, plan)``, both latency-bound; no gradient flows through.  ``plan``: a plan or ``orb_ptr`` as for ``BatchedOrbitals``.
+    ``scf_target_iterative`` builds the same target without any solve."""
     _require_gpu(H_target)
     _require_gpu(S)
     op = _orb_ptr_of(plan)
     basis = LowdinBasis.of(S.detach(), op)
     D = BatchedOrbitals(op, H_target.device).solve(H_target.detach(), S.detach()).density(n_occ)
     return ScfTarget(basis, basis.orbitals.sym_congruence(basis.half, D)[0])
+
+
+def scf_target_iterative(H_target: torch.Tensor, S: torch.Tensor, plan, n_occ, max_iter: int = 100) -> ScfTarget:
+    """The ``ScfTarget`` of ``scf_target`` with NOTHING solved; no gradient flows through.  ``S^(1/2)`` and ``S^(-1/2)`` by Newton-Schulz
+    (``LowdinBasis.of(..., method="newton_schulz", max_iter=max_iter)``), ``H^L = S^(-1/2) H S^(-1/2)`` by one congruence, the projector ``X`` on its ``n_occ``
+    lowest levels by SP2 purification of that STANDARD problem (``BatchedPurification``, at most ``max_iter`` iterations), ``D^L = 2 X`` with no back-transform.
+    A target without a gap (status 4) or an overlap that is not positive definite gives NaN in that molecule's blocks only and is named by
+    ``ScfTarget.check()``."""
+    _require_gpu(H_target)
+    _require_gpu(S)
+    op = _orb_ptr_of(plan)
+    no = check_occupied(n_occ, op)
+    basis = LowdinBasis.of(S.detach(), op, method="newton_schulz", max_iter=max_iter)
+    HL = basis.orbitals.sym_congruence(basis.inv_half, H_target.detach())[0]
+    pur = BatchedPurification(op, H_target.device).purify(HL, no, max_iter)
+    target = ScfTarget(basis, pur.density())
+    target.purification = pur
+    return target
+
+
+def scf_target_blocks(target) -> dict:
+    """The three fields ``QHNetCommutatorLightning`` reads from a batch (its ``CACHED``), from an ``ScfTarget``: ``{"lowdin_inv_half", "lowdin_half",
+    "target_density_lowdin"}``, each a list of per-molecule float64 ``[m, m]`` CPU tensors, for a data pipeline to store with the conformer.  One device -> host
+    copy per field."""
+    basis, DL = target
+    pp, m = basis.orbitals.pack_ptr, np.diff(basis.orbitals.orb_ptr)
+    out = {}
+    for name, t in (("lowdin_inv_half", basis.inv_half), ("lowdin_half", basis.half), ("target_density_lowdin", DL)):
+        flat = t.detach().to(torch.float64).reshape(-1).cpu()
+        out[name] = [flat[int(pp[b]):int(pp[b + 1])].reshape(int(m[b]), int(m[b])).clone() for b in range(m.shape[0])]
+    return out
 
 
 def _pack_f64(blocks, P: int, device, name: str) -> torch.Tensor:
@@ -786,7 +837,7 @@ class QHNetCommutatorLightning(QHNetLowdinLightning):
     solves NOTHING for the prediction.  If the batch carries ``batch.lowdin_inv_half``, ``batch.lowdin_half`` and ``batch.target_density_lowdin`` (lists of
     per-molecule float64 matrices like ``batch.hamiltonian``: what ``scf_target`` computes, cached with the conformer), they are packed and used, and the step
     launches no solve at all; otherwise it computes ``scf_target`` from ``batch.hamiltonian`` and ``batch.overlap`` (required): one target solve and one
-    decomposition of ``S``, both detached.  Beside other active keys the parent's step runs unchanged and the residual term is added to it.  With the
+    decomposition of ``S``, both detached, or, with ``ScfResidualLoss(target_method="iterative")``, matrix products alone.  Beside other active keys the parent's step runs unchanged and the residual term is added to it.  With the
     coefficient at 0 (or without the key) the step is the parent's."""
 
     SCF = "scf_residual"
@@ -821,8 +872,9 @@ class QHNetCommutatorLightning(QHNetLowdinLightning):
             if overlap is None:
                 raise ValueError("QHNetCommutatorLightning: the residual term needs batch.overlap, or the cached batch.lowdin_inv_half / lowdin_half / "
                                  "target_density_lowdin")
-            charge = getattr(self.hparams.losses[self.SCF], "charge", 0)
-            target = scf_target(targets["hamiltonian"], asm.pack_targets(plan, overlap), op, occupied_counts(batch.z, batch.ptr, charge, op))
+            loss = self.hparams.losses[self.SCF]
+            build = scf_target_iterative if getattr(loss, "target_method", "solve") == "iterative" else scf_target
+            target = build(targets["hamiltonian"], asm.pack_targets(plan, overlap), op, occupied_counts(batch.z, batch.ptr, getattr(loss, "charge", 0), op))
         k = self.SCF
         preds[k], targets[k], preds[k + "_args"] = scf_residual_to_target(Hp, target), None, (op,)
         return preds, targets, loss_args
@@ -1031,4 +1083,4 @@ __all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mu
            "QHNetSmearedDensityLightning", "purified_density_matrix", "QHNetPurifiedDensityLightning", "bond_orders", "BondOrderLoss", "QHNetBondOrderLightning",
            "bond_layout", "dense_bond_orders", "LowdinBasis", "lowdin_basis", "lowdin_density", "lowdin_hamiltonian", "lowdin_populations", "lowdin_charges",
            "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning", "commutator", "scf_residual", "scf_residual_to_target", "ScfResidualLoss", "ScfTarget",
-           "scf_target", "QHNetCommutatorLightning", "ScfResidualErrors"]
+           "scf_target", "scf_target_iterative", "scf_target_blocks", "BatchedMatrixRoot", "QHNetCommutatorLightning", "ScfResidualErrors"]

@@ -28,7 +28,8 @@ decomposition; one per batch serves prediction and target, and since ``S`` belon
 the Löwdin density ``S^(1/2) D S^(1/2)`` or the orthogonalised Hamiltonian ``S^(-1/2) H S^(-1/2)``, ``sym_congruence_backward`` / ``matfun_response`` their
 reverse down to ``S``, evaluated without dividing by a difference of levels of ``S`` (csrc/orblowdin.hip; ``nabladft_amd.orbital_loss.lowdin_basis`` /
 ``lowdin_density`` / ``lowdin_populations`` / ``lowdin_bond_orders`` / ``lowdin_hamiltonian`` are the differentiable calls).  ``S`` must be positive definite
-(``info = 1`` and NaN otherwise); there is no ``S^(1/2)`` without a decomposition.
+(``info = 1`` and NaN otherwise).  ``BatchedMatrixRoot`` / ``LowdinBasis.of(..., method="newton_schulz")`` give the two functions WITHOUT a decomposition, by the coupled
+Newton-Schulz iteration on the matrix cores (csrc/orbsqrt.hip): no levels, no ``cond``, no gradient of ``S``; meant for ``kappa_2(S) <= 1e8``.
 
 **SCF residual.**  ``commutator(X, Y, x_anti, alpha)`` gives ``alpha (X Y - Y X)`` of packed symmetric matrices (``x_anti``: an antisymmetric ``X``, the form of
 its own reverse), ``antisymmetrize(G)`` the antisymmetric part of an upstream gradient, ``commutator_norms(R)`` the sum of squares and the largest magnitude (the
@@ -753,16 +754,37 @@ class LowdinBasis:
     def __init__(self, orbitals: "BatchedOrbitals", half: torch.Tensor, inv_half: torch.Tensor, cond: torch.Tensor, info: torch.Tensor):
         self.orbitals, self.half, self.inv_half, self.cond, self.info = orbitals, half, inv_half, cond, info
 
-    s = property(lambda self: self.orbitals.energies)
     orb_ptr = property(lambda self: self.orbitals.orb_ptr)
+    root = None                   # the BatchedMatrixRoot behind a basis of method "newton_schulz"
+
+    @property
+    def s(self):
+        if self.root is not None:
+            raise RuntimeError("LowdinBasis.s: a basis of method \"newton_schulz\" has no levels of S: there are none without a decomposition (use method=\"eigh\")")
+        return self.orbitals.energies
 
     @classmethod
-    def of(cls, S_packed: torch.Tensor, plan_or_orb_ptr) -> "LowdinBasis":
+    def of(cls, S_packed: torch.Tensor, plan_or_orb_ptr, method: str = "eigh", max_iter: int = 100) -> "LowdinBasis":
+        """``method="eigh"``: one standard solve of ``S`` (latency-bound) and its functions.  ``method="newton_schulz"``: ``BatchedMatrixRoot`` -- matrix
+        products alone, nothing is solved; ``orbitals`` is then a layout-only ``BatchedOrbitals`` (it serves the congruence and commutator launches), ``cond``
+        is None, ``s`` raises, ``info`` is the iteration's status (1: the row sums of ``S`` are unusable, 4: not converged in ``max_iter`` iterations: ``S``
+        is not positive definite, or ``kappa_2(S)`` is beyond about 1e8) and ``check()`` names the molecule.  Neither carries a gradient of ``S``."""
         _require_gpu(S_packed)
-        orb = BatchedOrbitals(plan_or_orb_ptr, S_packed.device).solve(S_packed)
-        return cls(orb, *orb.overlap_functions())
+        if method == "eigh":
+            orb = BatchedOrbitals(plan_or_orb_ptr, S_packed.device).solve(S_packed)
+            return cls(orb, *orb.overlap_functions())
+        if method != "newton_schulz":
+            raise ValueError(f"LowdinBasis.of: method must be \"eigh\" or \"newton_schulz\", not {method!r}")
+        orb = BatchedOrbitals(plan_or_orb_ptr, S_packed.device)
+        root = BatchedMatrixRoot(orb.orb_ptr, S_packed.device, state=orb.state).run(S_packed, max_iter)
+        basis = cls(orb, root.half, root.inv_half, None, root.status)
+        basis.root = root
+        return basis
 
     def check(self) -> "LowdinBasis":
+        if self.root is not None:
+            self.root.check()
+            return self
         self.orbitals.check()
         bad = np.nonzero(self.info.cpu().numpy())[0]
         if bad.size:
@@ -770,6 +792,111 @@ class LowdinBasis:
             st = self.orbitals.state
             lo = float(st.eps[int(st.orb_ptr_host[b])])
             raise RuntimeError(f"molecule {b}: the overlap matrix is not positive definite (its lowest level is {lo:g}): no S^(1/2) (info 1)")
+        return self
+
+
+class BatchedMatrixRoot:
+    """``S^(1/2)`` and ``S^(-1/2)`` of every molecule of a batch WITHOUT a decomposition: the coupled Newton-Schulz iteration on the float64 matrix cores
+    (csrc/orbsqrt.hip).
+
+    ``BatchedMatrixRoot(orb_ptr, device)`` as ``BatchedOrbitals`` (``state=``: an existing ``OrbitalState`` of the batch, whose layout and status words are
+    then used and whose matrices are left alone).  ``run(S_packed, max_iter=100)`` enqueues the scaling ``Y_0 = S / c`` (``c`` = the largest absolute row
+    sum), ``max_iter`` iterations ``T = (3 I - Z Y) / 2``, ``Y <- Y T``, ``Z <- T Z`` (two launches each; the workgroups of a finished molecule exit at once)
+    and the final scaling on the current stream and returns ``self``; nothing is read back.  ``prepare(S_packed, max_iter)`` / ``step(k)`` / ``finish()`` are
+    its parts (for tests: the steps in order from 0).  ``half`` / ``inv_half``: packed float64 [P], exactly symmetric.  ``iterations`` / ``status`` / ``info``
+    int32 [B] and ``residuals`` float64 [B, max_iter] (``delta_k = m - tr(Z_k Y_k)``) on the device.  ``check()`` reads the status once (a host
+    synchronisation) and raises ``RuntimeError`` naming the molecule whose ``S`` has unusable row sums (status 1) or did not converge (status 4: ``S`` is not
+    positive definite); such a molecule has NaN in its own blocks only.  Only the lower triangle of ``S`` (float32 or float64) is read.
+
+    About 18 iterations at ``kappa_2(S) = 1e4``, 25 at 1e6, 32 at 1e8; the stopping rule is meant for ``kappa_2(S) <= 1e8``.  Accuracy against a
+    decomposition: a fraction of ``m 2^-52 kappa_2(S) max|entry|``.  No gradient of ``S``."""
+
+    CTL = 24
+
+    def __init__(self, orb_ptr, device="cuda", state: Optional[OrbitalState] = None):
+        self.state = OrbitalState(orb_ptr, device) if state is None else state
+        if state is not None and not np.array_equal(state.orb_ptr_host, _orb_ptr_of(orb_ptr)):
+            raise ValueError("BatchedMatrixRoot: the state belongs to another batch")
+        self._max_iter = None
+        self.half = self.inv_half = None
+
+    status = property(lambda self: self.state.status)
+    info = property(lambda self: self.state.info)
+    iterations = property(lambda self: self.state.iters)
+    orb_ptr = property(lambda self: self.state.orb_ptr_host)
+    pack_ptr = property(lambda self: self.state.pack_ptr_host)
+    def _launch(self, name, *args):
+        st = self.state
+        with torch.cuda.device(st.buf.device):
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(st.buf), *st._dims, *args, _lib.stream_ptr()))
+
+    @property
+    def residuals(self) -> torch.Tensor:
+        self._prepared()
+        return self.ctl[:, self.CTL:]
+
+    def _prepared(self):
+        if self._max_iter is None:
+            raise RuntimeError("BatchedMatrixRoot: prepare() or run() first")
+
+    def _iterates(self):
+        return [_lib.ptr(t) for t in (self.Y, self.Z, self.T, self.Y2, self.Z2)]
+
+    def prepare(self, S_packed: torch.Tensor, max_iter: int = 100) -> "BatchedMatrixRoot":
+        """``nq_orb_sqrt_init``: ``c``, ``Y_0 = S / c``, ``Z_0 = I``, cleared ``ctl`` / ``log``, the status words."""
+        st, dev = self.state, self.state.buf.device
+        S = _packed(S_packed, st.P, "S_packed")
+        if S.device != dev:
+            raise ValueError(f"the matrices must live on {dev}")
+        max_iter = int(max_iter)
+        if not 1 <= max_iter <= 10000:
+            raise ValueError(f"max_iter={max_iter} outside 1..10000")
+        f64 = torch.float64
+        self.Y, self.Z, self.T, self.Y2, self.Z2 = (torch.empty(st.P, dtype=f64, device=dev) for _ in range(5))
+        self.ctl = torch.empty(st.B, self.CTL + max_iter, dtype=f64, device=dev)
+        self.log = torch.empty(st.B, max_iter, dtype=torch.int32, device=dev)
+        self.half = self.inv_half = None
+        self._max_iter = max_iter
+        self._launch("nq_orb_sqrt_init", _lib.ptr(S), int(S.dtype == f64), max_iter, _lib.ptr(self.Y), _lib.ptr(self.Z), _lib.ptr(self.ctl), _lib.ptr(self.log))
+        return self
+
+    def step(self, k: int) -> "BatchedMatrixRoot":
+        """Exactly one iteration, number ``k`` (``nq_orb_sqrt_step``; for tests: call them in order from 0)."""
+        self._prepared()
+        self._launch("nq_orb_sqrt_step", int(k), self._max_iter, *self._iterates(), _lib.ptr(self.ctl), _lib.ptr(self.log))
+        return self
+
+    def finish(self) -> "BatchedMatrixRoot":
+        """``nq_orb_sqrt_finish``: ``half`` and ``inv_half`` from the current iterates, status 4 and NaN for a molecule that did not stop."""
+        self._prepared()
+        st = self.state
+        self.half, self.inv_half = (torch.empty(st.P, dtype=torch.float64, device=st.buf.device) for _ in range(2))
+        self._launch("nq_orb_sqrt_finish", self._max_iter, _lib.ptr(self.Y), _lib.ptr(self.Z), _lib.ptr(self.Y2), _lib.ptr(self.Z2), _lib.ptr(self.ctl),
+                     _lib.ptr(self.log), _lib.ptr(self.half), _lib.ptr(self.inv_half))
+        return self
+
+    def run(self, S_packed: torch.Tensor, max_iter: int = 100) -> "BatchedMatrixRoot":
+        self.prepare(S_packed, max_iter)
+        self._launch("nq_orb_sqrt_run", self._max_iter, *self._iterates(), _lib.ptr(self.ctl), _lib.ptr(self.log))
+        self.finish()
+        self.Y = self.Z = self.T = self.Y2 = self.Z2 = None            # five [P] arrays nobody needs after the final scaling
+        return self
+
+    def check(self) -> "BatchedMatrixRoot":
+        self._prepared()
+        st = self.state
+        st.header()
+        status = st.status.cpu().numpy()
+        bad = np.nonzero(status)[0]
+        if bad.size:
+            b = int(bad[0])
+            if status[b] == 1:
+                raise RuntimeError(f"molecule {b}: the overlap matrix is not positive definite (its largest absolute row sum is zero or not finite): no "
+                                   "S^(1/2) (status 1)")
+            if status[b] == 4:
+                raise RuntimeError(f"molecule {b}: the Newton-Schulz iteration did not converge in {self._max_iter} iterations: the overlap matrix is not "
+                                   "positive definite, or its condition number is beyond about 1e8 (status 4)")
+            raise RuntimeError(_failure_text(b, int(status[b]), int(st.info[b]), int(st.m[b])))
         return self
 
 
@@ -1057,4 +1184,4 @@ def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
     return zz.to(device=atom_pop.device, dtype=torch.float64).reshape(-1) - atom_pop.to(torch.float64)
 
 
-__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "LowdinBasis", "OrbitalState", "OrbitalErrors", "ScfResidualErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
+__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "LowdinBasis", "BatchedMatrixRoot", "OrbitalState", "OrbitalErrors", "ScfResidualErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
