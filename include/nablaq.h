@@ -941,6 +941,24 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  *     untouched by it.
  *   NULL or aliased arrays, max_iter or k out of range and impossible dimensions are refused on the host and touch nothing.  float64 on
  *   v_mfma_f64_16x16x4_f64, no atomics, fixed summation orders: bitwise reproducible and independent of the rest of the batch; m = 1 .. 1024.
+ * Frontier levels without a solve (csrc/orbfrontier.hip; entry points added, ABI 17 unchanged): HOMO and LUMO of the orthogonalised Hamiltonian Ht of a
+ * purification (state part `work`) from its projector X (state part `coeff`) and its bounds shift [B][2] = (e_min, e_max) = ctl[b][0..1], by a Lanczos
+ * recurrence on P (Ht - e_min I) P with P = X (side 0, HOMO) and on P (e_max I - Ht) P with P = I - X (side 1, LUMO); the projector is applied on both sides
+ * of every application, every step is fully reorthogonalised in two passes.
+ *   nq_orb_front_lanczos: one workgroup per (molecule, side).  Ht, X [P]: full symmetric blocks; n_occ int32 [B]; W_or_null [P]: the back-transform, a general
+ *     block, coef_mu = sum_k W[k][mu] vec_k (the lower-triangular Z of nq_orb_pur_orthogonalizer or a symmetric S^(-1/2) alike; NULL: coef = vec); k_max in
+ *     1..1024; tol in (0, 1); V: workspace of 2 sum_b min(m_b, k_max) m_b doubles behind vptr int64 [B+1] (side s of molecule b at vptr[b] + s min(m, k_max) m).
+ *     Start vector v_0 = P r / |P r|, r_i = 0.5 + ((2654435761 i + 12345) mod 2^32) / 2^32 with i the orbital's index inside the molecule.  A side stops when
+ *     beta_j |s_last| <= tol (e_max - e_min) for the top Ritz pair (theta, s) of the tridiagonal, or after min(m, k_max) steps.  Outputs: eps [B][2] (the
+ *     Rayleigh quotient of the unshifted Ht, not theta), vec [2][M] (normalised), coef [2][M], iters int32 [B][2] (steps taken), res [B][2] (beta_j |s_last|
+ *     at the stop), conv int32 [B][2]: 1 converged, 0 not converged, -1 the level does not exist (HOMO for n_occ <= 0, LUMO for n_occ >= m).  conv != 1, a
+ *     molecule with status != 0 (conv 0) or a workspace slice that is too small (conv 0): NaN in that side's own eps, res, vec and coef, nothing else.
+ *   nq_orb_front_gram: out_gH [P] = sum_side g[b][side] c c^T and out_gS_or_null [P] = -sum_side g[b][side] eps[b][side] c c^T for c = coef of the side
+ *     (d eps / dH = c c^T, d eps / dS = -eps c c^T: the convention of the solver's energies); full blocks, exactly symmetric, elementwise.  conv = -1
+ *     contributes 0; conv = 0 or status != 0: NaN in the molecule's blocks.  out_gS needs eps.
+ *   NULL or aliased arrays, k_max, tol and impossible dimensions are refused on the host and touch nothing.  Plain float64 fma (memory-bound: no matrix-core
+ *   instruction), no atomics, fixed summation orders: bitwise reproducible and independent of the rest of the batch; m = 1 .. 1024.  Only the layout and the
+ *   status words of the state are read.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
 size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P);
 int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host);
@@ -1010,6 +1028,11 @@ int nq_orb_sqrt_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_it
                     void* stream);
 int nq_orb_sqrt_finish(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, const double* Y, const double* Z, const double* Y2, const double* Z2,
                        const double* ctl, const int32_t* log, double* half, double* inv_half, void* stream);
+int nq_orb_front_lanczos(void* state, int32_t B, int32_t M, int64_t P, const double* Ht, const double* X, const double* shift, const int32_t* n_occ,
+                         const double* W_or_null, int32_t k_max, double tol, double* V, const int64_t* vptr, double* eps, double* vec, double* coef, int32_t* iters,
+                         double* res, int32_t* conv, void* stream);
+int nq_orb_front_gram(void* state, int32_t B, int32_t M, int64_t P, const double* g, const double* eps_or_null, const double* coef, const int32_t* conv, double* out_gH,
+                      double* out_gS_or_null, void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

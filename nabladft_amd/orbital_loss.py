@@ -50,9 +50,18 @@ spectral-projection purification (SP2), ``D = 2 Z^T X Z``.  The response of a sp
 vector-Jacobian product is the density-matrix-perturbation recursion run with the upstream gradient as the perturbation, alongside the same SP2 iterates:
 ``X1_0 = -Gt / (e_max - e_min)``, ``X1 <- P + P^T`` or ``2 X1 - (P + P^T)`` with ``P = X X1`` by the branch the forward logged; then ``dL/dH = Z^T g Z`` and
 ``dL/dS = -Z^T (M + M^T + X Gt X) Z`` with ``M = g X Ht``.  No eigenpairs, no stored iterates, nothing divided.  It needs an open gap (a level shared by the
-occupied and the virtual side does not converge: status 4, NaN in that molecule's blocks) and has no energies and no smearing: ``orbital_solution`` /
+occupied and the virtual side does not converge: status 4, NaN in that molecule's blocks) and has no energies other than HOMO and LUMO (below) and no smearing: ``orbital_solution`` /
 ``smeared_solution`` stay the route for those.  ``QHNetPurifiedDensityLightning`` is ``QHNetDensityLightning`` on it.  Tested against the same yardsticks as
 ``orbital_solution`` and against ``orbital_solution`` itself (tests/orbital_purify_ref.py).
+
+**HOMO, LUMO and the gap without a solve.**  The purification leaves the orthogonalised ``Ht``, the projector ``X`` and the Gershgorin bounds on the device;
+``eps_HOMO = e_min + lambda_max(X (Ht - e_min I) X)`` and ``eps_LUMO = e_max - lambda_max((I - X)(e_max I - Ht)(I - X))`` are extreme eigenvalues of positive
+semidefinite operators, which ``purified_frontier`` finds by a fully reorthogonalised Lanczos recurrence (csrc/orbfrontier.hip: one workgroup per molecule and
+side, tens to about two hundred matrix-vector steps, no ``m^3`` work).  With ``c = Z^T v`` the gradients are ``d eps / dH = c c^T`` and
+``d eps / dS = -eps c c^T``, the convention of ``orbital_energies``: no eigenvector response.  ``FrontierLoss`` is the loss on them (``("mae", "both")`` equals
+``OrbitalEnergyLoss("mae", "frontier")``), ``QHNetPurifiedFrontierLightning`` the task with the key ``"frontier"``; a purified density term of the same step
+shares the purification (``solution=``).  These two are the only orbital energies the purification route has.  Tested against ``np.linalg.eigh``,
+``torch.linalg`` autograd and ``BatchedOrbitals.frontier`` (tests/orbital_frontier_ref.py).
 
 **Bond orders.**  ``bond_orders`` gives the Mayer bond-order table and the atomic valences of a closed-shell density under ``S``: with ``P = D S``,
 ``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` and ``V_A = sum_{B != A} B_AB`` (``S = None``: the Wiberg index of an orthogonal basis).  The reverse forms
@@ -99,7 +108,7 @@ import torch
 from torch import nn
 
 from .lightning import QHNetLightning
-from .orbitals import (BatchedMatrixRoot, BatchedOrbitals, BatchedPurification, LowdinBasis, Orthogonalizer, _orb_ptr_of, _require_gpu, bond_layout, check_occupied, dense_bond_orders,  # noqa: F401
+from .orbitals import (BatchedMatrixRoot, BatchedOrbitals, BatchedPurification, FrontierLevels, LowdinBasis, Orthogonalizer, _orb_ptr_of, _require_gpu, bond_layout, check_occupied, dense_bond_orders,  # noqa: F401
                        ScfResidualErrors, electron_counts, mulliken_charges, occupied_counts)
 
 
@@ -1024,7 +1033,8 @@ def purified_density_matrix(H_packed: torch.Tensor, S_packed: Optional[torch.Ten
     upstream gradient need not be symmetric; nothing is launched without one, the ``S`` half is skipped when ``S`` is None or requires no gradient, and the
     gradients are cast to the inputs' dtypes in the symmetric-matrix convention of ``orbital_energies``.  **Needs an open gap**: a molecule whose
     purification does not converge in ``max_iter`` iterations (status 4) or whose overlap is not positive definite (status 1) yields NaN in its own blocks
-    only; ``BatchedPurification.check()`` reports both.  No energies and no smearing.  ``populations(D, plan, S, H, orbitals=solution)`` works on the result."""
+    only; ``BatchedPurification.check()`` reports both.  No energies other than HOMO and LUMO (``purified_frontier(..., solution=solution)``) and no smearing.
+    ``populations(D, plan, S, H, orbitals=solution)`` works on the result."""
     _require_gpu(H_packed)
     if S_packed is not None:
         _require_gpu(S_packed)
@@ -1040,7 +1050,7 @@ def purified_density_matrix(H_packed: torch.Tensor, S_packed: Optional[torch.Ten
 class QHNetPurifiedDensityLightning(QHNetDensityLightning):
     """``QHNetDensityLightning`` without a solve: ``"density_matrix"`` and ``"mulliken_charges"`` come from ``purified_density_matrix`` of the packed prediction
     and a detached ``BatchedPurification`` of the packed target, both through ONE orthogonalizer of ``batch.overlap`` per step.  Purification has no orbital
-    energies: an active ``"orbital_energies"`` key raises ``ValueError`` (use the parent).  ``max_iter`` (attribute; class default 100) caps the iterations.
+    energies other than HOMO and LUMO (``QHNetPurifiedFrontierLightning``): an active ``"orbital_energies"`` key raises ``ValueError`` (use the parent).  ``max_iter`` (attribute; class default 100) caps the iterations.
     Prefer it where the gaps are safely open; a molecule without a gap gets NaN, which the parent's solver does not need.  With both coefficients at 0 (or
     without the keys) nothing is purified and the step is ``QHNetLightning``'s."""
 
@@ -1078,9 +1088,169 @@ class QHNetPurifiedDensityLightning(QHNetDensityLightning):
         return preds, targets, loss_args
 
 
+
+class _PurifiedFrontier(torch.autograd.Function):
+    """Forward: ``BatchedPurification.purify`` (unless the solution came purified) and ``frontier``.  Backward: one ``nq_orb_front_gram`` launch; nothing is
+    launched without an upstream gradient, and the ``S`` half is skipped when ``S`` asks for nothing."""
+
+    @staticmethod
+    def forward(ctx, pur, H, S, n_occ, orth, max_iter, k_max, tol, fresh):
+        if fresh:
+            pur.purify(H, n_occ, max_iter, orth)
+        levels = pur.frontier(k_max, tol)
+        ctx.set_materialize_grads(False)
+        ctx.pur, ctx.levels = pur, levels
+        ctx.h = (H.shape, H.dtype)
+        ctx.s = None if S is None else (S.shape, S.dtype)
+        pur.levels = levels
+        return levels.homo.clone(), levels.lumo.clone()
+
+    @staticmethod
+    def backward(ctx, g_homo, g_lumo):
+        none = (None,) * 9
+        want_h = ctx.needs_input_grad[1]
+        want_s = ctx.s is not None and ctx.needs_input_grad[2]
+        if (g_homo is None and g_lumo is None) or not (want_h or want_s):
+            return none
+        g = [None if t is None else t.to(torch.float64).reshape(-1).contiguous() for t in (g_homo, g_lumo)]
+        gH, gS = ctx.pur.frontier_gradients(ctx.levels, g[0], g[1], want_s)
+        return (None, gH.to(ctx.h[1]).view(ctx.h[0]) if want_h else None, gS.to(ctx.s[1]).view(ctx.s[0]) if want_s else None) + none[3:]
+
+
+def purified_frontier(H_packed: torch.Tensor, S_packed: Optional[torch.Tensor], plan_or_orb_ptr, n_occ, orthogonalizer: Optional[Orthogonalizer] = None,
+                      max_iter: int = 100, k_max: int = 256, tol: float = 2.0 ** -44, solution: Optional[BatchedPurification] = None,
+                      return_solution: bool = False):
+    """HOMO and LUMO of every molecule WITHOUT a solve -> ``(homo, lumo)`` float64 [B] on the device (``return_solution=True``: ``(homo, lumo,
+    BatchedPurification)``; its ``levels`` attribute holds the ``FrontierLevels``), differentiable with respect to ``H_packed`` and ``S_packed``: SP2
+    purification, then a projected Lanczos recurrence on ``X``, ``Ht`` and the bounds (``BatchedPurification.frontier``).
+
+    Arguments as for ``purified_density_matrix``; ``k_max`` caps the Lanczos steps per side (26..190 were needed at 130..539 orbitals), ``tol`` is the
+    residual bound in units of the Gershgorin width (the gradients are accurate to ``tol / sep``, ``sep`` the distance to the neighbouring level).
+    ``solution``: the ``BatchedPurification`` that ``purified_density_matrix(..., return_solution=True)`` already ran on the SAME ``H_packed`` (and ``S_packed``)
+    -- the prediction is then purified once per step; ``orthogonalizer`` and ``max_iter`` are its own.  The gradients need no eigenvector response:
+    ``d eps / dH = c c^T``, ``d eps / dS = -eps c c^T`` (the convention of ``orbital_energies``), cast to the inputs' dtypes; nothing is launched without an
+    upstream gradient and the ``S`` half is skipped when ``S`` is None or requires no gradient.  A level that does not exist (the LUMO where ``n_occ = m``, the
+    HOMO where ``n_occ = 0``) is NaN and takes no gradient; a side that does not converge in ``k_max`` steps is NaN and gives NaN gradient blocks for its
+    molecule only (``solution.frontier_check(solution.levels)`` reports it).  Needs an open gap, like the purification it follows."""
+    _require_gpu(H_packed)
+    if S_packed is not None:
+        _require_gpu(S_packed)
+    elif orthogonalizer is not None:
+        raise ValueError("purified_frontier: an orthogonalizer without S_packed")
+    fresh = solution is None
+    if fresh:
+        pur = BatchedPurification(plan_or_orb_ptr, H_packed.device)
+        if S_packed is not None and orthogonalizer is None:
+            orthogonalizer = pur.orthogonalize(S_packed)
+    else:
+        pur = solution
+        pur._purified()
+        if not np.array_equal(pur.orb_ptr, _orb_ptr_of(plan_or_orb_ptr)):
+            raise ValueError("purified_frontier: the solution belongs to another batch")
+        if (pur._orth is None) != (S_packed is None):
+            raise ValueError("purified_frontier: the solution was purified with an overlap and S_packed is None, or the reverse")
+    homo, lumo = _PurifiedFrontier.apply(pur, H_packed, S_packed, n_occ, orthogonalizer, max_iter, k_max, tol, fresh)
+    return (homo, lumo, pur) if return_solution else (homo, lumo)
+
+
+class FrontierLoss(nn.Module):
+    """``kind`` "mae" | "mse" of the frontier levels, ``which`` = "gap" (LUMO - HOMO) | "homo" | "lumo" | "both": the mean over the existing selected levels of each
+    molecule, then the mean over the molecules (a molecule where none of them exists -- the LUMO or the gap where every orbital is occupied -- adds 0).
+    ``("mae", "both")`` equals ``OrbitalEnergyLoss("mae", "frontier")`` on the same levels.  Prediction and target: float64 [2, B], row 0 HOMO, row 1 LUMO (what
+    ``torch.stack(purified_frontier(...))`` gives; NaN where a level does not exist).  ``charge`` is what the task counts the occupied orbitals with."""
+
+    packed = True
+
+    def __init__(self, kind: str = "mae", which: str = "gap", charge=0):
+        super().__init__()
+        if kind not in ("mae", "mse"):
+            raise ValueError(f"kind must be 'mae' or 'mse', not {kind!r}")
+        if which not in ("gap", "homo", "lumo", "both"):
+            raise ValueError(f"which must be 'gap', 'homo', 'lumo' or 'both', not {which!r}")
+        self.kind, self.which, self.charge = kind, which, charge
+
+    def occupied(self, z, ptr, orb_ptr=None) -> torch.Tensor:
+        return occupied_counts(z, ptr, self.charge, orb_ptr)
+
+    def forward(self, pred: torch.Tensor, target: torch.Tensor, n_occ, orb_ptr) -> torch.Tensor:
+        _require_gpu(pred)
+        op = _orb_ptr_of(orb_ptr)
+        no = check_occupied(n_occ, op)
+        m = np.diff(op)
+        B = m.shape[0]
+        if tuple(pred.shape) != (2, B) or tuple(target.shape) != (2, B):
+            raise ValueError(f"the levels have shapes {tuple(pred.shape)} / {tuple(target.shape)}, orb_ptr counts [2, {B}]")
+        has_lumo = no < m
+        d = pred.to(torch.float64) - target.to(torch.float64).detach()
+        if self.which == "gap":
+            rows, w = (d[1] - d[0]).unsqueeze(0), has_lumo[None, :] / B
+        elif self.which == "homo":
+            rows, w = d[0:1], np.full((1, B), 1.0 / B)
+        elif self.which == "lumo":
+            rows, w = d[1:2], has_lumo[None, :] / B
+        else:
+            rows, w = d, np.stack([np.ones(B), has_lumo.astype(np.float64)]) / (1.0 + has_lumo) / B
+        weight = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(pred.device)
+        rows = torch.where(weight > 0, rows, torch.zeros_like(rows))          # a level that does not exist is NaN: it neither counts nor takes a gradient
+        return torch.sum(weight * (rows.abs() if self.kind == "mae" else rows * rows))
+
+
+class QHNetPurifiedFrontierLightning(QHNetPurifiedDensityLightning):
+    """``QHNetPurifiedDensityLightning`` with a term on HOMO, LUMO or the gap, still without a solve: ``losses`` / ``loss_coefs`` take ``"frontier"`` (a
+    ``FrontierLoss``).  The prediction goes through ``purified_frontier``, which shares the purification of an active ``"density_matrix"`` /
+    ``"mulliken_charges"`` term (one ``nq_orb_pur_run`` for the prediction per step); the target through a detached ``BatchedPurification(...).frontier()``;
+    ONE orthogonalizer of ``batch.overlap`` per step serves all of it.  ``k_max`` / ``tol`` (attributes; class defaults 256 and 2^-44) are the Lanczos limits.
+    With the ``"frontier"`` coefficient at 0 (or without the key) the step is the parent's, and the parent's refusal of ``"orbital_energies"`` stays."""
+
+    KEYS = QHNetPurifiedDensityLightning.KEYS + ("frontier",)
+    k_max = 256
+    tol = 2.0 ** -44
+
+    def _evaluate(self, batch):
+        active = self._active()
+        if "frontier" not in active:
+            return super()._evaluate(batch)
+        if not self._packed():
+            raise ValueError("QHNetPurifiedFrontierLightning needs packed losses (HamiltonianLoss, FrontierLoss, DensityMatrixLoss, MullikenChargeLoss)")
+        if "orbital_energies" in active:
+            raise ValueError("QHNetPurifiedFrontierLightning: purification has no orbital energies other than HOMO and LUMO; use QHNetDensityLightning for an "
+                             "\"orbital_energies\" term")
+        preds, targets, loss_args = QHNetLightning._evaluate(self, batch)
+        charges = [getattr(self.hparams.losses[k], "charge", 0) for k in active]
+        if any(not np.array_equal(np.asarray(c), np.asarray(charges[0])) for c in charges[1:]):
+            raise ValueError("the orbital losses count the occupied orbitals with different charges")
+        plan, asm = self.net.last_plan, self.net._asm
+        overlap = getattr(batch, "overlap", None)
+        S = None if overlap is None else asm.pack_targets(plan, overlap)
+        op = _orb_ptr_of(plan)
+        n_occ = occupied_counts(batch.z, batch.ptr, charges[0], op)
+        Hp, Ht = preds["hamiltonian"], targets["hamiltonian"]
+        pur_t = BatchedPurification(op, Hp.device)
+        orth = None if S is None else pur_t.orthogonalize(S)
+        pur_t.purify(Ht, n_occ, self.max_iter, orth)
+        lv_t = pur_t.frontier(self.k_max, self.tol)
+        need_density = any(k != "frontier" for k in active)
+        pur_p = None
+        if need_density:
+            D_t = pur_t.density()
+            D, pur_p = purified_density_matrix(Hp, S, op, n_occ, orth, self.max_iter, return_solution=True)
+        homo, lumo = purified_frontier(Hp, S, op, n_occ, orth, self.max_iter, self.k_max, self.tol, solution=pur_p)
+        for k in active:
+            if k == "frontier":
+                preds[k], targets[k], preds[k + "_args"] = torch.stack((homo, lumo)), torch.stack((lv_t.homo, lv_t.lumo)), (n_occ, op)
+            elif k == "density_matrix":
+                preds[k], targets[k], preds[k + "_args"] = D, D_t, (op,)
+            else:
+                preds[k] = mulliken_charges(batch.z, populations(D, plan, S, None, pur_p)[0])
+                targets[k] = mulliken_charges(batch.z, pur_t.populations(D_t, plan, S)[0])
+                preds[k + "_args"] = (batch.ptr,)
+        return preds, targets, loss_args
+
+
 __all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "orbital_solution", "density_matrix", "populations",
            "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "SmearedSolution", "smeared_solution", "smeared_density_matrix",
            "QHNetSmearedDensityLightning", "purified_density_matrix", "QHNetPurifiedDensityLightning", "bond_orders", "BondOrderLoss", "QHNetBondOrderLightning",
            "bond_layout", "dense_bond_orders", "LowdinBasis", "lowdin_basis", "lowdin_density", "lowdin_hamiltonian", "lowdin_populations", "lowdin_charges",
            "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning", "commutator", "scf_residual", "scf_residual_to_target", "ScfResidualLoss", "ScfTarget",
-           "scf_target", "scf_target_iterative", "scf_target_blocks", "BatchedMatrixRoot", "QHNetCommutatorLightning", "ScfResidualErrors"]
+           "scf_target", "scf_target_iterative", "scf_target_blocks", "BatchedMatrixRoot", "QHNetCommutatorLightning", "ScfResidualErrors", "purified_frontier", "FrontierLoss",
+           "QHNetPurifiedFrontierLightning", "FrontierLevels"]

@@ -44,7 +44,10 @@ gradient chain over all orbital pairs, evaluated without dividing by a differenc
 **Without a solve.**  ``BatchedPurification`` gives the closed-shell density ``D = 2 Z^T X Z`` and its gradients from symmetric matrix products alone
 (csrc/orbpurify.hip): ``Z = L^-1`` of ``S = L L^T`` (``orthogonalize``; one serves prediction and target), ``X`` the projector on the ``n_occ`` lowest levels of
 ``Z H Z^T`` by second-order spectral-projection purification, the gradient by the density-matrix-perturbation recursion along the same iterates
-(``nabladft_amd.orbital_loss.purified_density_matrix`` is the differentiable call).  Closed shells only, needs an open gap, no energies, no smearing.
+(``nabladft_amd.orbital_loss.purified_density_matrix`` is the differentiable call).  Closed shells only, needs an open gap, no smearing, no orbital energies
+other than HOMO and LUMO: ``frontier()`` gives those two from ``X``, ``Ht`` and the bounds by a projected Lanczos recurrence (csrc/orbfrontier.hip; one
+workgroup per molecule and side, no ``m^3`` work), ``frontier_gradients`` their gradients ``c c^T`` and ``-eps c c^T``
+(``nabladft_amd.orbital_loss.purified_frontier`` is the differentiable call).
 
 Limits (each raises, nothing degrades silently): 1..``MAX_ORBITALS`` = 1024 orbitals per molecule; closed shells only in ``occupied_counts`` / ``density``
 (``occupied_counts`` refuses an odd electron count; the smeared calls take any count in (0, 2m)); MI355X only, no CPU path.
@@ -900,6 +903,13 @@ class BatchedMatrixRoot:
         return self
 
 
+FrontierLevels = namedtuple("FrontierLevels", "homo lumo gap coeff vectors iterations residual converged")
+FrontierLevels.__doc__ = """What ``BatchedPurification.frontier`` returns, all on the device: ``homo`` / ``lumo`` / ``gap`` float64 [B] (NaN where the level does not exist or
+the side did not converge), ``coeff`` float64 [2, M] (the levels' coefficient vectors ``c = W^T v`` in the atomic-orbital basis, ``c^T S c = 1``; row 0 HOMO, row 1
+LUMO), ``vectors`` float64 [2, M] (``v`` in the orthonormal basis), ``iterations`` int32 [B, 2] (Lanczos steps), ``residual`` float64 [B, 2] (``beta |s_last|`` at
+the stop) and ``converged`` int32 [B, 2]: 1 converged, 0 not converged, -1 the level does not exist (HOMO for ``n_occ = 0``, LUMO for ``n_occ = m``)."""
+
+
 Orthogonalizer = namedtuple("Orthogonalizer", "Z status info orb_ptr")
 Orthogonalizer.__doc__ = """What ``BatchedPurification.orthogonalize`` returns, reusable for any purification of the same batch: ``Z`` float64 [P] on the device
 (``L^-1`` of ``S = L L^T`` per molecule, lower triangular), ``status`` / ``info`` int32 [B] copies (1: the overlap is not positive definite, ``info`` = the
@@ -918,7 +928,12 @@ class BatchedPurification:
     with no stored iterates, no eigenpairs and no division.  ``iterations`` int32 [B] on the device.  ``check()`` reads the status once (a host
     synchronisation) and raises ``RuntimeError`` naming the molecule whose overlap was not positive definite (status 1) or whose purification did not
     converge (status 4: needs an open gap).  A failed molecule has NaN in its own blocks only.  ``populations`` / ``populations_backward`` / ``bond_orders`` /
-    ``bond_orders_backward`` and the layout-only Löwdin launches (``low_product`` / ``low_symprod`` / ``sym_congruence``) are ``BatchedOrbitals``'.  No energies, no smearing, closed shells only."""
+    ``bond_orders_backward`` and the layout-only Löwdin launches (``low_product`` / ``low_symprod`` / ``sym_congruence``) are ``BatchedOrbitals``'.  After ``purify``,
+    ``frontier(k_max=256, tol=2**-44, transform=None)`` -> ``FrontierLevels``: HOMO, LUMO and the gap by a projected Lanczos recurrence (one launch,
+    csrc/orbfrontier.hip); ``transform``: a packed float64 [P] back-transform in place of the orthogonaliser of the last purify (``S^(-1/2)`` after a purification of
+    the standard problem in the Löwdin basis).  ``frontier_gradients(levels, g_homo, g_lumo, overlap=True)`` -> ``(dL/dH, dL/dS or None)``;
+    ``frontier_check(levels)`` raises naming the first molecule and side that did not converge in ``k_max`` steps.  No energies other than HOMO and LUMO, no
+    smearing, closed shells only."""
 
     def __init__(self, orb_ptr, device="cuda"):
         self.state = OrbitalState(orb_ptr, device)
@@ -1066,6 +1081,61 @@ class BatchedPurification:
         A = self.gemm(st.coeff, self.gemm(Gt, st.coeff), M2)                               # X Gt X + 2 M; its symmetric part is M + M^T + X Gt X
         return gH, self.congruence(Z, A, True, -1.0, symmetrize=True)
 
+    def frontier(self, k_max: int = 256, tol: float = 2.0 ** -44, transform: Optional[torch.Tensor] = None) -> FrontierLevels:
+        """HOMO, LUMO and the gap of the last ``purify`` (``nq_orb_front_lanczos``, one launch on the current stream, nothing is read back)."""
+        self._purified()
+        st, dev = self.state, self.state.buf.device
+        k_max, tol = int(k_max), float(tol)
+        if not 1 <= k_max <= 1024:
+            raise ValueError(f"k_max={k_max} outside 1..1024")
+        if not 0.0 < tol < 1.0:
+            raise ValueError(f"tol={tol} outside (0, 1)")
+        if transform is None:
+            W = None if self._orth is None else self._orth.Z
+        else:
+            W = self._f64(transform, st.P, "transform")
+        kk = np.minimum(st.m, k_max)
+        vptr_host = np.concatenate([[0], np.cumsum(2 * kk * st.m)]).astype(np.int64)
+        vptr = torch.from_numpy(vptr_host).to(dev)
+        V = self._scratch(int(vptr_host[-1]))
+        shift = self.ctl[:, :2].contiguous()
+        eps = torch.empty(st.B, 2, dtype=torch.float64, device=dev)
+        res = torch.empty(st.B, 2, dtype=torch.float64, device=dev)
+        vec = torch.empty(2, st.M, dtype=torch.float64, device=dev)
+        coef = torch.empty(2, st.M, dtype=torch.float64, device=dev)
+        iters = torch.empty(st.B, 2, dtype=torch.int32, device=dev)
+        conv = torch.empty(st.B, 2, dtype=torch.int32, device=dev)
+        self._call("nq_orb_front_lanczos", _lib.ptr(st.work), _lib.ptr(st.coeff), _lib.ptr(shift), _lib.ptr(self._n_occ), _lib.ptr(W), k_max, tol, _lib.ptr(V),
+                   _lib.ptr(vptr), _lib.ptr(eps), _lib.ptr(vec), _lib.ptr(coef), _lib.ptr(iters), _lib.ptr(res), _lib.ptr(conv))
+        self._k_max = k_max
+        return FrontierLevels(eps[:, 0], eps[:, 1], eps[:, 1] - eps[:, 0], coef, vec, iters, res, conv)
+
+    def frontier_gradients(self, levels: FrontierLevels, g_homo: Optional[torch.Tensor], g_lumo: Optional[torch.Tensor], overlap: bool = True):
+        """``(dL/dH, dL/dS or None)`` for the upstream gradients ``g_homo`` / ``g_lumo`` float64 [B] (None: zero) of ``levels.homo`` / ``levels.lumo``: ``sum g c c^T`` and
+        ``-sum g eps c c^T`` (``nq_orb_front_gram``), packed float64 [P], exactly symmetric.  A level that does not exist contributes nothing."""
+        st, dev = self.state, self.state.buf.device
+        g = torch.zeros(st.B, 2, dtype=torch.float64, device=dev)
+        for k, gk in enumerate((g_homo, g_lumo)):
+            if gk is not None:
+                g[:, k] = self._f64(gk, st.B, "g_homo" if k == 0 else "g_lumo")
+        eps = torch.stack((levels.homo, levels.lumo), 1).contiguous()
+        gH = self._scratch(st.P)
+        gS = self._scratch(st.P, bool(overlap))
+        self._call("nq_orb_front_gram", _lib.ptr(g), _lib.ptr(eps), _lib.ptr(self._f64(levels.coeff, 2 * st.M, "levels.coeff")), _lib.ptr(levels.converged),
+                   _lib.ptr(gH), _lib.ptr(gS))
+        return gH, gS
+
+    def frontier_check(self, levels: FrontierLevels) -> "BatchedPurification":
+        """Reads ``levels.converged`` once (a host synchronisation) and raises ``RuntimeError`` naming the first molecule and side that did not converge."""
+        self.check()
+        conv = levels.converged.cpu().numpy()
+        bad = np.argwhere(conv == 0)
+        if bad.size:
+            b, side = int(bad[0][0]), int(bad[0][1])
+            raise RuntimeError(f"molecule {b}: the {'LUMO' if side else 'HOMO'} did not converge in {int(levels.iterations[b, side])} Lanczos steps "
+                               f"(k_max={getattr(self, '_k_max', None)}, m={int(self.state.m[b])})")
+        return self
+
     def check(self) -> "BatchedPurification":
         st = self.state
         st.header()
@@ -1184,4 +1254,4 @@ def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
     return zz.to(device=atom_pop.device, dtype=torch.float64).reshape(-1) - atom_pop.to(torch.float64)
 
 
-__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "LowdinBasis", "BatchedMatrixRoot", "OrbitalState", "OrbitalErrors", "ScfResidualErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
+__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "FrontierLevels", "LowdinBasis", "BatchedMatrixRoot", "OrbitalState", "OrbitalErrors", "ScfResidualErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
