@@ -22,18 +22,19 @@ SOURCES = ["graph.hip", "gemm.hip", "gemm_bf16.hip", "edge.hip", "molpair.hip", 
 # orbitals.hip: the rank-2 update of the tridiagonalisation keeps the matrix exactly symmetric only if v_i w_j + w_i v_j is two products and one sum; the
 # kernels call fma() where they want one
 # orbdens.hip: the same setting as the solver it follows; its sums are written with fma() and the matrix instruction
-# orbresp.hip: the same, for the density response that follows both
+# orbresp.hip: the same, for the density response that follows both (from here on every file takes the molecule lookup, the workgroup sum and maximum and
+# the host-side launch check from orbstate.h, and the product tiles and the symmetrise tile routine from orbresp_tiles.h)
 # orbsmear.hip: the same, for the smeared occupations and their response (it shares orbresp_tiles.h with orbresp.hip)
 # orbpurify.hip: the same, for the purification and its response: 2 X - Y and the mirrored tiles keep X exactly symmetric (it shares orbresp_tiles.h too)
 # orbbond.hip: the same, for the bond orders that follow a density: its pair sums are written with fma() and the matrix instruction (orbresp_tiles.h again)
-# orblowdin.hip: the same, for the Löwdin functions of S and their reverse: K = 1 / (a_i + a_j) is a sum and a division as written (it shares orbbond_tiles.h
-# with orbbond.hip)
+# orblowdin.hip: the same, for the Löwdin functions of S and their reverse: K = 1 / (a_i + a_j) is a sum and a division as written (it shares the run-time-oriented
+# operand tiles of orbbond_tiles.h with orbbond.hip; its symmetrise kernel is the tile routine of orbresp_tiles.h)
 # orbcomm.hip: the same, for the commutators of the SCF residual: the difference of its two contractions is taken inside the accumulators as written (it
-# shares orbbond_tiles.h too)
+# shares orbbond_tiles.h too; its antisymmetrise kernel is the same tile routine with the other sign)
 # orbsqrt.hip: the same, for the Newton-Schulz square roots: (3 I - Z Y) / 2 is a difference and a product as written, so that T is the mirrored number on both
 # sides of the diagonal (it shares orbresp_tiles.h with orbpurify.hip)
 # orbfrontier.hip: the same, for the projected Lanczos recurrence of the frontier levels: its sums are written with fma(), and c_i c_j is one product on both
-# sides of the diagonal (it shares orbbond_tiles.h with orbbond.hip)
+# sides of the diagonal (it includes orbbond_tiles.h for the tiles' constants; its molecule lookup is orbstate.h's)
 EXTRA = {"molpair.hip": ["-fno-slp-vectorize"], "md.hip": ["-ffp-contract=off"], "vib.hip": ["-ffp-contract=off"], "orbitals.hip": ["-ffp-contract=off"], "orbdens.hip": ["-ffp-contract=off"], "orbresp.hip": ["-ffp-contract=off"], "orbsmear.hip": ["-ffp-contract=off"], "orbpurify.hip": ["-ffp-contract=off"], "orbbond.hip": ["-ffp-contract=off"], "orblowdin.hip": ["-ffp-contract=off"], "orbcomm.hip": ["-ffp-contract=off"], "orbsqrt.hip": ["-ffp-contract=off"], "orbfrontier.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=on", "-Wall", "-Wno-unused-function"]
 

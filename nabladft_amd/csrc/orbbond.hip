@@ -66,8 +66,8 @@ __device__ __forceinline__ bool bd_range(const long long* atom_orb_ptr, int at, 
 // ---- P = D S -----------------------------------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NQ_RS_NT) void k_orb_bond_product(OrbArgs a, int tr, const double* D, const void* S, int s_f64, double* out) {
   __shared__ double lds[2 * NQ_RS_TILE];
-  BdMol q;
-  if (!bd_mol(a, tr * tr, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, tr * tr, q)) return;
   const int m = q.m, ti = q.t / tr, tj = q.t - ti * tr;
   const int i0 = ti * NQ_ORB_TILE, j0 = tj * NQ_ORB_TILE;
   if (i0 >= m || j0 >= m) return;                              // uniform
@@ -100,8 +100,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_orb_bond_product(OrbArgs a, int tr
 // ---- B_AB ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NQ_RS_NT) void k_orb_bond_reduce(OrbArgs a, const double* Pm, int N, long long Q, const int* mol_ptr, const long long* atom_orb_ptr,
                                                               const long long* bond_ptr, double* bond) {
-  BdMol q;
-  if (!bd_mol(a, NQ_BD_CHUNKS, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, NQ_BD_CHUNKS, q)) return;
   BdAtoms t;
   if (!bd_atoms(q.b, N, Q, mol_ptr, bond_ptr, t)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = q.m;
@@ -134,8 +134,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_orb_bond_reduce(OrbArgs a, const d
 
 __global__ __launch_bounds__(NQ_RS_NT) void k_orb_bond_valence(OrbArgs a, int N, long long Q, const int* mol_ptr, const long long* bond_ptr, const double* bond,
                                                                double* valence) {
-  BdMol q;
-  if (!bd_mol(a, NQ_BD_CHUNKS, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, NQ_BD_CHUNKS, q)) return;
   BdAtoms t;
   if (!bd_atoms(q.b, N, Q, mol_ptr, bond_ptr, t)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -153,8 +153,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_orb_bond_valence(OrbArgs a, int N,
 __global__ __launch_bounds__(NQ_RS_NT) void k_orb_bond_e(OrbArgs a, int tr, const double* gB, const double* gV, const double* Pm, int N, long long Q,
                                                          const int* mol_ptr, const long long* atom_orb_ptr, const long long* bond_ptr, double* E) {
   __shared__ short atom_of[NQ_ORB_MAX_M];
-  BdMol q;
-  if (!bd_mol(a, tr, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, tr, q)) return;
   const int m = q.m, i0 = q.t * NQ_ORB_TILE;
   if (i0 >= m) return;                                         // uniform
   BdAtoms t;
@@ -193,8 +193,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_orb_bond_e(OrbArgs a, int tr, cons
 __global__ __launch_bounds__(NQ_RS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_orb_bond_backward(OrbArgs a, int nt, const double* E, const double* D, const void* S, int s_f64, double* gD,
                                                                 double* gS) {
   __shared__ double lds[4 * NQ_RS_TILE];
-  BdMol q;
-  if (!bd_mol(a, nt, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, nt, q)) return;
   const int m = q.m;
   if (q.t >= orb_tile_count(m)) return;                        // uniform
   int ti, tj;
@@ -245,11 +245,10 @@ static int bd_check_atoms(const char* who, int32_t B, int32_t N, int64_t Q, bool
 extern "C" {
 
 int nq_orb_bond_product(void* state, int32_t B, int32_t M, int64_t P, const double* D, const void* S, int32_t s_f64, double* out_P, void* stream) {
-  if (!state || !D || !out_P) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_product: null argument");
+  int tr = 0;
+  NQ_TRY(orb_check_launch("nq_orb_bond_product", state, B, M, P, ORB_GRID_SQUARE, &tr));
+  if (!D || !out_P) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_product: null argument");
   if (out_P == D || (const void*)out_P == S) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_product: the output must not be an operand");
-  NQ_TRY(orb_check_dims(B, M, P));
-  const int tr = orb_tile_rows(orb_largest_m_bound(B, M, P));
-  NQ_TRY(bd_check_grid("nq_orb_bond_product", B, (long long)tr * tr));
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, S ? "orb_bond_product" : "orb_bond_product_copy");
   hipLaunchKernelGGL(k_orb_bond_product, dim3(B * tr * tr), dim3(NQ_RS_NT), 0, st, orb_args(state, B, M, P), tr, D, S, s_f64, out_P);
@@ -259,10 +258,9 @@ int nq_orb_bond_product(void* state, int32_t B, int32_t M, int64_t P, const doub
 
 int nq_orb_bond_reduce(void* state, int32_t B, int32_t M, int64_t P, const double* Pm, int32_t N, int64_t Q, const int32_t* mol_ptr, const int64_t* atom_orb_ptr,
                        const int64_t* bond_ptr, double* out_bond, double* out_valence, void* stream) {
-  if (!state || !Pm || !mol_ptr || !atom_orb_ptr || !bond_ptr || !out_bond) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_reduce: null argument");
-  NQ_TRY(orb_check_dims(B, M, P));
+  NQ_TRY(orb_check_launch("nq_orb_bond_reduce", state, B, M, P, ORB_GRID_MOL, nullptr, NQ_BD_CHUNKS));
+  if (!Pm || !mol_ptr || !atom_orb_ptr || !bond_ptr || !out_bond) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_reduce: null argument");
   NQ_TRY(bd_check_atoms("nq_orb_bond_reduce", B, N, Q, true));
-  NQ_TRY(bd_check_grid("nq_orb_bond_reduce", B, NQ_BD_CHUNKS));
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_bond_reduce");
   const OrbArgs a = orb_args(state, B, M, P);
@@ -280,7 +278,9 @@ int nq_orb_bond_reduce(void* state, int32_t B, int32_t M, int64_t P, const doubl
 int nq_orb_bond_backward(void* state, int32_t B, int32_t M, int64_t P, const double* gB, const double* gV, const double* Pm, const double* D, const void* S,
                          int32_t s_f64, int32_t N, int64_t Q, const int32_t* mol_ptr, const int64_t* atom_orb_ptr, const int64_t* bond_ptr, double* E,
                          double* out_gD, double* out_gS, void* stream) {
-  if (!state || !Pm || !mol_ptr || !atom_orb_ptr || !E) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_backward: null argument");
+  int tr = 0;
+  NQ_TRY(orb_check_launch("nq_orb_bond_backward", state, B, M, P, ORB_GRID_LOWER, &tr));
+  if (!Pm || !mol_ptr || !atom_orb_ptr || !E) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_backward: null argument");
   if (gB && !bond_ptr) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_backward: null argument (gB needs bond_ptr)");
   if (!out_gD && !out_gS) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_backward: null argument (no output)");
   if (out_gS && !S) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_backward: a gradient of S needs S");
@@ -288,10 +288,8 @@ int nq_orb_bond_backward(void* state, int32_t B, int32_t M, int64_t P, const dou
   if (D && !out_gS) return nq_fail(NQ_ERR_ARG, "nq_orb_bond_backward: D is the second input, of out_gS: a second input needs its output");
   if (E == Pm || E == out_gD || E == out_gS || E == D || (const void*)E == S || (out_gD && out_gD == out_gS))
     return nq_fail(NQ_ERR_ARG, "nq_orb_bond_backward: E and the outputs must be arrays of their own");
-  NQ_TRY(orb_check_dims(B, M, P));
   NQ_TRY(bd_check_atoms("nq_orb_bond_backward", B, N, Q, gB != nullptr));
-  const int tr = orb_tile_rows(orb_largest_m_bound(B, M, P)), nt = tr * (tr + 1) / 2;
-  NQ_TRY(bd_check_grid("nq_orb_bond_backward", B, nt));
+  const int nt = tr * (tr + 1) / 2;
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, out_gS ? (out_gD ? "orb_bond_backward_two" : "orb_bond_backward_s") : "orb_bond_backward_one");
   const OrbArgs a = orb_args(state, B, M, P);

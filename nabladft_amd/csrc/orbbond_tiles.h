@@ -1,6 +1,6 @@
 // What the bond-order kernels (orbbond.hip) and the Löwdin kernels (orblowdin.hip) share: operand tiles whose staging orientation is chosen at run time, the
-// product loop over them, the workgroup -> (molecule, tile) map that reads the layout of the state alone, and the host-side check of the grid.  Header-only,
-// every function static or __forceinline__ (each file keeps its own copy and its own flags); orbbond.hip's header comment describes the orientation rule.
+// product loop over them.  (The workgroup -> (molecule, tile) map that reads the layout of the state alone and the host-side check of the grid, which began
+// here, are orb_tile_mol<ORB_HDR_DIMS> and orb_check_launch of orbstate.h.)  Shared by orbcomm.hip and orbfrontier.hip too.  Header-only, every function static or __forceinline__ (each file keeps its own copy and its own flags); orbbond.hip's header comment describes the orientation rule.
 #pragma once
 #include "orbresp_tiles.h"
 
@@ -97,29 +97,4 @@ __device__ __forceinline__ void bd_gemm(const BdOperand& A1, const BdOperand& B1
       }
     }
   }
-}
-
-// ---- which molecule a workgroup serves: the layout of the state alone; false: exit (uniform over the workgroup) ------------------------------------------------
-struct BdMol {
-  int b, t, m, o0;
-  long long base;
-  bool failed;
-};
-
-__device__ __forceinline__ bool bd_mol(const OrbArgs& a, int per, BdMol& q) {
-  if (!orb_dims_ok(a)) return false;
-  q.b = blockIdx.x / per;
-  q.t = blockIdx.x - q.b * per;
-  if (q.b >= a.B) return false;
-  q.o0 = a.orb_ptr[q.b];
-  q.m = a.orb_ptr[q.b + 1] - q.o0;
-  q.base = a.pack_ptr[q.b];
-  if (q.m < 1 || q.m > NQ_ORB_MAX_M || q.o0 < 0 || q.o0 + q.m > a.M || q.base < 0 || q.base + (long long)q.m * q.m > a.P) return false;
-  q.failed = a.status[q.b] != 0;
-  return true;
-}
-
-static int bd_check_grid(const char* who, int32_t B, long long per) {
-  if ((long long)B * per > INT_MAX) return nq_fail(NQ_ERR_ARG, "%s: B=%d molecules of up to %lld workgroups exceed the grid", who, B, per);
-  return NQ_OK;
 }

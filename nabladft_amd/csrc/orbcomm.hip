@@ -35,8 +35,8 @@
 __global__ __launch_bounds__(NQ_RS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_orb_comm_product(OrbArgs a, int nt, const double* Xs, int x_anti, const double* Ys,
                                                                                                         double alpha, double* out) {
   __shared__ double lds[4 * NQ_RS_TILE];
-  BdMol q;
-  if (!bd_mol(a, nt, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, nt, q)) return;
   const int m = q.m;
   if (q.t >= orb_tile_count(m)) return;                        // uniform
   int ti, tj;
@@ -76,64 +76,14 @@ __global__ __launch_bounds__(NQ_RS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))
 // ---- out = (G - G^T) / 2 ------------------------------------------------------------------------------------------------------------------------------------------------
 // one workgroup per (molecule, lower-triangle 64 x 64 tile): the transposed tile comes through LDS, so that both global reads and both stores run along rows
 __global__ __launch_bounds__(NQ_RS_NT) void k_orb_comm_antisymmetrize(OrbArgs a, int nt, const double* G, double* out) {
-  __shared__ double tile[NQ_ORB_TILE][NQ_ORB_TILE + 1];
-  BdMol q;
-  if (!bd_mol(a, nt, q)) return;
-  const int m = q.m;
-  if (q.t >= orb_tile_count(m)) return;                        // uniform
-  int ti, tj;
-  orb_tile_decode(q.t, &ti, &tj);
-  const int i0 = ti * NQ_ORB_TILE, j0 = tj * NQ_ORB_TILE;
-  const double* Gb = G + q.base;
-  double* Z = out + q.base;
-  const double nan = nq_nan_f64();
-  constexpr int PER = NQ_ORB_TILE * NQ_ORB_TILE / NQ_RS_NT;
-  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {    // tile[r][c] = G[j0 + r][i0 + c]: the mirror image of this workgroup's tile
-    const int r = e >> 6, c = e & 63;
-    tile[r][c] = (j0 + r < m && i0 + c < m) ? Gb[(long long)(j0 + r) * m + i0 + c] : 0.0;
-  }
-  __syncthreads();
-  double v[PER];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int e = threadIdx.x + k * NQ_RS_NT, r = e >> 6, c = e & 63;
-    const int i = i0 + r, j = j0 + c;
-    v[k] = 0.0;
-    if (i < m && j <= i) {
-      v[k] = q.failed ? nan : (i == j ? 0.0 : 0.5 * (Gb[(long long)i * m + j] - tile[c][r]));
-      Z[(long long)i * m + j] = v[k];
-    }
-  }
-  __syncthreads();                                             // the mirror image has been consumed
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int e = threadIdx.x + k * NQ_RS_NT;
-    tile[e >> 6][e & 63] = v[k];
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {    // out[j0 + r][i0 + c] = minus the value of (i0 + c, j0 + r), strictly above the diagonal
-    const int r = e >> 6, c = e & 63;
-    const int j = j0 + r, i = i0 + c;
-    if (i < m && j < i) Z[(long long)j * m + i] = 0.0 - tile[c][r];          // exact; equal entries give +0.0 on both sides, as (G_ji - G_ij) / 2 does
-  }
+  orb_symmetrize_kernel<true, false>(a, nt, G, out);
 }
 
 // ---- sum R_ij^2 and max |R_ij| ------------------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double cm_block_max(double v, double* red) {
-  v = nq_wave_max_f64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = red[0];
-#pragma unroll
-  for (int w = 1; w < NQ_ORB_NW; ++w) r = fmax(r, red[w]);
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_comm_norms(OrbArgs a, const double* R, double* out_sumsq, double* out_maxabs) {
   __shared__ double red[NQ_ORB_NW];
-  BdMol q;
-  if (!bd_mol(a, 1, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, 1, q)) return;
   const int tid = threadIdx.x;
   const double nan = nq_nan_f64();
   if (q.failed) {
@@ -153,7 +103,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_comm_norms(OrbArgs a, const d
     mx = fmax(fmax(mx, fmax(fabs(v0), fabs(v1))), fmax(fabs(v2), fabs(v3)));
   }
   const double sum = orb_block_sum((s0 + s1) + (s2 + s3), red);
-  const double top = cm_block_max(mx, red);
+  const double top = orb_block_max(mx, red);
   if (tid == 0) {
     out_sumsq[q.b] = sum;
     out_maxabs[q.b] = sum != sum ? nan : top;                  // fmax drops a NaN entry, the sum keeps it
@@ -164,12 +114,12 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_comm_norms(OrbArgs a, const d
 extern "C" {
 
 int nq_orb_comm_product(void* state, int32_t B, int32_t M, int64_t P, const double* X, int32_t x_anti, const double* Y, double alpha, double* out, void* stream) {
-  if (!state || !X || !Y || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_product: null argument");
+  int tr = 0;
+  NQ_TRY(orb_check_launch("nq_orb_comm_product", state, B, M, P, ORB_GRID_LOWER, &tr));
+  if (!X || !Y || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_product: null argument");
   if (x_anti != 0 && x_anti != 1) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_product: x_anti=%d is neither 0 (X symmetric) nor 1 (X antisymmetric)", x_anti);
   if (out == X || out == Y) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_product: the output must not be an operand");
-  NQ_TRY(orb_check_dims(B, M, P));
-  const int tr = orb_tile_rows(orb_largest_m_bound(B, M, P)), nt = tr * (tr + 1) / 2;
-  NQ_TRY(bd_check_grid("nq_orb_comm_product", B, nt));
+  const int nt = tr * (tr + 1) / 2;
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, x_anti ? "orb_comm_product_anti" : "orb_comm_product");
   hipLaunchKernelGGL(k_orb_comm_product, dim3(B * nt), dim3(NQ_RS_NT), 0, st, orb_args(state, B, M, P), nt, X, x_anti, Y, alpha, out);
@@ -178,11 +128,11 @@ int nq_orb_comm_product(void* state, int32_t B, int32_t M, int64_t P, const doub
 }
 
 int nq_orb_comm_antisymmetrize(void* state, int32_t B, int32_t M, int64_t P, const double* G, double* out, void* stream) {
-  if (!state || !G || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_antisymmetrize: null argument");
+  int tr = 0;
+  NQ_TRY(orb_check_launch("nq_orb_comm_antisymmetrize", state, B, M, P, ORB_GRID_LOWER, &tr));
+  if (!G || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_antisymmetrize: null argument");
   if (out == G) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_antisymmetrize: the output must not be the operand");
-  NQ_TRY(orb_check_dims(B, M, P));
-  const int tr = orb_tile_rows(orb_largest_m_bound(B, M, P)), nt = tr * (tr + 1) / 2;
-  NQ_TRY(bd_check_grid("nq_orb_comm_antisymmetrize", B, nt));
+  const int nt = tr * (tr + 1) / 2;
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_comm_antisymmetrize");
   hipLaunchKernelGGL(k_orb_comm_antisymmetrize, dim3(B * nt), dim3(NQ_RS_NT), 0, st, orb_args(state, B, M, P), nt, G, out);
@@ -191,10 +141,10 @@ int nq_orb_comm_antisymmetrize(void* state, int32_t B, int32_t M, int64_t P, con
 }
 
 int nq_orb_comm_norms(void* state, int32_t B, int32_t M, int64_t P, const double* R, double* out_sumsq, double* out_maxabs, void* stream) {
-  if (!state || !R || !out_sumsq || !out_maxabs) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_norms: null argument");
+  NQ_TRY(orb_check_launch("nq_orb_comm_norms", state, B, M, P, ORB_GRID_MOL));
+  if (!R || !out_sumsq || !out_maxabs) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_norms: null argument");
   if (out_sumsq == out_maxabs) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_norms: the outputs must be arrays of their own");
   if (out_sumsq == R || out_maxabs == R) return nq_fail(NQ_ERR_ARG, "nq_orb_comm_norms: an output must not be the operand");
-  NQ_TRY(orb_check_dims(B, M, P));
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_comm_norms");
   hipLaunchKernelGGL(k_orb_comm_norms, dim3(B), dim3(NQ_ORB_NT), 0, st, orb_args(state, B, M, P), R, out_sumsq, out_maxabs);

@@ -314,8 +314,8 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_front_lanczos(OrbArgs a, const do
 // ---- out_gH = sum_side g c c^T, out_gS = -sum_side g eps c c^T; one workgroup per 64 x 64 tile --------------------------------------------------------------
 __global__ __launch_bounds__(NQ_RS_NT) void k_front_gram(OrbArgs a, int tr, const double* g, const double* eps, const double* coef, const int* conv, double* out_gH,
                                                          double* out_gS) {
-  BdMol q;
-  if (!bd_mol(a, tr * tr, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, tr * tr, q)) return;
   const int m = q.m, ti = q.t / tr, tj = q.t - ti * tr;
   if (ti * NQ_ORB_TILE >= m || tj * NQ_ORB_TILE >= m) return;
   const int c0 = conv[2 * q.b], c1 = conv[2 * q.b + 1];
@@ -350,15 +350,13 @@ extern "C" {
 int nq_orb_front_lanczos(void* state, int32_t B, int32_t M, int64_t P, const double* Ht, const double* X, const double* shift, const int32_t* n_occ,
                          const double* W_or_null, int32_t k_max, double tol, double* V, const int64_t* vptr, double* eps, double* vec, double* coef, int32_t* iters,
                          double* res, int32_t* conv, void* stream) {
-  if (!state || !Ht || !X || !shift || !V || !vptr || !eps || !vec || !coef || !iters || !res || !conv)
-    return nq_fail(NQ_ERR_ARG, "nq_orb_front_lanczos: null argument");
+  NQ_TRY(orb_check_launch("nq_orb_front_lanczos", state, B, M, P, ORB_GRID_MOL, nullptr, 2));
+  if (!Ht || !X || !shift || !V || !vptr || !eps || !vec || !coef || !iters || !res || !conv) return nq_fail(NQ_ERR_ARG, "nq_orb_front_lanczos: null argument");
   if (!n_occ) return nq_fail(NQ_ERR_ARG, "nq_orb_front_lanczos: n_occ is missing");
   if (k_max < 1 || k_max > NQ_FR_MAX_K) return nq_fail(NQ_ERR_ARG, "nq_orb_front_lanczos: k_max=%d outside 1..%d", k_max, NQ_FR_MAX_K);
   if (!(tol > 0.0) || !(tol < 1.0)) return nq_fail(NQ_ERR_ARG, "nq_orb_front_lanczos: tol=%g outside (0, 1)", tol);
   if (vec == coef || eps == res || (const double*)V == Ht || (const double*)V == X || (W_or_null && (const double*)V == W_or_null) || vec == V || coef == V)
     return nq_fail(NQ_ERR_ARG, "nq_orb_front_lanczos: the outputs and the workspace must be different arrays");
-  NQ_TRY(orb_check_dims(B, M, P));
-  NQ_TRY(bd_check_grid("nq_orb_front_lanczos", B, 2));
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_front_lanczos");
   hipLaunchKernelGGL(k_front_lanczos, dim3(2 * B), dim3(NQ_ORB_NT), 0, st, orb_args(state, B, M, P), Ht, X, shift, (const int*)n_occ, W_or_null, (int)k_max, tol, V,
@@ -369,13 +367,12 @@ int nq_orb_front_lanczos(void* state, int32_t B, int32_t M, int64_t P, const dou
 
 int nq_orb_front_gram(void* state, int32_t B, int32_t M, int64_t P, const double* g, const double* eps_or_null, const double* coef, const int32_t* conv, double* out_gH,
                       double* out_gS_or_null, void* stream) {
-  if (!state || !g || !coef || !conv || !out_gH) return nq_fail(NQ_ERR_ARG, "nq_orb_front_gram: null argument");
+  int tr = 0;
+  NQ_TRY(orb_check_launch("nq_orb_front_gram", state, B, M, P, ORB_GRID_SQUARE, &tr));
+  if (!g || !coef || !conv || !out_gH) return nq_fail(NQ_ERR_ARG, "nq_orb_front_gram: null argument");
   if (out_gS_or_null && !eps_or_null) return nq_fail(NQ_ERR_ARG, "nq_orb_front_gram: the second output out_gS needs the levels eps");
   if (out_gH == out_gS_or_null || out_gH == coef || out_gH == g || (out_gS_or_null && (out_gS_or_null == coef || out_gS_or_null == g)))
     return nq_fail(NQ_ERR_ARG, "nq_orb_front_gram: the outputs must be different arrays from each other and from the inputs");
-  NQ_TRY(orb_check_dims(B, M, P));
-  const int tr = orb_tile_rows(orb_largest_m_bound(B, M, P));
-  NQ_TRY(bd_check_grid("nq_orb_front_gram", B, (long long)tr * tr));
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_front_gram");
   hipLaunchKernelGGL(k_front_gram, dim3(B * tr * tr), dim3(NQ_RS_NT), 0, st, orb_args(state, B, M, P), tr, g, eps_or_null, coef, (const int*)conv, out_gH,

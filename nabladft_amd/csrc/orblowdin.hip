@@ -30,25 +30,6 @@
 // Compiled with -ffp-contract=off like its neighbours: K is a sum, a product and a division as written.
 #include "orbbond_tiles.h"
 
-// the molecule of a workgroup of the one-workgroup-per-molecule kernel and of the row-owning product; false: exit (uniform)
-__device__ __forceinline__ bool lw_block_mol(const OrbArgs& a, int b, int& o0, int& m, long long& base) {
-  o0 = a.orb_ptr[b];
-  m = a.orb_ptr[b + 1] - o0;
-  base = a.pack_ptr[b];
-  return m >= 1 && m <= NQ_ORB_MAX_M && o0 >= 0 && o0 + m <= a.M && base >= 0 && base + (long long)m * m <= a.P;
-}
-
-__device__ __forceinline__ double lw_block_max(double v, double* red) {
-  v = nq_wave_max_f64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = red[0];
-#pragma unroll
-  for (int w = 1; w < NQ_ORB_NW; ++w) r = fmax(r, red[w]);
-  __syncthreads();
-  return r;
-}
-
 // a level of S the square roots cannot be taken of: not finite, or not positive (NaN fails the comparison)
 __device__ __forceinline__ bool lw_bad_level(double s) { return !(s > 0.0) || !isfinite(s); }
 
@@ -60,7 +41,8 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_low_weights(OrbArgs a, double
   if (b >= a.B) return;
   int o0, m;
   long long base;
-  if (!lw_block_mol(a, b, o0, m, base)) return;                  // uniform: a state overwritten since nq_orb_init
+  bool failed;
+  if (!orb_mol(a, b, o0, m, base, failed)) return;               // uniform: a state overwritten since nq_orb_init
   // at most two levels per thread (m <= 1024 = 2 x 512)
   const int k0 = tid, k1 = tid + NQ_ORB_NT;
   const bool h0 = k0 < m, h1 = k1 < m;
@@ -69,14 +51,14 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_low_weights(OrbArgs a, double
   const double inf = __longlong_as_double(0x7ff0000000000000LL);
   double bad = (lw_bad_level(s0) || lw_bad_level(s1)) ? 1.0 : 0.0;
   bad = orb_block_sum(bad, red);                                 // a count: exact, the same bits in every thread
-  if (a.status[b] != 0 || bad != 0.0) {
+  if (failed || bad != 0.0) {
     if (h0) out_half[o0 + k0] = nan, out_inv_half[o0 + k0] = nan;
     if (h1) out_half[o0 + k1] = nan, out_inv_half[o0 + k1] = nan;
     if (tid == 0) out_cond[b] = nan, out_info[b] = 1;
     return;
   }
-  const double smax = lw_block_max(fmax(h0 ? s0 : -inf, h1 ? s1 : -inf), red);
-  const double smin = -lw_block_max(fmax(h0 ? -s0 : -inf, h1 ? -s1 : -inf), red);
+  const double smax = orb_block_max(fmax(h0 ? s0 : -inf, h1 ? s1 : -inf), red);
+  const double smin = -orb_block_max(fmax(h0 ? -s0 : -inf, h1 ? -s1 : -inf), red);
   if (h0) {
     const double r = sqrt(s0);
     out_half[o0 + k0] = r;
@@ -93,8 +75,8 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_low_weights(OrbArgs a, double
 // ---- Y = M X ----------------------------------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NQ_RS_NT) void k_orb_low_product(OrbArgs a, int tr, const void* Ms, int m_f64, const double* Xs, double* out) {
   __shared__ double lds[2 * NQ_RS_TILE];
-  BdMol q;
-  if (!bd_mol(a, tr * tr, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, tr * tr, q)) return;
   const int m = q.m, ti = q.t / tr, tj = q.t - ti * tr;
   const int i0 = ti * NQ_ORB_TILE, j0 = tj * NQ_ORB_TILE;
   if (i0 >= m || j0 >= m) return;                              // uniform
@@ -122,8 +104,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_orb_low_product(OrbArgs a, int tr,
 __global__ __launch_bounds__(NQ_RS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_orb_low_symprod(OrbArgs a, int nt, const double* E, const double* Xs, int side, double alpha,
                                                                                                        double* out) {
   __shared__ double lds[4 * NQ_RS_TILE];
-  BdMol q;
-  if (!bd_mol(a, nt, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, nt, q)) return;
   const int m = q.m;
   if (q.t >= orb_tile_count(m)) return;                        // uniform
   int ti, tj;
@@ -158,60 +140,17 @@ __global__ __launch_bounds__(NQ_RS_NT) __attribute__((amdgpu_waves_per_eu(2, 2))
 
 // ---- out = (G + G^T) / 2 ------------------------------------------------------------------------------------------------------------------------------------------------
 // one workgroup per (molecule, lower-triangle 64 x 64 tile): the transposed tile comes through LDS, so that both global reads and both stores run along rows
-__global__ __launch_bounds__(NQ_RS_NT) void k_orb_low_symmetrize(OrbArgs a, int nt, const double* G, double* out) {
-  __shared__ double tile[NQ_ORB_TILE][NQ_ORB_TILE + 1];
-  BdMol q;
-  if (!bd_mol(a, nt, q)) return;
-  const int m = q.m;
-  if (q.t >= orb_tile_count(m)) return;                        // uniform
-  int ti, tj;
-  orb_tile_decode(q.t, &ti, &tj);
-  const int i0 = ti * NQ_ORB_TILE, j0 = tj * NQ_ORB_TILE;
-  const double* Gb = G + q.base;
-  double* Z = out + q.base;
-  const double nan = nq_nan_f64();
-  constexpr int PER = NQ_ORB_TILE * NQ_ORB_TILE / NQ_RS_NT;
-  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {    // tile[r][c] = G[j0 + r][i0 + c]: the mirror image of this workgroup's tile
-    const int r = e >> 6, c = e & 63;
-    tile[r][c] = (j0 + r < m && i0 + c < m) ? Gb[(long long)(j0 + r) * m + i0 + c] : 0.0;
-  }
-  __syncthreads();
-  double v[PER];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int e = threadIdx.x + k * NQ_RS_NT, r = e >> 6, c = e & 63;
-    const int i = i0 + r, j = j0 + c;
-    v[k] = 0.0;
-    if (i < m && j <= i) {
-      v[k] = q.failed ? nan : 0.5 * (Gb[(long long)i * m + j] + tile[c][r]);
-      Z[(long long)i * m + j] = v[k];
-    }
-  }
-  __syncthreads();                                             // the mirror image has been consumed
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int e = threadIdx.x + k * NQ_RS_NT;
-    tile[e >> 6][e & 63] = v[k];
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {    // out[j0 + r][i0 + c] = the value of (i0 + c, j0 + r), strictly above the diagonal
-    const int r = e >> 6, c = e & 63;
-    const int j = j0 + r, i = i0 + c;
-    if (i < m && j < i) Z[(long long)j * m + i] = tile[c][r];
-  }
-}
+__global__ __launch_bounds__(NQ_RS_NT) void k_orb_low_symmetrize(OrbArgs a, int nt, const double* G, double* out) { orb_symmetrize_kernel<false, false>(a, nt, G, out); }
 
 // ---- A_out = K o (U^T T) ------------------------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NQ_RS_NT) void k_orb_low_mo(OrbArgs a, int tr, int kind, const double* T, double* A_out) {
   __shared__ double lds[3 * NQ_RS_TILE];
   __shared__ int flagged;
-  if (!orb_kind_ok(a, false)) return;
-  const int b = blockIdx.x / tr, t = blockIdx.x - b * tr;
-  if (b >= a.B) return;
-  int o0, m;
-  long long base;
-  if (!lw_block_mol(a, b, o0, m, base)) return;
-  const int i0 = t * NQ_ORB_TILE;                              // the workgroup's 64 rows of W; it walks the columns itself
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_SOLVE>(a, tr, q)) return;
+  const int b = q.b, o0 = q.o0, m = q.m;
+  const long long base = q.base;
+  const int i0 = q.t * NQ_ORB_TILE;                              // the workgroup's 64 rows of W; it walks the columns itself
   if (i0 >= m) return;                                         // uniform
   const double* Ct = a.coeff + base;
   const double* eps = a.eps + o0;
@@ -221,7 +160,7 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_orb_low_mo(OrbArgs a, int tr, int 
   for (int k = threadIdx.x; k < m; k += NQ_RS_NT) mine = mine || lw_bad_level(eps[k]);
   if (mine) flagged = 1;                                       // every writer stores the same value
   __syncthreads();
-  const bool failed = a.status[b] != 0 || flagged != 0;        // what k_orb_low_weights reports as info 1
+  const bool failed = q.failed || flagged != 0;              // what k_orb_low_weights reports as info 1
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lc = lane & 15, lk = lane >> 4;
   const double nan = nq_nan_f64();
   double ai[4];                                                // this thread's four rows
@@ -257,9 +196,9 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_orb_low_mo(OrbArgs a, int tr, int 
 extern "C" {
 
 int nq_orb_low_weights(void* state, int32_t B, int32_t M, int64_t P, double* out_half, double* out_inv_half, double* out_cond, int32_t* out_info, void* stream) {
-  if (!state || !out_half || !out_inv_half || !out_cond || !out_info) return nq_fail(NQ_ERR_ARG, "nq_orb_low_weights: null argument");
+  NQ_TRY(orb_check_launch("nq_orb_low_weights", state, B, M, P, ORB_GRID_MOL));
+  if (!out_half || !out_inv_half || !out_cond || !out_info) return nq_fail(NQ_ERR_ARG, "nq_orb_low_weights: null argument");
   if (out_half == out_inv_half) return nq_fail(NQ_ERR_ARG, "nq_orb_low_weights: the outputs must be arrays of their own");
-  NQ_TRY(orb_check_dims(B, M, P));
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_low_weights");
   hipLaunchKernelGGL(k_orb_low_weights, dim3(B), dim3(NQ_ORB_NT), 0, st, orb_args(state, B, M, P), out_half, out_inv_half, out_cond, (int*)out_info);
@@ -268,11 +207,10 @@ int nq_orb_low_weights(void* state, int32_t B, int32_t M, int64_t P, double* out
 }
 
 int nq_orb_low_product(void* state, int32_t B, int32_t M, int64_t P, const void* Msym, int32_t m_f64, const double* X, double* out_Y, void* stream) {
-  if (!state || !Msym || !X || !out_Y) return nq_fail(NQ_ERR_ARG, "nq_orb_low_product: null argument");
+  int tr = 0;
+  NQ_TRY(orb_check_launch("nq_orb_low_product", state, B, M, P, ORB_GRID_SQUARE, &tr));
+  if (!Msym || !X || !out_Y) return nq_fail(NQ_ERR_ARG, "nq_orb_low_product: null argument");
   if ((const void*)out_Y == Msym || out_Y == X) return nq_fail(NQ_ERR_ARG, "nq_orb_low_product: the output must not be an operand");
-  NQ_TRY(orb_check_dims(B, M, P));
-  const int tr = orb_tile_rows(orb_largest_m_bound(B, M, P));
-  NQ_TRY(bd_check_grid("nq_orb_low_product", B, (long long)tr * tr));
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_low_product");
   hipLaunchKernelGGL(k_orb_low_product, dim3(B * tr * tr), dim3(NQ_RS_NT), 0, st, orb_args(state, B, M, P), tr, Msym, m_f64, X, out_Y);
@@ -281,12 +219,12 @@ int nq_orb_low_product(void* state, int32_t B, int32_t M, int64_t P, const void*
 }
 
 int nq_orb_low_symprod(void* state, int32_t B, int32_t M, int64_t P, const double* E, const double* X, int32_t side, double alpha, double* out, void* stream) {
-  if (!state || !E || !X || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_low_symprod: null argument");
+  int tr = 0;
+  NQ_TRY(orb_check_launch("nq_orb_low_symprod", state, B, M, P, ORB_GRID_LOWER, &tr));
+  if (!E || !X || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_low_symprod: null argument");
   if (side != 0 && side != 1) return nq_fail(NQ_ERR_ARG, "nq_orb_low_symprod: side=%d is neither 0 (sym(X E)) nor 1 (sym(E X))", side);
   if (out == E || out == X) return nq_fail(NQ_ERR_ARG, "nq_orb_low_symprod: the output must not be an operand");
-  NQ_TRY(orb_check_dims(B, M, P));
-  const int tr = orb_tile_rows(orb_largest_m_bound(B, M, P)), nt = tr * (tr + 1) / 2;
-  NQ_TRY(bd_check_grid("nq_orb_low_symprod", B, nt));
+  const int nt = tr * (tr + 1) / 2;
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, side == 0 ? "orb_low_symprod_left" : "orb_low_symprod_right");
   hipLaunchKernelGGL(k_orb_low_symprod, dim3(B * nt), dim3(NQ_RS_NT), 0, st, orb_args(state, B, M, P), nt, E, X, side, alpha, out);
@@ -295,11 +233,11 @@ int nq_orb_low_symprod(void* state, int32_t B, int32_t M, int64_t P, const doubl
 }
 
 int nq_orb_low_symmetrize(void* state, int32_t B, int32_t M, int64_t P, const double* G, double* out, void* stream) {
-  if (!state || !G || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_low_symmetrize: null argument");
+  int tr = 0;
+  NQ_TRY(orb_check_launch("nq_orb_low_symmetrize", state, B, M, P, ORB_GRID_LOWER, &tr));
+  if (!G || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_low_symmetrize: null argument");
   if (out == G) return nq_fail(NQ_ERR_ARG, "nq_orb_low_symmetrize: the output must not be the operand");
-  NQ_TRY(orb_check_dims(B, M, P));
-  const int tr = orb_tile_rows(orb_largest_m_bound(B, M, P)), nt = tr * (tr + 1) / 2;
-  NQ_TRY(bd_check_grid("nq_orb_low_symmetrize", B, nt));
+  const int nt = tr * (tr + 1) / 2;
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_low_symmetrize");
   hipLaunchKernelGGL(k_orb_low_symmetrize, dim3(B * nt), dim3(NQ_RS_NT), 0, st, orb_args(state, B, M, P), nt, G, out);
@@ -308,12 +246,11 @@ int nq_orb_low_symmetrize(void* state, int32_t B, int32_t M, int64_t P, const do
 }
 
 int nq_orb_low_mo(void* state, int32_t B, int32_t M, int64_t P, int32_t kind, const double* T, double* A_out, void* stream) {
-  if (!state || !T || !A_out) return nq_fail(NQ_ERR_ARG, "nq_orb_low_mo: null argument");
+  int tr = 0;
+  NQ_TRY(orb_check_launch("nq_orb_low_mo", state, B, M, P, ORB_GRID_ROWS, &tr));
+  if (!T || !A_out) return nq_fail(NQ_ERR_ARG, "nq_orb_low_mo: null argument");
   if (kind != 0 && kind != 1) return nq_fail(NQ_ERR_ARG, "nq_orb_low_mo: kind=%d is neither 0 (S^(1/2)) nor 1 (S^(-1/2))", kind);
   if (A_out == T) return nq_fail(NQ_ERR_ARG, "nq_orb_low_mo: the output must not be the operand");
-  NQ_TRY(orb_check_dims(B, M, P));
-  const int tr = orb_tile_rows(orb_largest_m_bound(B, M, P));
-  NQ_TRY(bd_check_grid("nq_orb_low_mo", B, tr));
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, kind == 0 ? "orb_low_mo_half" : "orb_low_mo_inv_half");
   hipLaunchKernelGGL(k_orb_low_mo, dim3(B * tr), dim3(NQ_RS_NT), 0, st, orb_args(state, B, M, P), tr, kind, T, A_out);

@@ -41,25 +41,7 @@
 #define NQ_PUR_MAX_ITER 10000
 enum { PC_EMIN = 0, PC_EMAX, PC_KIND, PC_NOCC, PC_T, PC_T2, PC_SLOT = 8 };
 
-struct PurMol {
-  int b, t, m;
-  long long base;
-};
-
-// which molecule and tile a workgroup serves; false: exit (uniform over the workgroup)
-// (KIND: the kernel reads X, Ht or Y from the state; the others use its layout only)
-template <bool KIND>
-__device__ __forceinline__ bool pur_mol(const OrbArgs& a, int nt, PurMol& q) {
-  if (!(KIND ? orb_kind_ok(a, true) : orb_dims_ok(a))) return false;
-  q.b = blockIdx.x / nt;
-  q.t = blockIdx.x - q.b * nt;
-  if (q.b >= a.B) return false;
-  const int o0 = a.orb_ptr[q.b];
-  q.m = a.orb_ptr[q.b + 1] - o0;
-  q.base = a.pack_ptr[q.b];
-  return !(q.m < 1 || q.m > NQ_ORB_MAX_M || o0 < 0 || o0 + q.m > a.M || q.base < 0 || q.base + (long long)q.m * q.m > a.P);
-}
-
+// KIND kernels read X, Ht or Y from the state (orb_tile_mol<ORB_HDR_PURIFY>); the others use its layout only (ORB_HDR_DIMS)
 __device__ __forceinline__ bool pur_branch(int entry) { return entry == 1 || entry == 2; }
 __device__ __forceinline__ double pur_x0(double h, bool diag, double e_min, double e_max) { return ((diag ? e_max : 0.0) - h) / (e_max - e_min); }
 
@@ -122,8 +104,8 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_pur_orth(OrbArgs a, const void* S
 
 // ---- out = alpha A, symmetric: the lower triangle mirrored (sym = 0) or (A + A^T) / 2 (sym = 1); one workgroup per 64 x 64 tile --------------------------------
 __global__ __launch_bounds__(NQ_RS_NT) void k_pur_load(OrbArgs a, int tr, const void* A, int a_f64, int sym, double alpha, double* out) {
-  PurMol q;
-  if (!pur_mol<false>(a, tr * tr, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, tr * tr, q)) return;
   const int m = q.m, ti = q.t / tr, tj = q.t - ti * tr;
   if (ti * NQ_ORB_TILE >= m || tj * NQ_ORB_TILE >= m) return;
   for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {
@@ -145,8 +127,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_pur_prod(OrbArgs a, int nt, int tr
                                                        double* out) {
   __shared__ double lds[3 * NQ_RS_TILE];
   constexpr bool LOWER = MODE == 1 || MODE == 3;
-  PurMol q;
-  if (!pur_mol<false>(a, nt, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, nt, q)) return;
   const int m = q.m;
   int ti, tj;
   if (LOWER) {
@@ -264,8 +246,8 @@ template <bool RESP>
 __global__ __launch_bounds__(NQ_RS_NT) void k_pur_square(OrbArgs a, int nt, int k, int max_iter, double* ctl_all, const int* log_all, const double* X1all,
                                                          double* Qall) {
   __shared__ double lds[3 * NQ_RS_TILE];
-  PurMol q;
-  if (!pur_mol<true>(a, nt, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_PURIFY>(a, nt, q)) return;
   const int m = q.m;
   if (q.t >= orb_tile_count(m) || a.status[q.b] != 0) return;
   const int* log = log_all + (long long)q.b * max_iter;
@@ -330,8 +312,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_pur_square(OrbArgs a, int nt, int 
 // ---- the decision and the elementwise update; one workgroup per 64 x 64 tile of X --------------------------------------------------------------------------------------
 template <bool RESP>
 __global__ __launch_bounds__(NQ_RS_NT) void k_pur_update(OrbArgs a, int tr, int k, int max_iter, double* ctl_all, int* log_all, double* X1all, const double* Qall) {
-  PurMol q;
-  if (!pur_mol<true>(a, tr * tr, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_PURIFY>(a, tr * tr, q)) return;
   const int m = q.m, ti = q.t / tr, tj = q.t - ti * tr;
   if (ti * NQ_ORB_TILE >= m || tj * NQ_ORB_TILE >= m || a.status[q.b] != 0) return;
   int* log = log_all + (long long)q.b * max_iter;
@@ -372,8 +354,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_pur_update(OrbArgs a, int tr, int 
 }
 
 __global__ __launch_bounds__(NQ_RS_NT) void k_pur_finish(OrbArgs a, int tr, int max_iter, const int* log_all) {
-  PurMol q;
-  if (!pur_mol<true>(a, tr * tr, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_PURIFY>(a, tr * tr, q)) return;
   const int m = q.m, ti = q.t / tr, tj = q.t - ti * tr;
   if (ti * NQ_ORB_TILE >= m || tj * NQ_ORB_TILE >= m) return;
   if (!pur_branch(log_all[(long long)q.b * max_iter + max_iter - 1])) return;   // the log is zero unless the molecule iterated
@@ -387,8 +369,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_pur_finish(OrbArgs a, int tr, int 
 }
 
 __global__ __launch_bounds__(NQ_RS_NT) void k_pur_resp_init(OrbArgs a, int tr, int max_iter, const double* ctl_all, const double* Gt, double* X1all) {
-  PurMol q;
-  if (!pur_mol<true>(a, tr * tr, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_PURIFY>(a, tr * tr, q)) return;
   const int m = q.m, ti = q.t / tr, tj = q.t - ti * tr;
   if (ti * NQ_ORB_TILE >= m || tj * NQ_ORB_TILE >= m) return;
   const double* ctl = ctl_all + (long long)q.b * (NQ_PUR_CTL + max_iter);
@@ -410,14 +392,6 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_pur_resp_init(OrbArgs a, int tr, i
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------------------------------
-static int pur_check(const char* who, const void* state, int32_t B, int32_t M, int64_t P, int* tr) {
-  if (!state) return nq_fail(NQ_ERR_ARG, "%s: null argument", who);
-  NQ_TRY(orb_check_dims(B, M, P));
-  *tr = orb_tile_rows(orb_largest_m_bound(B, M, P));
-  if ((long long)B * *tr * *tr > INT_MAX) return nq_fail(NQ_ERR_ARG, "%s: B=%d molecules of up to %d tiles exceed the grid", who, B, *tr * *tr);
-  return NQ_OK;
-}
-
 static int pur_check_iter(const char* who, int32_t k, int32_t max_iter) {
   if (max_iter < 1 || max_iter > NQ_PUR_MAX_ITER) return nq_fail(NQ_ERR_ARG, "%s: max_iter=%d outside 1..%d", who, max_iter, NQ_PUR_MAX_ITER);
   if (k < 0 || k >= max_iter) return nq_fail(NQ_ERR_ARG, "%s: iteration k=%d outside 0..max_iter-1=%d", who, k, max_iter - 1);
@@ -450,7 +424,7 @@ extern "C" {
 
 int nq_orb_pur_orthogonalizer(void* state, int32_t B, int32_t M, int64_t P, const void* S, int32_t s_f64, double* Z, void* stream) {
   int tr = 0;
-  NQ_TRY(pur_check("nq_orb_pur_orthogonalizer", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_pur_orthogonalizer", state, B, M, P, ORB_GRID_SQUARE, &tr));
   if (!S || !Z) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_orthogonalizer: null argument");
   if ((const void*)Z == S) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_orthogonalizer: Z must not be S");
   hipStream_t st = (hipStream_t)stream;
@@ -463,7 +437,7 @@ int nq_orb_pur_orthogonalizer(void* state, int32_t B, int32_t M, int64_t P, cons
 int nq_orb_pur_congruence(void* state, int32_t B, int32_t M, int64_t P, const double* Z, int32_t trans, const void* A, int32_t a_f64, int32_t a_sym, double alpha,
                           double* tmp, double* out, void* stream) {
   int tr = 0;
-  NQ_TRY(pur_check("nq_orb_pur_congruence", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_pur_congruence", state, B, M, P, ORB_GRID_SQUARE, &tr));
   if (!A || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_congruence: null argument");
   if (Z && !tmp) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_congruence: the products need the scratch array tmp");
   if (A == (const void*)out || (Z && (tmp == out || A == (const void*)tmp || Z == out || Z == tmp)))
@@ -492,7 +466,7 @@ int nq_orb_pur_congruence(void* state, int32_t B, int32_t M, int64_t P, const do
 int nq_orb_pur_gemm(void* state, int32_t B, int32_t M, int64_t P, const double* A, const double* Bm, const double* C, double alpha, double beta, double* out,
                     void* stream) {
   int tr = 0;
-  NQ_TRY(pur_check("nq_orb_pur_gemm", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_pur_gemm", state, B, M, P, ORB_GRID_SQUARE, &tr));
   if (!A || !Bm || !out) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_gemm: null argument");
   if (out == A || out == Bm) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_gemm: out must not be an operand of the product");
   hipStream_t st = (hipStream_t)stream;
@@ -505,7 +479,7 @@ int nq_orb_pur_gemm(void* state, int32_t B, int32_t M, int64_t P, const double* 
 int nq_orb_pur_init(void* state, int32_t B, int32_t M, int64_t P, const void* Ht, int32_t h_f64, const double* Z, const int32_t* n_occ, int32_t max_iter,
                     double* ctl, int32_t* log, void* stream) {
   int tr = 0;
-  NQ_TRY(pur_check("nq_orb_pur_init", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_pur_init", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(pur_check_iter("nq_orb_pur_init", 0, max_iter));
   if (!n_occ) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_init: n_occ is missing");
   if (!ctl || !log) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_init: null argument");
@@ -520,7 +494,7 @@ int nq_orb_pur_init(void* state, int32_t B, int32_t M, int64_t P, const void* Ht
 
 int nq_orb_pur_step(void* state, int32_t B, int32_t M, int64_t P, int32_t k, int32_t max_iter, double* ctl, int32_t* log, void* stream) {
   int tr = 0;
-  NQ_TRY(pur_check("nq_orb_pur_step", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_pur_step", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(pur_check_iter("nq_orb_pur_step", k, max_iter));
   if (!ctl || !log) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_step: null argument");
   hipStream_t st = (hipStream_t)stream;
@@ -530,7 +504,7 @@ int nq_orb_pur_step(void* state, int32_t B, int32_t M, int64_t P, int32_t k, int
 
 int nq_orb_pur_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, double* ctl, int32_t* log, void* stream) {
   int tr = 0;
-  NQ_TRY(pur_check("nq_orb_pur_run", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_pur_run", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(pur_check_iter("nq_orb_pur_run", 0, max_iter));
   if (!ctl || !log) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_run: null argument");
   hipStream_t st = (hipStream_t)stream;
@@ -544,7 +518,7 @@ int nq_orb_pur_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_ite
 
 int nq_orb_pur_response_init(void* state, int32_t B, int32_t M, int64_t P, const double* Gt, int32_t max_iter, const double* ctl, double* X1, void* stream) {
   int tr = 0;
-  NQ_TRY(pur_check("nq_orb_pur_response_init", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_pur_response_init", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(pur_check_iter("nq_orb_pur_response_init", 0, max_iter));
   if (!Gt || !ctl || !X1) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_response_init: null argument");
   if (Gt == X1) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_response_init: X1 must not be Gt");
@@ -557,7 +531,7 @@ int nq_orb_pur_response_init(void* state, int32_t B, int32_t M, int64_t P, const
 
 int nq_orb_pur_response_step(void* state, int32_t B, int32_t M, int64_t P, int32_t k, int32_t max_iter, const int32_t* log, double* Q, double* X1, void* stream) {
   int tr = 0;
-  NQ_TRY(pur_check("nq_orb_pur_response_step", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_pur_response_step", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(pur_check_iter("nq_orb_pur_response_step", k, max_iter));
   if (!log || !X1) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_response_step: null argument");
   if (!Q) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_response_step: the second input X1 needs the second output Q");
@@ -569,7 +543,7 @@ int nq_orb_pur_response_step(void* state, int32_t B, int32_t M, int64_t P, int32
 
 int nq_orb_pur_response_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, const int32_t* log, double* Q, double* X1, void* stream) {
   int tr = 0;
-  NQ_TRY(pur_check("nq_orb_pur_response_run", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_pur_response_run", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(pur_check_iter("nq_orb_pur_response_run", 0, max_iter));
   if (!log || !X1) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_response_run: null argument");
   if (!Q) return nq_fail(NQ_ERR_ARG, "nq_orb_pur_response_run: the second input X1 needs the second output Q");

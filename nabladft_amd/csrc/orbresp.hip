@@ -4,7 +4,7 @@
 //
 // With Gs = (G + G^T) / 2 for an upstream G = dL/dD, o = the first n_occ orbitals, v = the rest (the state stores C^T: row k of a block = orbital k):
 //
-//   k_orb_resp_sym      Gs                                            packed [m][m], lower-triangle 64 x 64 tiles through LDS, written to both triangles
+//   k_orb_resp_sym      Gs                                            packed [m][m], lower-triangle 64 x 64 tiles through LDS, mirrored (orbresp_tiles.h)
 //   k_orb_resp<1>       T[mu][i]  = sum_nu Gs[nu][mu] Ct[i][nu]       occupied-packed [m][n_o]  (= Gs C_o; nq_orb_resp_project launches both)
 //   k_orb_resp<2>       W[k][i]   = sum_mu Ct[k][mu] T[mu][i]         and its epilogue: k >= n_o: A_H = 4 W / (eps_i - eps_k), A_S = -eps_i A_H;
 //                                                                     k < n_o: A_H = 0, A_S = -2 W          occupied-packed [m][n_o]  (nq_orb_resp_mo)
@@ -38,43 +38,10 @@
 #include "orbresp_tiles.h"
 
 // ---- Gs = (G + G^T) / 2 ---------------------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NQ_RS_NT) void k_orb_resp_sym(OrbArgs a, int nt, const double* G, double* Gs) {
-  __shared__ double tt[NQ_ORB_TILE][NQ_ORB_TILE + 1];
-  if (!orb_dims_ok(a)) return;
-  const int b = blockIdx.x / nt, t = blockIdx.x - b * nt;
-  if (b >= a.B) return;
-  const int o0 = a.orb_ptr[b], m = a.orb_ptr[b + 1] - o0;
-  const long long base = a.pack_ptr[b];
-  if (m < 1 || m > NQ_ORB_MAX_M || base < 0 || base + (long long)m * m > a.P) return;
-  if (t >= orb_tile_count(m)) return;                           // uniform: the barriers below are reached by the whole workgroup or not at all
-  int ti, tj;
-  orb_tile_decode(t, &ti, &tj);
-  const int i0 = ti * NQ_ORB_TILE, j0 = tj * NQ_ORB_TILE;
-  const double* g = G + base;
-  double* out = Gs + base;
-  // rows i0.. of the output: G[i][j] straight from memory, G[j][i] through the transposed tile
-  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {
-    const int r = e >> 6, c = e & 63;
-    tt[r][c] = (j0 + r < m && i0 + c < m) ? g[(long long)(j0 + r) * m + i0 + c] : 0.0;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {
-    const int r = e >> 6, c = e & 63;
-    if (i0 + r < m && j0 + c < m) out[(long long)(i0 + r) * m + j0 + c] = 0.5 * (g[(long long)(i0 + r) * m + j0 + c] + tt[c][r]);
-  }
-  if (ti == tj) return;
-  // rows j0.. of the output, the mirror: the same two numbers in the same order
-  __syncthreads();
-  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {
-    const int r = e >> 6, c = e & 63;
-    tt[r][c] = (i0 + r < m && j0 + c < m) ? g[(long long)(i0 + r) * m + j0 + c] : 0.0;
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {
-    const int r = e >> 6, c = e & 63;
-    if (j0 + r < m && i0 + c < m) out[(long long)(j0 + r) * m + i0 + c] = 0.5 * (tt[c][r] + g[(long long)(j0 + r) * m + i0 + c]);
-  }
-}
+// The tile routine of orbresp_tiles.h.  A failed molecule's Gs stays the finite average: the NaN of its outputs comes from the products that follow.  The range
+// test of the molecule's first orbital that the shared lookup adds to this kernel cannot fail on a state that passed orb_dims_ok (nq_orb_init wrote orb_ptr
+// and pack_ptr together).
+__global__ __launch_bounds__(NQ_RS_NT) void k_orb_resp_sym(OrbArgs a, int nt, const double* G, double* Gs) { orb_symmetrize_kernel<false, true>(a, nt, G, Gs); }
 
 // ---- steps 1 to 3 ---------------------------------------------------------------------------------------------------------------------------------------------------
 // STEP 1: T = Gs C_o; STEP 2: A_H (out0), A_S (out1, TWO) from W = Ct T; STEP 3: Rt_H (out0), Rt_S (out1, TWO) from A_H (in0), A_S (in1)

@@ -1,10 +1,10 @@
-// The tile routines of the density-response kernels (orbresp.hip: the closed-shell chain; orbsmear.hip: the chain over all orbital pairs): staging of operand
-// tiles through padded LDS, the product loop on v_mfma_f64_16x16x4_f64, the workgroup -> (molecule, tile) map and the host-side check of the occupied-packed
-// layout.  Header-only, every function static or __forceinline__ (each file keeps its own copy and its own flags); orbresp.hip's header comment describes
+// The tile routines of the density-response kernels (orbresp.hip: the closed-shell chain; orbsmear.hip: the chain over all orbital pairs) and of the files
+// that came after them (orbpurify.hip, orbsqrt.hip and, through orbbond_tiles.h, orbbond.hip, orblowdin.hip, orbcomm.hip, orbfrontier.hip): staging of operand
+// tiles through padded LDS, the product loop on v_mfma_f64_16x16x4_f64, the occupied-layout part of the workgroup -> (molecule, tile) map (the common part is
+// orbstate.h's), the symmetrise tile routine behind k_orb_resp_sym, k_orb_low_symmetrize and k_orb_comm_antisymmetrize, and the host-side check of the
+// occupied-packed layout.  Header-only, every function static or __forceinline__ (each file keeps its own copy and its own flags); orbresp.hip's header comment describes
 // the orientation of the operands and why the tiles are padded as they are.
 #pragma once
-#include <limits.h>
-
 #include "orbstate.h"
 
 #define NQ_RS_NT 256
@@ -89,38 +89,77 @@ __device__ __forceinline__ void rs_zero(orb_f64x4 (&acc)[4]) {
   for (int s = 0; s < 4; ++s) acc[s] = orb_f64x4{0.0, 0.0, 0.0, 0.0};
 }
 
-// ---- which molecule and tile a workgroup serves; false: exit (uniform over the workgroup) -----------------------------------------------------------------------
-struct RsMol {
-  int b, t, m, no, o0;
-  long long base, obase;
-  bool failed;
+// ---- which molecule and tile a workgroup serves (orb_tile_mol) and where its occupied-packed block lies; false: exit (uniform over the workgroup) -----------------
+struct RsMol : OrbTile {
+  int no;
+  long long obase;
 };
 
 __device__ __forceinline__ bool rs_mol(const OrbArgs& a, int nt, const int* n_occ, const long long* occ_ptr, long long O, RsMol& q) {
-  if (!orb_kind_ok(a, false)) return false;
-  q.b = blockIdx.x / nt;
-  q.t = blockIdx.x - q.b * nt;
-  if (q.b >= a.B) return false;
-  q.o0 = a.orb_ptr[q.b];
-  q.m = a.orb_ptr[q.b + 1] - q.o0;
-  q.base = a.pack_ptr[q.b];
-  if (q.m < 1 || q.m > NQ_ORB_MAX_M || q.o0 < 0 || q.o0 + q.m > a.M || q.base < 0 || q.base + (long long)q.m * q.m > a.P) return false;
-  int no = n_occ[q.b];
+  if (!orb_tile_mol<ORB_HDR_SOLVE>(a, nt, q)) return false;
+  const int no = n_occ[q.b];
   q.no = no < 0 ? 0 : (no > q.m ? q.m : no);
   q.obase = occ_ptr[q.b];
-  if (q.obase < 0 || q.obase + (long long)q.no * q.m > O) return false;
-  q.failed = a.status[q.b] != 0;
-  return true;
+  return q.obase >= 0 && q.obase + (long long)q.no * q.m <= O;
 }
 
-// ---- host: the arguments every launch of the family checks first --------------------------------------------------------------------------------------------------
+// ---- (G + G^T) / 2, or with ANTI (G - G^T) / 2, on the lower-triangle 64 x 64 tile (i0, j0), j0 <= i0, of an m x m block, mirrored ------------------------------------
+// The transposed tile comes through LDS, so that both global reads and both stores run along rows.  Every entry below the diagonal is computed once and stored
+// twice: the result is exactly symmetric, or exactly antisymmetric with a +0.0 diagonal.  failed: NaN.  Every thread of the workgroup calls it (barriers
+// inside); Z must not be Gb.
+template <bool ANTI>
+__device__ __forceinline__ void orb_symmetrize_tile(const double* Gb, double* Z, int m, int i0, int j0, bool failed, double (&tile)[NQ_ORB_TILE][NQ_ORB_TILE + 1]) {
+  const double nan = nq_nan_f64();
+  constexpr int PER = NQ_ORB_TILE * NQ_ORB_TILE / NQ_RS_NT;
+  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {    // tile[r][c] = G[j0 + r][i0 + c]: the mirror image of this workgroup's tile
+    const int r = e >> 6, c = e & 63;
+    tile[r][c] = (j0 + r < m && i0 + c < m) ? Gb[(long long)(j0 + r) * m + i0 + c] : 0.0;
+  }
+  __syncthreads();
+  double v[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const int e = threadIdx.x + k * NQ_RS_NT, r = e >> 6, c = e & 63;
+    const int i = i0 + r, j = j0 + c;
+    v[k] = 0.0;
+    if (i < m && j <= i) {
+      if (ANTI) v[k] = failed ? nan : (i == j ? 0.0 : 0.5 * (Gb[(long long)i * m + j] - tile[c][r]));
+      else v[k] = failed ? nan : 0.5 * (Gb[(long long)i * m + j] + tile[c][r]);
+      Z[(long long)i * m + j] = v[k];
+    }
+  }
+  __syncthreads();                                             // the mirror image has been consumed
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const int e = threadIdx.x + k * NQ_RS_NT;
+    tile[e >> 6][e & 63] = v[k];
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < NQ_ORB_TILE * NQ_ORB_TILE; e += NQ_RS_NT) {    // out[j0 + r][i0 + c] from the value of (i0 + c, j0 + r), strictly above the diagonal
+    const int r = e >> 6, c = e & 63;
+    const int j = j0 + r, i = i0 + c;
+    // 0.0 - v is exact; equal entries give +0.0 on both sides, as (G_ji - G_ij) / 2 does
+    if (i < m && j < i) Z[(long long)j * m + i] = ANTI ? 0.0 - tile[c][r] : tile[c][r];
+  }
+}
+
+// One workgroup per (molecule, lower-triangle tile); KEEP_FAILED: a failed molecule's block is averaged like any other (orbresp.hip), else it is NaN.
+template <bool ANTI, bool KEEP_FAILED>
+__device__ __forceinline__ void orb_symmetrize_kernel(const OrbArgs& a, int nt, const double* G, double* out) {
+  __shared__ double tile[NQ_ORB_TILE][NQ_ORB_TILE + 1];
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, nt, q)) return;
+  if (q.t >= orb_tile_count(q.m)) return;                       // uniform: the barriers are reached by the whole workgroup or not at all
+  int ti, tj;
+  orb_tile_decode(q.t, &ti, &tj);
+  orb_symmetrize_tile<ANTI>(G + q.base, out + q.base, q.m, ti * NQ_ORB_TILE, tj * NQ_ORB_TILE, KEEP_FAILED ? false : q.failed, tile);
+}
+
+// ---- host: the occupied-packed layout, after what every launch of the family checks first (orb_check_launch) --------------------------------------------------------
 static int rs_check(const char* who, const void* state, int32_t B, int32_t M, int64_t P, const int32_t* n_occ, const int64_t* occ_ptr, int64_t O, int* tr) {
-  if (!state) return nq_fail(NQ_ERR_ARG, "%s: null argument", who);
+  NQ_TRY(orb_check_launch(who, state, B, M, P, ORB_GRID_LOWER, tr));
   if (!n_occ) return nq_fail(NQ_ERR_ARG, "%s: n_occ is missing", who);
   if (!occ_ptr) return nq_fail(NQ_ERR_ARG, "%s: occ_ptr is missing", who);
-  NQ_TRY(orb_check_dims(B, M, P));
   if (O < 0 || O > P) return nq_fail(NQ_ERR_ARG, "%s: O=%lld occupied-packed entries do not fit P=%lld", who, (long long)O, (long long)P);
-  *tr = orb_tile_rows(orb_largest_m_bound(B, M, P));
-  if ((long long)B * (*tr * (*tr + 1) / 2) > INT_MAX) return nq_fail(NQ_ERR_ARG, "%s: B=%d molecules of up to %d tiles exceed the grid", who, B, *tr * (*tr + 1) / 2);
   return NQ_OK;
 }

@@ -26,25 +26,6 @@
 #define NQ_SM_KT_MAX 1e300    // a larger kT (inf and NaN too) is refused with info = 1: kT (log(2m / n_elec) + 2) must stay finite for the bracket of mu
 #define NQ_SM_MAX_ITER 4096  // a bisection step at least every third iteration: 3 x (the 1075 halvings from the widest bracket of doubles to one ulp) fits
 
-__device__ __forceinline__ double sm_block_max(double v, double* red) {
-  v = nq_wave_max_f64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = red[0];
-#pragma unroll
-  for (int w = 1; w < NQ_ORB_NW; ++w) r = fmax(r, red[w]);
-  __syncthreads();
-  return r;
-}
-
-// the molecule of a workgroup of the one-workgroup-per-molecule kernels; false: exit (uniform)
-__device__ __forceinline__ bool sm_block_mol(const OrbArgs& a, int b, int& o0, int& m, long long& base) {
-  o0 = a.orb_ptr[b];
-  m = a.orb_ptr[b + 1] - o0;
-  base = a.pack_ptr[b];
-  return m >= 1 && m <= NQ_ORB_MAX_M && o0 >= 0 && o0 + m <= a.M && base >= 0 && base + (long long)m * m <= a.P;
-}
-
 // ---- the chemical potential and the occupations ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_fermi(OrbArgs a, const double* n_elec, const double* kT_in, double* out_mu, double* out_occ, double* out_docc,
                                                          double* out_ent, int* out_info) {
@@ -53,7 +34,8 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_fermi(OrbArgs a, const double
   const int b = blockIdx.x, tid = threadIdx.x;
   int o0, m;
   long long base;
-  if (!sm_block_mol(a, b, o0, m, base)) return;                  // uniform: a state overwritten since nq_orb_init
+  bool failed;
+  if (!orb_mol(a, b, o0, m, base, failed)) return;               // uniform: a state overwritten since nq_orb_init
   const double n = n_elec[b], kT = kT_in[b];
   const double nan = nq_nan_f64();
   // at most two levels per thread (m <= 1024 = 2 x 512)
@@ -63,15 +45,15 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_fermi(OrbArgs a, const double
   const double inf = __longlong_as_double(0x7ff0000000000000LL);
   double bad = ((h0 && !isfinite(e0)) || (h1 && !isfinite(e1))) ? 1.0 : 0.0;
   bad = orb_block_sum(bad, red);
-  const bool ok = a.status[b] == 0 && bad == 0.0 && kT > 0.0 && kT < NQ_SM_KT_MAX && n > 0.0 && n < 2.0 * (double)m;   // NaN n_elec fails both comparisons
+  const bool ok = !failed && bad == 0.0 && kT > 0.0 && kT < NQ_SM_KT_MAX && n > 0.0 && n < 2.0 * (double)m;   // NaN n_elec fails both comparisons
   if (!ok) {
     if (h0) out_occ[o0 + k0] = nan, out_docc[o0 + k0] = nan;
     if (h1) out_occ[o0 + k1] = nan, out_docc[o0 + k1] = nan;
     if (tid == 0) out_mu[b] = nan, out_ent[b] = nan, out_info[b] = 1;
     return;
   }
-  const double emax = sm_block_max(fmax(h0 ? e0 : -inf, h1 ? e1 : -inf), red);
-  const double emin = -sm_block_max(fmax(h0 ? -e0 : -inf, h1 ? -e1 : -inf), red);
+  const double emax = orb_block_max(fmax(h0 ? e0 : -inf, h1 ? e1 : -inf), red);
+  const double emin = -orb_block_max(fmax(h0 ? -e0 : -inf, h1 ? -e1 : -inf), red);
   // the bracket: below lo every F_k <= 2 e^-x sums to less than n_elec / e^2, above hi the holes sum to less than (2m - n_elec) / e^2
   double lo = emin - kT * (log(2.0 * (double)m / n) + 2.0), hi = emax + kT * (log(2.0 * (double)m / (2.0 * (double)m - n)) + 2.0);
   if (!(lo < emin)) lo = nextafter(emin, -inf);                  // kT below the spacing of doubles at eps: x is then clamped to -+1e300 one ulp away
@@ -135,20 +117,10 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_fermi(OrbArgs a, const double
 }
 
 // ---- which molecule and 64 orbitals a workgroup of the two products serves; false: exit (uniform over the workgroup) --------------------------------------------
-struct SmMol {
-  int b, t, m, o0;
-  long long base;
-  bool failed;
-};
-
-__device__ __forceinline__ bool sm_mol(const OrbArgs& a, int tr, SmMol& q) {
-  if (!orb_kind_ok(a, false)) return false;
-  q.b = blockIdx.x / tr;
-  q.t = blockIdx.x - q.b * tr;
-  if (q.b >= a.B) return false;
-  if (!sm_block_mol(a, q.b, q.o0, q.m, q.base)) return false;
-  q.failed = a.status[q.b] != 0;
-  return q.t * NQ_ORB_TILE < q.m;
+__device__ __forceinline__ bool sm_mol(const OrbArgs& a, int tr, OrbTile& q) {
+  if (!orb_tile_mol<ORB_HDR_SOLVE>(a, tr, q)) return false;
+  if (q.t * NQ_ORB_TILE >= q.m) return false;                    // two early returns, not one `return a && b`: k_orb_smear_back's register count hangs on it
+  return true;                                                   // (profiles/orbital_refactor_resources.txt)
 }
 
 // ---- W = C^T T and the divided differences -------------------------------------------------------------------------------------------------------------------------
@@ -156,7 +128,7 @@ template <bool TWO>
 __global__ __launch_bounds__(NQ_RS_NT) void k_orb_smear_mo(OrbArgs a, int tr, const double* mu_in, const double* kT_in, const double* T, double* A_H, double* A_S,
                                                            double* wdiag) {
   __shared__ double lds[3 * NQ_RS_TILE];
-  SmMol q;
+  OrbTile q;
   if (!sm_mol(a, tr, q)) return;
   const int m = q.m, i0 = q.t * NQ_ORB_TILE;                     // the workgroup's 64 rows of W; it walks the columns itself
   const double* Ct = a.coeff + q.base;
@@ -211,8 +183,8 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_smear_diag(OrbArgs a, const d
   const int b = blockIdx.x, tid = threadIdx.x;
   int o0, m;
   long long base;
-  if (!sm_block_mol(a, b, o0, m, base)) return;
-  const bool failed = a.status[b] != 0;
+  bool failed;
+  if (!orb_mol(a, b, o0, m, base, failed)) return;
   const double mu = mu_in[b], kT = kT_in[b], gm = g_mu ? g_mu[b] : 0.0, ge = g_ent ? g_ent[b] : 0.0;
   const double inf = __longlong_as_double(0x7ff0000000000000LL);
   double x[2], gF[2], u[2];
@@ -227,7 +199,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_smear_diag(OrbArgs a, const d
       amin = fmin(amin, fabs(x[s]));
     }
   }
-  amin = -sm_block_max(-amin, red);
+  amin = -orb_block_max(-amin, red);
   double su = 0.0, sg = 0.0;
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -259,7 +231,7 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_orb_smear_diag(OrbArgs a, const d
 template <bool TWO>
 __global__ __launch_bounds__(NQ_RS_NT) void k_orb_smear_back(OrbArgs a, int tr, const double* A_H, const double* A_S, double* Rt_H, double* Rt_S) {
   __shared__ double lds[3 * NQ_RS_TILE];
-  SmMol q;
+  OrbTile q;
   if (!sm_mol(a, tr, q)) return;
   const int m = q.m, j0 = q.t * NQ_ORB_TILE;                     // the workgroup's 64 basis functions mu; it walks the orbitals i itself
   const double* Ct = a.coeff + q.base;
@@ -287,20 +259,12 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_orb_smear_back(OrbArgs a, int tr, 
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------------------------------------
-static int sm_check(const char* who, const void* state, int32_t B, int32_t M, int64_t P, int* tr) {
-  if (!state) return nq_fail(NQ_ERR_ARG, "%s: null argument", who);
-  NQ_TRY(orb_check_dims(B, M, P));
-  *tr = orb_tile_rows(orb_largest_m_bound(B, M, P));
-  if ((long long)B * *tr > INT_MAX) return nq_fail(NQ_ERR_ARG, "%s: B=%d molecules of up to %d tile rows exceed the grid", who, B, *tr);
-  return NQ_OK;
-}
-
 extern "C" {
 
 int nq_orb_fermi(void* state, int32_t B, int32_t M, int64_t P, const double* n_elec, const double* kT, double* out_mu, double* out_occ, double* out_docc,
                  double* out_entropy, int32_t* out_info, void* stream) {
   int tr = 0;
-  NQ_TRY(sm_check("nq_orb_fermi", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_fermi", state, B, M, P, ORB_GRID_ROWS, &tr));
   if (!n_elec || !kT || !out_mu || !out_occ || !out_docc || !out_entropy || !out_info) return nq_fail(NQ_ERR_ARG, "nq_orb_fermi: null argument");
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_fermi");
@@ -312,7 +276,7 @@ int nq_orb_fermi(void* state, int32_t B, int32_t M, int64_t P, const double* n_e
 int nq_orb_smear_mo(void* state, int32_t B, int32_t M, int64_t P, const double* mu, const double* kT, const double* T, double* A_H, double* A_S, double* wdiag,
                     void* stream) {
   int tr = 0;
-  NQ_TRY(sm_check("nq_orb_smear_mo", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_smear_mo", state, B, M, P, ORB_GRID_ROWS, &tr));
   if (!mu || !kT || !T || !A_H || !wdiag) return nq_fail(NQ_ERR_ARG, "nq_orb_smear_mo: null argument");
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, A_S ? "orb_smear_mo_two" : "orb_smear_mo_one");
@@ -329,7 +293,7 @@ int nq_orb_smear_diag(void* state, int32_t B, int32_t M, int64_t P, const double
                       const double* wdiag, const double* g_eps, const double* g_occ, const double* g_mu, const double* g_ent, double* A_H, double* A_S,
                       void* stream) {
   int tr = 0;
-  NQ_TRY(sm_check("nq_orb_smear_diag", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_smear_diag", state, B, M, P, ORB_GRID_ROWS, &tr));
   if (!mu || !kT || !occ || !docc || !wdiag || !A_H) return nq_fail(NQ_ERR_ARG, "nq_orb_smear_diag: null argument");
   hipStream_t st = (hipStream_t)stream;
   NQ_PROF(st, "orb_smear_diag");
@@ -340,7 +304,7 @@ int nq_orb_smear_diag(void* state, int32_t B, int32_t M, int64_t P, const double
 
 int nq_orb_smear_back(void* state, int32_t B, int32_t M, int64_t P, const double* A_H, const double* A_S, double* Rt_H, double* Rt_S, void* stream) {
   int tr = 0;
-  NQ_TRY(sm_check("nq_orb_smear_back", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_smear_back", state, B, M, P, ORB_GRID_ROWS, &tr));
   if (!A_H || !Rt_H) return nq_fail(NQ_ERR_ARG, "nq_orb_smear_back: null argument");
   if (A_S && !Rt_S) return nq_fail(NQ_ERR_ARG, "nq_orb_smear_back: a second input needs a second output");
   hipStream_t st = (hipStream_t)stream;

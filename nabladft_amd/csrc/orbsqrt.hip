@@ -41,24 +41,7 @@
 #define NQ_SQ_LDS (NQ_ORB_TILE * NQ_SQ_TP > 3 * NQ_RS_TILE ? NQ_ORB_TILE * NQ_SQ_TP : 3 * NQ_RS_TILE)
 enum { SC_C = 0, SC_ROOT, SC_TR, SC_SLOT = 8 };
 
-struct SqMol {
-  int b, t, m;
-  long long base;
-};
-
-// which molecule and tile a workgroup serves; false: exit (uniform over the workgroup)
-__device__ __forceinline__ bool sq_mol(const OrbArgs& a, int nt, SqMol& q) {
-  if (!orb_dims_ok(a)) return false;
-  q.b = blockIdx.x / nt;
-  q.t = blockIdx.x - q.b * nt;
-  if (q.b >= a.B) return false;
-  const int o0 = a.orb_ptr[q.b];
-  q.m = a.orb_ptr[q.b + 1] - o0;
-  q.base = a.pack_ptr[q.b];
-  return !(q.m < 1 || q.m > NQ_ORB_MAX_M || o0 < 0 || o0 + q.m > a.M || q.base < 0 || q.base + (long long)q.m * q.m > a.P);
-}
-
-__device__ __forceinline__ bool sq_runs(const OrbArgs& a, const SqMol& q, const int* log, int k) { return a.status[q.b] == 0 && (k == 0 || log[k - 1] == 1); }
+__device__ __forceinline__ bool sq_runs(const OrbArgs& a, const OrbTile& q, const int* log, int k) { return a.status[q.b] == 0 && (k == 0 || log[k - 1] == 1); }
 
 // ---- c, Y_0 = S / c, Z_0 = I -------------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NQ_ORB_NT) void k_sq_init(OrbArgs a, const void* S, int s_f64, int max_iter, double* Yall, double* Zall, double* ctl_all, int* log_all) {
@@ -113,8 +96,8 @@ __global__ __launch_bounds__(NQ_ORB_NT) void k_sq_init(OrbArgs a, const void* S,
 __global__ __launch_bounds__(NQ_RS_NT) void k_sq_t(OrbArgs a, int nt, int k, int max_iter, const double* Y0, const double* Z0, const double* Y1, const double* Z1,
                                                    double* Tall, double* ctl_all, const int* log_all) {
   __shared__ double lds[3 * NQ_RS_TILE];
-  SqMol q;
-  if (!sq_mol(a, nt, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, nt, q)) return;
   const int m = q.m;
   if (q.t >= orb_tile_count(m) || !sq_runs(a, q, log_all + (long long)q.b * max_iter, k)) return;
   int ti, tj;
@@ -199,8 +182,8 @@ __device__ __forceinline__ void sq_gemm2(const double* Y, const double* Z, const
 __global__ __launch_bounds__(NQ_RS_NT) void k_sq_update(OrbArgs a, int tr, int k, int max_iter, double* Y0, double* Z0, double* Y1, double* Z1, const double* Tall,
                                                         double* ctl_all, int* log_all) {
   __shared__ double lds[NQ_SQ_LDS];
-  SqMol q;
-  if (!sq_mol(a, tr * tr, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, tr * tr, q)) return;
   const int m = q.m, ti = q.t / tr, tj = q.t - ti * tr;
   if (ti * NQ_ORB_TILE >= m || tj * NQ_ORB_TILE >= m) return;
   int* log = log_all + (long long)q.b * max_iter;
@@ -249,8 +232,8 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_sq_update(OrbArgs a, int tr, int k
 // ---- half = sqrt(c) Y and inv_half = Z / sqrt(c), lower triangles mirrored; one workgroup per lower-triangle 64 x 64 tile ------------------------------------------
 __global__ __launch_bounds__(NQ_RS_NT) void k_sq_finish(OrbArgs a, int nt, int max_iter, const double* Y0, const double* Z0, const double* Y1, const double* Z1,
                                                         const double* ctl_all, const int* log_all, double* half, double* inv_half) {
-  SqMol q;
-  if (!sq_mol(a, nt, q)) return;
+  OrbTile q;
+  if (!orb_tile_mol<ORB_HDR_DIMS>(a, nt, q)) return;
   const int m = q.m;
   if (q.t >= orb_tile_count(m)) return;
   int ti, tj;
@@ -276,14 +259,6 @@ __global__ __launch_bounds__(NQ_RS_NT) void k_sq_finish(OrbArgs a, int nt, int m
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------------------------------
-static int sq_check(const char* who, const void* state, int32_t B, int32_t M, int64_t P, int* tr) {
-  if (!state) return nq_fail(NQ_ERR_ARG, "%s: null argument", who);
-  NQ_TRY(orb_check_dims(B, M, P));
-  *tr = orb_tile_rows(orb_largest_m_bound(B, M, P));
-  if ((long long)B * *tr * *tr > INT_MAX) return nq_fail(NQ_ERR_ARG, "%s: B=%d molecules of up to %d tiles exceed the grid", who, B, *tr * *tr);
-  return NQ_OK;
-}
-
 static int sq_check_iter(const char* who, int32_t k, int32_t max_iter) {
   if (max_iter < 1 || max_iter > NQ_SQ_MAX_ITER) return nq_fail(NQ_ERR_ARG, "%s: max_iter=%d outside 1..%d", who, max_iter, NQ_SQ_MAX_ITER);
   if (k < 0 || k >= max_iter) return nq_fail(NQ_ERR_ARG, "%s: iteration k=%d outside 0..max_iter-1=%d", who, k, max_iter - 1);
@@ -317,7 +292,7 @@ extern "C" {
 int nq_orb_sqrt_init(void* state, int32_t B, int32_t M, int64_t P, const void* S, int32_t s_f64, int32_t max_iter, double* Y, double* Z, double* ctl, int32_t* log,
                      void* stream) {
   int tr = 0;
-  NQ_TRY(sq_check("nq_orb_sqrt_init", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_sqrt_init", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(sq_check_iter("nq_orb_sqrt_init", 0, max_iter));
   if (!S || !Y || !Z || !ctl || !log) return nq_fail(NQ_ERR_ARG, "nq_orb_sqrt_init: null argument");
   if ((const void*)Y == S || (const void*)Z == S || Y == Z || (void*)ctl == (void*)log || (void*)ctl == (void*)Y || (void*)ctl == (void*)Z ||
@@ -333,7 +308,7 @@ int nq_orb_sqrt_init(void* state, int32_t B, int32_t M, int64_t P, const void* S
 int nq_orb_sqrt_step(void* state, int32_t B, int32_t M, int64_t P, int32_t k, int32_t max_iter, double* Y, double* Z, double* T, double* Y2, double* Z2, double* ctl,
                      int32_t* log, void* stream) {
   int tr = 0;
-  NQ_TRY(sq_check("nq_orb_sqrt_step", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_sqrt_step", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(sq_check_iter("nq_orb_sqrt_step", k, max_iter));
   NQ_TRY(sq_check_arrays("nq_orb_sqrt_step", Y, Z, T, Y2, Z2, ctl, log, nullptr, nullptr));
   hipStream_t st = (hipStream_t)stream;
@@ -344,7 +319,7 @@ int nq_orb_sqrt_step(void* state, int32_t B, int32_t M, int64_t P, int32_t k, in
 int nq_orb_sqrt_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, double* Y, double* Z, double* T, double* Y2, double* Z2, double* ctl, int32_t* log,
                     void* stream) {
   int tr = 0;
-  NQ_TRY(sq_check("nq_orb_sqrt_run", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_sqrt_run", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(sq_check_iter("nq_orb_sqrt_run", 0, max_iter));
   NQ_TRY(sq_check_arrays("nq_orb_sqrt_run", Y, Z, T, Y2, Z2, ctl, log, nullptr, nullptr));
   hipStream_t st = (hipStream_t)stream;
@@ -357,7 +332,7 @@ int nq_orb_sqrt_run(void* state, int32_t B, int32_t M, int64_t P, int32_t max_it
 int nq_orb_sqrt_finish(void* state, int32_t B, int32_t M, int64_t P, int32_t max_iter, const double* Y, const double* Z, const double* Y2, const double* Z2,
                        const double* ctl, const int32_t* log, double* half, double* inv_half, void* stream) {
   int tr = 0;
-  NQ_TRY(sq_check("nq_orb_sqrt_finish", state, B, M, P, &tr));
+  NQ_TRY(orb_check_launch("nq_orb_sqrt_finish", state, B, M, P, ORB_GRID_SQUARE, &tr));
   NQ_TRY(sq_check_iter("nq_orb_sqrt_finish", 0, max_iter));
   if (!half || !inv_half) return nq_fail(NQ_ERR_ARG, "nq_orb_sqrt_finish: null argument");
   NQ_TRY(sq_check_arrays("nq_orb_sqrt_finish", Y, Z, half, Y2, Z2, ctl, log, inv_half, nullptr));

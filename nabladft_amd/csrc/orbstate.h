@@ -1,8 +1,11 @@
-// What the two files of the orbital job share (orbitals.hip: the solver and its figures; orbdens.hip: weighted Gram products of the coefficient blocks and
-// populations): the parts of the caller-owned state buffer, the kernels' view of it, the refusal of a call that comes with other dimensions than nq_orb_init,
-// the host-side check of the dimensions, the workgroup sum, and the arithmetic that maps a workgroup to a lower-triangle output tile.  Header-only, every
-// function static or __forceinline__ (each file keeps its own copy and its own flags); no a * b + c in here.
+// What the files of the orbital family share (orbitals.hip: the solver and its figures; orbdens.hip: weighted Gram products of the coefficient blocks and
+// populations; and, through orbresp_tiles.h, every orb*.hip after them): the parts of the caller-owned state buffer, the kernels' view of it, the refusal of a
+// call that comes with other dimensions than nq_orb_init, the workgroup -> (molecule, tile) map with its one bounds test (orb_mol, orb_tile_mol), the workgroup
+// sum and maximum, the arithmetic that maps a workgroup to a lower-triangle output tile, and the host-side check every entry point makes first: the state
+// pointer, the dimensions and the grid (orb_check_launch).  Header-only, every function static or __forceinline__ (each file keeps its own copy and its own
+// flags); no a * b + c in here.
 #pragma once
+#include <limits.h>
 #include <math.h>
 
 #include "../../include/nablaq.h"
@@ -46,6 +49,37 @@ __device__ __forceinline__ bool orb_kind_ok(const OrbArgs& a, bool purify) {
   return ok;
 }
 
+// ---- which molecule (and which of its tiles) a workgroup serves; false: exit (uniform over the workgroup) -------------------------------------------------------
+// Molecule b's first orbital o0, its orbital count m, the start of its packed m x m block and whether its status word reports a failure.  false: the block
+// does not lie inside the state (a state overwritten since nq_orb_init).  A kernel that does not read `failed` does not load the status word.
+__device__ __forceinline__ bool orb_mol(const OrbArgs& a, int b, int& o0, int& m, long long& base, bool& failed) {
+  o0 = a.orb_ptr[b];
+  m = a.orb_ptr[b + 1] - o0;
+  base = a.pack_ptr[b];
+  if (m < 1 || m > NQ_ORB_MAX_M || o0 < 0 || o0 + m > a.M || base < 0 || base + (long long)m * m > a.P) return false;
+  failed = a.status[b] != 0;
+  return true;
+}
+
+struct OrbTile {
+  int b, t, m, o0;
+  long long base;
+  bool failed;
+};
+
+// what a kernel needs of the state's header: its layout alone, the coefficients and energies of a solve, or the iterates of a purification (orb_kind_ok)
+enum OrbHeader { ORB_HDR_DIMS = 0, ORB_HDR_SOLVE, ORB_HDR_PURIFY };
+
+// workgroup blockIdx.x is workgroup t of the `per` that serve molecule b
+template <OrbHeader HDR>
+__device__ __forceinline__ bool orb_tile_mol(const OrbArgs& a, int per, OrbTile& q) {
+  if (!(HDR == ORB_HDR_DIMS ? orb_dims_ok(a) : orb_kind_ok(a, HDR == ORB_HDR_PURIFY))) return false;
+  q.b = blockIdx.x / per;
+  q.t = blockIdx.x - q.b * per;
+  if (q.b >= a.B) return false;
+  return orb_mol(a, q.b, q.o0, q.m, q.base, q.failed);
+}
+
 // the wavefronts' partial sums meet in red[NQ_ORB_NW] and are added in wavefront order; every thread returns what it read from LDS (uniform)
 __device__ __forceinline__ double orb_block_sum(double v, double* red) {
   v = nq_wave_sum_f64(v);
@@ -54,6 +88,18 @@ __device__ __forceinline__ double orb_block_sum(double v, double* red) {
   double r = 0.0;
 #pragma unroll
   for (int w = 0; w < NQ_ORB_NW; ++w) r += red[w];
+  __syncthreads();
+  return r;
+}
+
+// the same for the maximum (fmax: a NaN is dropped)
+__device__ __forceinline__ double orb_block_max(double v, double* red) {
+  v = nq_wave_max_f64(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double r = red[0];
+#pragma unroll
+  for (int w = 1; w < NQ_ORB_NW; ++w) r = fmax(r, red[w]);
   __syncthreads();
   return r;
 }
@@ -94,4 +140,19 @@ static inline int orb_largest_m_bound(int32_t B, int32_t M, int64_t P) {
   if (b > NQ_ORB_MAX_M) b = NQ_ORB_MAX_M;
   while (b > 1 && b * b > p) --b;
   return b < 1 ? 1 : (int)b;
+}
+
+// ---- host: what every entry point of the family checks first ------------------------------------------------------------------------------------------------------
+// The workgroups a launch gives every molecule: `per_mol` of them (one, unless the kernel splits a molecule's work into a fixed number of shares), one per 64
+// orbitals, one per lower-triangle 64 x 64 tile, or one per tile of the square.  tr = the tile rows of the largest molecule the dimensions allow.
+enum OrbGrid { ORB_GRID_MOL = 0, ORB_GRID_ROWS, ORB_GRID_LOWER, ORB_GRID_SQUARE };
+
+static int orb_check_launch(const char* who, const void* state, int32_t B, int32_t M, int64_t P, OrbGrid grid, int* tr = nullptr, int per_mol = 1) {
+  if (!state) return nq_fail(NQ_ERR_ARG, "%s: null argument (state)", who);
+  NQ_TRY(orb_check_dims(B, M, P));
+  const long long r = orb_tile_rows(orb_largest_m_bound(B, M, P));
+  const long long per = grid == ORB_GRID_MOL ? per_mol : grid == ORB_GRID_ROWS ? r : grid == ORB_GRID_LOWER ? r * (r + 1) / 2 : r * r;
+  if ((long long)B * per > INT_MAX) return nq_fail(NQ_ERR_ARG, "%s: B=%d molecules of up to %lld workgroups exceed the grid", who, B, per);
+  if (tr) *tr = (int)r;
+  return NQ_OK;
 }

@@ -191,6 +191,15 @@ def _packed(t: torch.Tensor, P: int, name: str) -> torch.Tensor:
     return t.reshape(-1).contiguous()
 
 
+def _typed(t: Optional[torch.Tensor]):
+    """The argument pair of a float32-or-float64 matrix that may be absent: ``(pointer, is_float64)``."""
+    return _lib.ptr(t), int(t is not None and t.dtype == torch.float64)
+
+
+def _ptrs(tensors):
+    return [_lib.ptr(t) for t in tensors]
+
+
 class OrbitalState(DeviceState):
     """One caller-owned device buffer behind ``nq_orb_*`` plus typed views of its parts: ``eps`` f64 [M], ``coeff`` f64 [P] (row k of a block = orbital k),
     ``status`` / ``info`` / ``iters`` int32 [B] (include/nablaq.h)."""
@@ -222,14 +231,17 @@ class OrbitalState(DeviceState):
             _lib.check(_lib.load().nq_orb_init(_lib.ptr(self.buf), nbytes, op32.ctypes.data_as(C.c_void_p), *self._dims, out, _lib.stream_ptr()))
         self.max_m = int(out[0])
 
+    def call(self, name: str, *args):
+        """The one launch line of the family: ``name(buf, B, M, P, *args, stream)`` on the state's device and the current stream; raises on a refusal."""
+        with torch.cuda.device(self.buf.device):
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(self.buf), *self._dims, *args, _lib.stream_ptr()))
+
     def solve(self, H_packed: torch.Tensor, S_packed: Optional[torch.Tensor] = None):
         H = _packed(H_packed, self.P, "H_packed")
         S = None if S_packed is None else _packed(S_packed, self.P, "S_packed")
         if H.device != self.buf.device or (S is not None and S.device != self.buf.device):
             raise ValueError(f"the matrices must live on {self.buf.device}")
-        with torch.cuda.device(self.buf.device):
-            _lib.check(_lib.load().nq_orb_solve(_lib.ptr(self.buf), *self._dims, _lib.ptr(H), int(H.dtype == torch.float64), _lib.ptr(S),
-                                                int(S is not None and S.dtype == torch.float64), _lib.stream_ptr()))
+        self.call("nq_orb_solve", *_typed(H), *_typed(S))
 
     def header(self) -> dict:
         """The header words (one small device->host copy, synchronises the stream); raises if a call was refused on the device."""
@@ -240,8 +252,204 @@ class OrbitalState(DeviceState):
             raise RuntimeError("a state that holds a purification was passed to a call that reads orbital coefficients, or the reverse")
         return dict(B=h[0], M=h[1], P=(h[2] & 0xffffffff) + (h[3] << 32), status=h[4], max_m=h[5])
 
+    def first_failure(self):
+        """What every ``check()`` starts with: the header (raises if a call was refused on the device) and the status words, one host synchronisation ->
+        ``(b, status[b])`` of the first molecule with a non-zero status, or None."""
+        self.header()
+        status = self.status.cpu().numpy()
+        bad = np.nonzero(status)[0]
+        return (int(bad[0]), int(status[bad[0]])) if bad.size else None
 
-class BatchedOrbitals:
+
+class _LayoutLaunches:
+    """The launches that read the layout of ``self.state`` alone (its ``orb_ptr`` / ``pack_ptr`` and status words), whatever its matrices hold: populations, bond
+    orders, the Löwdin congruences and the commutators.  ``BatchedOrbitals`` and ``BatchedPurification`` derive from it."""
+
+    def _f64(self, t: torch.Tensor, n: int, name: str) -> torch.Tensor:
+        dev = self.state.buf.device
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.numel() != n or t.device != dev:
+            raise ValueError(f"{name} must be float64 [{n}] on {dev}")
+        return t.detach().reshape(-1).contiguous()
+
+    def _scratch(self, n: int, make: bool = True):
+        return torch.empty(n, dtype=torch.float64, device=self.state.buf.device) if make else None
+
+    # ---- populations (csrc/orbdens.hip, csrc/orbresp.hip) and bond orders (csrc/orbbond.hip) ------------------------------------------------------------------
+    def _bond_tables(self, plan):
+        """The one validation of a plan against the batch -> ``(N, Q, mol_ptr int32, atom_orb_ptr int64, bond_ptr int64)``, the three tables on the device; one
+        small device -> host copy of ``mol_ptr``, remembered per plan.  The populations use the first, third and fourth, the bond orders all five."""
+        st, dev = self.state, self.state.buf.device
+        cached = getattr(self, "_bond_cache", None)
+        if cached is not None and cached[0] is plan:
+            return cached[1]
+        if int(plan.B) != st.B or int(plan.m_total) != st.M or int(plan.total) != st.P:
+            raise ValueError("the plan belongs to another batch")
+        N = int(plan.N)
+        mp = _host_ptr(plan.mol_ptr)
+        if mp.shape[0] != st.B + 1 or plan.orb_ptr.numel() != N + 1 or int(mp[0]) != 0 or int(mp[-1]) != N:
+            raise ValueError("the plan belongs to another batch: its mol_ptr / orb_ptr do not have B + 1 / N + 1 entries")
+        bp = bond_layout(mp)
+        out = (N, int(bp[-1]), plan.mol_ptr.to(device=dev, dtype=torch.int32).contiguous(), plan.orb_ptr.to(device=dev, dtype=torch.int64).contiguous(),
+               torch.from_numpy(bp).to(dev))
+        self._bond_cache = (plan, out)
+        return out
+
+    def populations(self, D: torch.Tensor, plan, S_packed: Optional[torch.Tensor] = None, H_packed: Optional[torch.Tensor] = None):
+        """Mulliken analysis of a packed density ``D`` -> ``(atom_pop [N], nelec [B], eband [B] or None without H_packed)``, float64 on the device:
+        ``pop_mu = sum_nu D_mu,nu S_mu,nu`` summed over each atom's orbitals, ``nelec = Tr(D S)``, ``eband = Tr(D H)``.  ``plan``: the ``BlockAssembler`` /
+        ``IrrepsAssembler`` plan of the batch (its ``mol_ptr`` and per-atom ``orb_ptr``).  ``S_packed = None``: the identity."""
+        st, dev = self.state, self.state.buf.device
+        Dp = _packed(D, st.P, "D")
+        if Dp.dtype != torch.float64:
+            raise TypeError("D must be float64 (what density() returns)")
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        H = None if H_packed is None else _packed(H_packed, st.P, "H_packed")
+        N, _, mol_ptr, atom_ptr, _ = self._bond_tables(plan)
+        pop = torch.empty(N, dtype=torch.float64, device=dev)
+        nelec = torch.empty(st.B, dtype=torch.float64, device=dev)
+        eband = None if H is None else torch.empty(st.B, dtype=torch.float64, device=dev)
+        st.call("nq_orb_population", _lib.ptr(Dp), *_typed(H), *_typed(S), N, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr), _lib.ptr(pop), _lib.ptr(nelec),
+                                     _lib.ptr(eband))
+        return pop, nelec, eband
+
+    def populations_backward(self, plan, g_pop, g_nelec, g_eband, D=None, S_packed=None, H_packed=None, want_s: bool = False, want_h: bool = False):
+        """The reverse of ``populations`` (``nq_orb_population_backward``): upstream gradients (float64, each may be None) -> ``(gD, gS or None, gH or None)``,
+        packed float64 [P], with respect to symmetric ``D``, ``S`` and ``H``."""
+        st = self.state
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        H = None if H_packed is None else _packed(H_packed, st.P, "H_packed")
+        Dp = None if D is None else self._f64(D, st.P, "D")
+        N, _, mol_ptr, atom_ptr, _ = self._bond_tables(plan)
+        gs = [None if g is None else self._f64(g, n, name) for g, n, name in ((g_pop, N, "g_pop"), (g_nelec, st.B, "g_nelec"), (g_eband, st.B, "g_eband"))]
+        outs = [self._scratch(st.P), self._scratch(st.P, want_s), self._scratch(st.P, want_h)]
+        st.call("nq_orb_population_backward", *[_lib.ptr(g) for g in gs], _lib.ptr(Dp), *_typed(H), *_typed(S), N, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
+                                              *[_lib.ptr(o) for o in outs])
+        return tuple(outs)
+
+    def bond_product(self, D: torch.Tensor, S_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``P = D S`` per molecule (``nq_orb_bond_product``), packed float64 [P], not symmetric; only the lower triangles of ``D`` and ``S`` are read.
+        ``S_packed = None``: ``D`` made symmetric from its lower triangle."""
+        st = self.state
+        Dp = self._f64(D, st.P, "D")
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        out = self._scratch(st.P)
+        st.call("nq_orb_bond_product", _lib.ptr(Dp), *_typed(S), _lib.ptr(out))
+        return out
+
+    def bond_reduce(self, Pm: torch.Tensor, plan, valence: bool = True):
+        """``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` and (``valence``) ``V_A = sum_{B != A} B_AB`` (``nq_orb_bond_reduce``) -> ``(bond [Q], valence [N] or
+        None)``, float64 on the device; ``bond`` is exactly symmetric inside each molecule's ``[n, n]`` block (``bond_layout``)."""
+        st, dev = self.state, self.state.buf.device
+        N, Q, mol_ptr, atom_ptr, bond_ptr = self._bond_tables(plan)
+        bond = self._scratch(Q)
+        val = torch.empty(N, dtype=torch.float64, device=dev) if valence else None
+        st.call("nq_orb_bond_reduce", _lib.ptr(self._f64(Pm, st.P, "P")), N, Q, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr), _lib.ptr(bond_ptr), _lib.ptr(bond),
+                                      _lib.ptr(val))
+        return bond, val
+
+    def bond_orders(self, D: torch.Tensor, plan, S_packed: Optional[torch.Tensor] = None):
+        """Mayer bond orders and valences of a packed closed-shell density ``D`` (float64 [P], carrying the factor 2: what ``density()`` returns) ->
+        ``(bond [Q], valence [N], P [P])``, float64 on the device: ``P = D S``, ``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` (``B_AA`` included; molecule b's
+        table is ``dense_bond_orders(bond, plan.mol_ptr, b)``), ``V_A = sum_{B != A} B_AB``.  ``plan``: the ``BlockAssembler`` / ``IrrepsAssembler`` plan of the batch
+        (its ``mol_ptr`` and per-atom ``orb_ptr``).  ``S_packed = None``: the Wiberg index of an orthogonal basis.  An atom with more than 32 orbitals gets NaN
+        in its row and column, a molecule the solver failed on NaN in all its entries.  Two launches (three with the valences); nothing is read back."""
+        Pm = self.bond_product(D, S_packed)
+        bond, val = self.bond_reduce(Pm, plan)
+        return bond, val, Pm
+
+    def bond_orders_backward(self, plan, g_bond, g_valence, Pm: torch.Tensor, D=None, S_packed=None, want_d: bool = True, want_s: bool = False, return_e: bool = False):
+        """The reverse of ``bond_orders`` (``nq_orb_bond_backward``): upstream gradients ``g_bond`` [Q] and ``g_valence`` [N] (float64, each may be None) and the
+        ``P`` of the forward -> ``(gD or None, gS or None)``, packed float64 [P], exactly symmetric, with respect to symmetric ``D`` and ``S``:
+        ``sym(E S)`` and ``sym(D E)`` with ``E_mu,nu = (Gamma_AB + Gamma_BA) P_nu,mu``, ``Gamma_AB = g_bond_AB + (A != B) g_valence_A``.  ``want_s`` needs ``D`` and
+        ``S_packed``.  ``return_e``: ``E`` as a third member (for tests)."""
+        st = self.state
+        N, Q, mol_ptr, atom_ptr, bond_ptr = self._bond_tables(plan)
+        if not (want_d or want_s):
+            raise ValueError("bond_orders_backward: neither gradient is asked for")
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        if want_s and (S is None or D is None):
+            raise ValueError("bond_orders_backward: the gradient of S needs S_packed and D")
+        Dp = self._f64(D, st.P, "D") if want_s else None
+        gb = None if g_bond is None else self._f64(g_bond, Q, "g_bond")
+        gv = None if g_valence is None else self._f64(g_valence, N, "g_valence")
+        E, gD, gS = self._scratch(st.P), self._scratch(st.P, want_d), self._scratch(st.P, want_s)
+        st.call("nq_orb_bond_backward", _lib.ptr(gb), _lib.ptr(gv), _lib.ptr(self._f64(Pm, st.P, "P")), _lib.ptr(Dp), *_typed(S), N, Q, _lib.ptr(mol_ptr),
+                                        _lib.ptr(atom_ptr), _lib.ptr(bond_ptr), _lib.ptr(E), _lib.ptr(gD), _lib.ptr(gS))
+        return (gD, gS, E) if return_e else (gD, gS)
+
+    # ---- Löwdin congruences (csrc/orblowdin.hip) ---------------------------------------------------------------------------------------------------------------
+    def low_product(self, Msym: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+        """``Y = M X`` per molecule (``nq_orb_low_product``), packed float64 [P], not symmetric: ``Msym`` float32 or float64 [P] and ``X`` float64 [P] are
+        symmetric and only their lower triangles are read."""
+        st = self.state
+        Mp = _packed(Msym, st.P, "M")
+        out = self._scratch(st.P)
+        st.call("nq_orb_low_product", *_typed(Mp), _lib.ptr(self._f64(X, st.P, "X")), _lib.ptr(out))
+        return out
+
+    def low_symprod(self, E: torch.Tensor, X: torch.Tensor, side: int, alpha: float = 1.0) -> torch.Tensor:
+        """``alpha sym(X E)`` (``side`` 0) or ``alpha sym(E X)`` (``side`` 1) per molecule (``nq_orb_low_symprod``), packed float64 [P], exactly symmetric: ``E``
+        any matrix, ``X`` symmetric, its lower triangle read."""
+        st = self.state
+        if side not in (0, 1):
+            raise ValueError(f"low_symprod: side must be 0 (sym(X E)) or 1 (sym(E X)), not {side!r}")
+        out = self._scratch(st.P)
+        st.call("nq_orb_low_symprod", _lib.ptr(self._f64(E, st.P, "E")), _lib.ptr(self._f64(X, st.P, "X")), int(side), float(alpha), _lib.ptr(out))
+        return out
+
+    def low_symmetrize(self, G: torch.Tensor) -> torch.Tensor:
+        """``(G + G^T) / 2`` per molecule (``nq_orb_low_symmetrize``), packed float64 [P], exactly symmetric: one elementwise launch on the device."""
+        st = self.state
+        out = self._scratch(st.P)
+        st.call("nq_orb_low_symmetrize", _lib.ptr(self._f64(G, st.P, "G")), _lib.ptr(out))
+        return out
+
+    def sym_congruence(self, X: torch.Tensor, Msym: torch.Tensor):
+        """``M^L = X M X`` for symmetric ``X`` (``S^(1/2)`` or ``S^(-1/2)``) and symmetric ``M`` (``D`` or ``H``, float32 or float64) -> ``(M_L, Y)``: ``Y = M X``
+        is kept for the reverse, ``M_L = sym(X Y)`` is exactly symmetric.  Two launches."""
+        Y = self.low_product(Msym, X)
+        return self.low_symprod(Y, X, 0), Y
+
+    def sym_congruence_backward(self, G: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, want_m: bool = True, want_x: bool = True, symmetric: bool = True):
+        """The reverse of ``sym_congruence`` for an upstream ``G = dL/dM^L`` -> ``(dL/dM or None, dL/dX or None)``: ``sym(X (G X))`` (two launches) and
+        ``Y G + G Y^T = 2 sym(Y G)`` (one), packed float64 [P], exactly symmetric.  ``symmetric=True`` (the default): ``G`` is symmetric and its lower triangle
+        is read; ``False``: any matrix, made symmetric first by one ``nq_orb_low_symmetrize`` launch."""
+        if not (want_m or want_x):
+            raise ValueError("sym_congruence_backward: neither gradient is asked for")
+        if not symmetric:
+            G = self.low_symmetrize(G)
+        gM = self.low_symprod(self.low_product(G, X), X, 0) if want_m else None
+        gX = self.low_symprod(Y, G, 1, 2.0) if want_x else None
+        return gM, gX
+
+    # ---- SCF residual (csrc/orbcomm.hip) -------------------------------------------------------------------------------------------------------------------------
+    def commutator(self, X: torch.Tensor, Y: torch.Tensor, x_anti: bool = False, alpha: float = 1.0) -> torch.Tensor:
+        """``alpha (X Y - Y X)`` per molecule (``nq_orb_comm_product``), packed float64 [P].  ``Y`` is symmetric, its lower triangle is read.  ``x_anti=False``:
+        ``X`` symmetric (lower triangle read), the result exactly antisymmetric with a ``+0.0`` diagonal; ``x_anti=True``: ``X`` antisymmetric (strict lower
+        triangle read, the mirrored element is the negated one, the stored diagonal is ignored), the result exactly symmetric.  Only the layout of the state
+        is read: no solve is needed."""
+        st = self.state
+        out = self._scratch(st.P)
+        st.call("nq_orb_comm_product", _lib.ptr(self._f64(X, st.P, "X")), int(bool(x_anti)), _lib.ptr(self._f64(Y, st.P, "Y")), float(alpha), _lib.ptr(out))
+        return out
+
+    def antisymmetrize(self, G: torch.Tensor) -> torch.Tensor:
+        """``(G - G^T) / 2`` per molecule (``nq_orb_comm_antisymmetrize``), packed float64 [P], exactly antisymmetric with a ``+0.0`` diagonal."""
+        st = self.state
+        out = self._scratch(st.P)
+        st.call("nq_orb_comm_antisymmetrize", _lib.ptr(self._f64(G, st.P, "G")), _lib.ptr(out))
+        return out
+
+    def commutator_norms(self, R: torch.Tensor):
+        """``(sum_ij R_ij^2, max_ij |R_ij|)`` per molecule over the whole block (``nq_orb_comm_norms``), float64 [B] each on the device; the maximum of an SCF
+        residual is the DIIS error.  A molecule with ``status != 0`` or a NaN entry gets NaN in both."""
+        st = self.state
+        sumsq, maxabs = self._scratch(st.B), self._scratch(st.B)
+        st.call("nq_orb_comm_norms", _lib.ptr(self._f64(R, st.P, "R")), _lib.ptr(sumsq), _lib.ptr(maxabs))
+        return sumsq, maxabs
+
+
+class BatchedOrbitals(_LayoutLaunches):
     """Orbital energies and coefficients of every molecule of a batch.
 
     ``BatchedOrbitals(orb_ptr)``: ``orb_ptr`` [B+1] (host array or tensor), or a ``BlockAssembler`` / ``IrrepsAssembler`` plan (its ``mol_orb_ptr``).
@@ -290,8 +498,7 @@ class BatchedOrbitals:
         st = self.state
         no = torch.from_numpy(check_occupied(n_occ, st.orb_ptr_host)).to(st.buf.device)
         out = torch.empty(3, st.B, dtype=torch.float64, device=st.buf.device)
-        with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_frontier(_lib.ptr(st.buf), *st._dims, _lib.ptr(no), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.stream_ptr()))
+        st.call("nq_orb_frontier", _lib.ptr(no), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]))
         return out[0], out[1], out[2]
 
     def compare(self, target: "BatchedOrbitals", n_occ, S_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -303,8 +510,8 @@ class BatchedOrbitals:
         S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
         out = torch.empty(len(FIGURES), st.B, dtype=torch.float64, device=st.buf.device)
         with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_compare(_lib.ptr(st.buf), _lib.ptr(tt.buf), *st._dims, _lib.ptr(S), int(S is not None and S.dtype == torch.float64),
-                                                  _lib.ptr(no), _lib.ptr(out), _lib.stream_ptr()))
+            # two states in front of the dimensions: the one launch that is not OrbitalState.call
+            _lib.check(_lib.load().nq_orb_compare(_lib.ptr(st.buf), _lib.ptr(tt.buf), *st._dims, *_typed(S), _lib.ptr(no), _lib.ptr(out), _lib.stream_ptr()))
         return out
 
     def weighted_gram(self, w0: torch.Tensor, w1: Optional[torch.Tensor] = None, k_lo=None, k_hi=None):
@@ -328,9 +535,7 @@ class BatchedOrbitals:
             ks.append(None if k is None else k.contiguous())
         out0 = torch.empty(st.P, dtype=torch.float64, device=dev)
         out1 = None if ws[1] is None else torch.empty(st.P, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().nq_orb_wgram(_lib.ptr(st.buf), *st._dims, _lib.ptr(ws[0]), _lib.ptr(ws[1]), _lib.ptr(ks[0]), _lib.ptr(ks[1]), _lib.ptr(out0),
-                                                _lib.ptr(out1), _lib.stream_ptr()))
+        st.call("nq_orb_wgram", _lib.ptr(ws[0]), _lib.ptr(ws[1]), _lib.ptr(ks[0]), _lib.ptr(ks[1]), _lib.ptr(out0), _lib.ptr(out1))
         return out0 if out1 is None else (out0, out1)
 
     def density(self, n_occ, energy_weighted: bool = False):
@@ -341,32 +546,6 @@ class BatchedOrbitals:
         two = torch.full((st.M,), 2.0, dtype=torch.float64, device=st.buf.device)
         return self.weighted_gram(two, 2.0 * st.eps if energy_weighted else None, None, no)
 
-    def populations(self, D: torch.Tensor, plan, S_packed: Optional[torch.Tensor] = None, H_packed: Optional[torch.Tensor] = None):
-        """Mulliken analysis of a packed density ``D`` -> ``(atom_pop [N], nelec [B], eband [B] or None without H_packed)``, float64 on the device:
-        ``pop_mu = sum_nu D_mu,nu S_mu,nu`` summed over each atom's orbitals, ``nelec = Tr(D S)``, ``eband = Tr(D H)``.  ``plan``: the ``BlockAssembler`` /
-        ``IrrepsAssembler`` plan of the batch (its ``mol_ptr`` and per-atom ``orb_ptr``).  ``S_packed = None``: the identity."""
-        st, dev = self.state, self.state.buf.device
-        Dp = _packed(D, st.P, "D")
-        if Dp.dtype != torch.float64:
-            raise TypeError("D must be float64 (what density() returns)")
-        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
-        H = None if H_packed is None else _packed(H_packed, st.P, "H_packed")
-        if int(plan.B) != st.B or int(plan.m_total) != st.M or int(plan.total) != st.P:
-            raise ValueError("the plan belongs to another batch")
-        mol_ptr = plan.mol_ptr.to(device=dev, dtype=torch.int32).contiguous()
-        atom_ptr = plan.orb_ptr.to(device=dev, dtype=torch.int64).contiguous()
-        N = int(plan.N)
-        if mol_ptr.numel() != st.B + 1 or atom_ptr.numel() != N + 1:
-            raise ValueError("the plan's mol_ptr / orb_ptr do not have B + 1 / N + 1 entries")
-        pop = torch.empty(N, dtype=torch.float64, device=dev)
-        nelec = torch.empty(st.B, dtype=torch.float64, device=dev)
-        eband = None if H is None else torch.empty(st.B, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().nq_orb_population(_lib.ptr(st.buf), *st._dims, _lib.ptr(Dp), _lib.ptr(H), int(H is not None and H.dtype == torch.float64),
-                                                     _lib.ptr(S), int(S is not None and S.dtype == torch.float64), N, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
-                                                     _lib.ptr(pop), _lib.ptr(nelec), _lib.ptr(eband), _lib.stream_ptr()))
-        return pop, nelec, eband
-
     # ---- the density response (csrc/orbresp.hip): thin launches; nabladft_amd.orbital_loss chains them -------------------------------------------------------
     def occupied_layout(self, n_occ):
         """The occupied-packed layout of the response's scratch arrays -> ``(n_occ int32 [B], occ_ptr int64 [B+1], O)``, the first two on the device:
@@ -376,43 +555,35 @@ class BatchedOrbitals:
         occ = np.concatenate([[0], np.cumsum(no.astype(np.int64) * st.m)]).astype(np.int64)
         return torch.from_numpy(no).to(st.buf.device), torch.from_numpy(occ).to(st.buf.device), int(occ[-1])
 
-    def _resp(self, name, layout, ins, outs):
-        st = self.state
-        no, occ, O = layout
-        with torch.cuda.device(st.buf.device):
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(st.buf), *st._dims, _lib.ptr(no), _lib.ptr(occ), O, *[_lib.ptr(t) for t in ins + outs], _lib.stream_ptr()))
-        return outs
-
-    def _f64(self, t: torch.Tensor, n: int, name: str) -> torch.Tensor:
-        dev = self.state.buf.device
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.numel() != n or t.device != dev:
-            raise ValueError(f"{name} must be float64 [{n}] on {dev}")
-        return t.detach().reshape(-1).contiguous()
-
-    def _scratch(self, n: int, make: bool = True):
-        return torch.empty(n, dtype=torch.float64, device=self.state.buf.device) if make else None
-
     def resp_project(self, G: torch.Tensor, layout) -> torch.Tensor:
         """``T = Gs C_o`` with ``Gs = (G + G^T) / 2`` (``nq_orb_resp_project``): ``G`` packed float64 [P], any matrix -> occupied-packed [m][n_occ], float64 [O]."""
         P = self.state.P
-        return self._resp("nq_orb_resp_project", layout, [self._f64(G, P, "G")], [self._scratch(P), self._scratch(layout[2])])[1]
+        Gs, T = self._scratch(P), self._scratch(layout[2])
+        self.state.call("nq_orb_resp_project", *_ptrs(layout[:2]), layout[2], *_ptrs([self._f64(G, P, "G"), Gs, T]))
+        return T
 
     def resp_mo(self, T: torch.Tensor, layout, overlap: bool = True):
         """``W = C^T T`` divided by the occupied-virtual differences (``nq_orb_resp_mo``) -> ``(A_H, A_S or None)``, occupied-packed [m][n_occ]."""
         O = layout[2]
-        return tuple(self._resp("nq_orb_resp_mo", layout, [self._f64(T, O, "T")], [self._scratch(O), self._scratch(O, overlap)]))
+        outs = self._scratch(O), self._scratch(O, overlap)
+        self.state.call("nq_orb_resp_mo", *_ptrs(layout[:2]), O, *_ptrs((self._f64(T, O, "T"),) + outs))
+        return outs
 
     def resp_back(self, A_H: torch.Tensor, A_S: Optional[torch.Tensor], layout):
         """``Rt_X = A_X^T C^T`` (``nq_orb_resp_back``) -> ``(Rt_H, Rt_S or None)``, occupied-packed [n_occ][m]; both from the same loads of the coefficients."""
         O = layout[2]
-        ins = [self._f64(A_H, O, "A_H"), None if A_S is None else self._f64(A_S, O, "A_S")]
-        return tuple(self._resp("nq_orb_resp_back", layout, ins, [self._scratch(O), self._scratch(O, A_S is not None)]))
+        ins = self._f64(A_H, O, "A_H"), None if A_S is None else self._f64(A_S, O, "A_S")
+        outs = self._scratch(O), self._scratch(O, A_S is not None)
+        self.state.call("nq_orb_resp_back", *_ptrs(layout[:2]), O, *_ptrs(ins + outs))
+        return outs
 
     def syr2k(self, Rt0: torch.Tensor, Rt1: Optional[torch.Tensor], layout):
         """``X = 1/2 sum_{i < n_occ} (r_i c_i^T + c_i r_i^T)`` (``nq_orb_syr2k``) -> ``(X0, X1 or None)``, packed float64 [P], exactly symmetric."""
         O, P = layout[2], self.state.P
-        ins = [self._f64(Rt0, O, "Rt0"), None if Rt1 is None else self._f64(Rt1, O, "Rt1")]
-        return tuple(self._resp("nq_orb_syr2k", layout, ins, [self._scratch(P), self._scratch(P, Rt1 is not None)]))
+        ins = self._f64(Rt0, O, "Rt0"), None if Rt1 is None else self._f64(Rt1, O, "Rt1")
+        outs = self._scratch(P), self._scratch(P, Rt1 is not None)
+        self.state.call("nq_orb_syr2k", *_ptrs(layout[:2]), O, *_ptrs(ins + outs))
+        return outs
 
     def density_response(self, G: torch.Tensor, n_occ_or_layout, overlap: bool = True):
         """``dL/dH`` and (``overlap``) ``dL/dS`` of a loss with ``dL/dD = G`` on the density ``density(n_occ)`` of the last solve: the four launches above ->
@@ -443,9 +614,7 @@ class BatchedOrbitals:
         mu, ent = self._scratch(st.B), self._scratch(st.B)
         occ, docc = self._scratch(st.M), self._scratch(st.M)
         info = torch.empty(st.B, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().nq_orb_fermi(_lib.ptr(st.buf), *st._dims, _lib.ptr(ne), _lib.ptr(kt), _lib.ptr(mu), _lib.ptr(occ), _lib.ptr(docc), _lib.ptr(ent),
-                                                _lib.ptr(info), _lib.stream_ptr()))
+        st.call("nq_orb_fermi", _lib.ptr(ne), _lib.ptr(kt), _lib.ptr(mu), _lib.ptr(occ), _lib.ptr(docc), _lib.ptr(ent), _lib.ptr(info))
         self._fermi_info = info
         return FermiResult(mu, occ, docc, ent, info, ne, kt)
 
@@ -462,17 +631,12 @@ class BatchedOrbitals:
             self._full = (torch.from_numpy(st.m.astype(np.int32)).to(st.buf.device), st.pack_ptr, st.P)
         return self._full
 
-    def _smear(self, name, args):
-        st = self.state
-        with torch.cuda.device(st.buf.device):
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(st.buf), *st._dims, *[_lib.ptr(t) for t in args], _lib.stream_ptr()))
-
     def smear_mo(self, T: torch.Tensor, fermi_result: FermiResult, overlap: bool = True):
         """``W = C^T T`` times the divided differences of F (``nq_orb_smear_mo``) -> ``(A_H, A_S or None, wdiag)``: packed [m][m] without their diagonals, which
         ``smear_diag`` writes, and ``wdiag`` [M] = ``W_kk``."""
         st = self.state
         out = [self._scratch(st.P), self._scratch(st.P, overlap), self._scratch(st.M)]
-        self._smear("nq_orb_smear_mo", [fermi_result.mu, fermi_result.kT, self._f64(T, st.P, "T")] + out)
+        st.call("nq_orb_smear_mo", *_ptrs([fermi_result.mu, fermi_result.kT, self._f64(T, st.P, "T")] + out))
         return tuple(out)
 
     def smear_diag(self, A_H: torch.Tensor, A_S: Optional[torch.Tensor], wdiag: torch.Tensor, fermi_result: FermiResult, g_eps=None, g_occ=None, g_mu=None, g_ent=None):
@@ -480,15 +644,15 @@ class BatchedOrbitals:
         ``entropy`` [B] (each may be None) -> ``(A_H, A_S)``."""
         st, fr = self.state, fermi_result
         gs = [None if g is None else self._f64(g, n, name) for g, n, name in ((g_eps, st.M, "g_eps"), (g_occ, st.M, "g_occ"), (g_mu, st.B, "g_mu"), (g_ent, st.B, "g_ent"))]
-        self._smear("nq_orb_smear_diag", [fr.mu, fr.kT, fr.occ, fr.docc, self._f64(wdiag, st.M, "wdiag")] + gs +
-                    [self._f64(A_H, st.P, "A_H"), None if A_S is None else self._f64(A_S, st.P, "A_S")])
+        st.call("nq_orb_smear_diag", *_ptrs([fr.mu, fr.kT, fr.occ, fr.docc, self._f64(wdiag, st.M, "wdiag")] + gs +
+                                            [self._f64(A_H, st.P, "A_H"), None if A_S is None else self._f64(A_S, st.P, "A_S")]))
         return A_H, A_S
 
     def smear_back(self, A_H: torch.Tensor, A_S: Optional[torch.Tensor]):
         """``Rt_X = A_X^T C^T`` over all orbitals (``nq_orb_smear_back``) -> ``(Rt_H, Rt_S or None)``, packed [m][m]; both from the same loads of the coefficients."""
         P = self.state.P
         out = [self._scratch(P), self._scratch(P, A_S is not None)]
-        self._smear("nq_orb_smear_back", [self._f64(A_H, P, "A_H"), None if A_S is None else self._f64(A_S, P, "A_S")] + out)
+        self.state.call("nq_orb_smear_back", *_ptrs([self._f64(A_H, P, "A_H"), None if A_S is None else self._f64(A_S, P, "A_S")] + out))
         return tuple(out)
 
     def smeared_response(self, G: Optional[torch.Tensor], fermi_result: FermiResult, g_eps=None, g_occ=None, g_mu=None, g_ent=None, overlap: bool = True):
@@ -513,104 +677,7 @@ class BatchedOrbitals:
         self.smear_diag(A_H, A_S, wdiag, fermi_result, g_eps, g_occ, g_mu, g_ent)
         return self.syr2k(*self.smear_back(A_H, A_S), layout)
 
-    def populations_backward(self, plan, g_pop, g_nelec, g_eband, D=None, S_packed=None, H_packed=None, want_s: bool = False, want_h: bool = False):
-        """The reverse of ``populations`` (``nq_orb_population_backward``): upstream gradients (float64, each may be None) -> ``(gD, gS or None, gH or None)``,
-        packed float64 [P], with respect to symmetric ``D``, ``S`` and ``H``."""
-        st, dev = self.state, self.state.buf.device
-        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
-        H = None if H_packed is None else _packed(H_packed, st.P, "H_packed")
-        Dp = None if D is None else self._f64(D, st.P, "D")
-        N = int(plan.N)
-        gs = [None if g is None else self._f64(g, n, name) for g, n, name in ((g_pop, N, "g_pop"), (g_nelec, st.B, "g_nelec"), (g_eband, st.B, "g_eband"))]
-        mol_ptr = plan.mol_ptr.to(device=dev, dtype=torch.int32).contiguous()
-        atom_ptr = plan.orb_ptr.to(device=dev, dtype=torch.int64).contiguous()
-        if int(plan.B) != st.B or int(plan.m_total) != st.M or int(plan.total) != st.P or mol_ptr.numel() != st.B + 1 or atom_ptr.numel() != N + 1:
-            raise ValueError("the plan belongs to another batch")
-        outs = [self._scratch(st.P), self._scratch(st.P, want_s), self._scratch(st.P, want_h)]
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().nq_orb_population_backward(_lib.ptr(st.buf), *st._dims, *[_lib.ptr(g) for g in gs], _lib.ptr(Dp), _lib.ptr(H),
-                                                              int(H is not None and H.dtype == torch.float64), _lib.ptr(S),
-                                                              int(S is not None and S.dtype == torch.float64), N, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
-                                                              *[_lib.ptr(o) for o in outs], _lib.stream_ptr()))
-        return tuple(outs)
-
-    # ---- bond orders (csrc/orbbond.hip) ------------------------------------------------------------------------------------------------------------------------
-    def _bond_tables(self, plan):
-        """``(N, Q, mol_ptr int32, atom_orb_ptr int64, bond_ptr int64)`` of a plan, the three tables on the device; one small device -> host copy of ``mol_ptr``,
-        remembered per plan."""
-        st, dev = self.state, self.state.buf.device
-        cached = getattr(self, "_bond_cache", None)
-        if cached is not None and cached[0] is plan:
-            return cached[1]
-        if int(plan.B) != st.B or int(plan.m_total) != st.M or int(plan.total) != st.P:
-            raise ValueError("the plan belongs to another batch")
-        N = int(plan.N)
-        mp = _host_ptr(plan.mol_ptr)
-        if mp.shape[0] != st.B + 1 or plan.orb_ptr.numel() != N + 1 or int(mp[0]) != 0 or int(mp[-1]) != N:
-            raise ValueError("the plan's mol_ptr / orb_ptr do not have B + 1 / N + 1 entries")
-        bp = bond_layout(mp)
-        out = (N, int(bp[-1]), plan.mol_ptr.to(device=dev, dtype=torch.int32).contiguous(), plan.orb_ptr.to(device=dev, dtype=torch.int64).contiguous(),
-               torch.from_numpy(bp).to(dev))
-        self._bond_cache = (plan, out)
-        return out
-
-    def bond_product(self, D: torch.Tensor, S_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``P = D S`` per molecule (``nq_orb_bond_product``), packed float64 [P], not symmetric; only the lower triangles of ``D`` and ``S`` are read.
-        ``S_packed = None``: ``D`` made symmetric from its lower triangle."""
-        st = self.state
-        Dp = self._f64(D, st.P, "D")
-        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
-        out = self._scratch(st.P)
-        with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_bond_product(_lib.ptr(st.buf), *st._dims, _lib.ptr(Dp), _lib.ptr(S), int(S is not None and S.dtype == torch.float64),
-                                                       _lib.ptr(out), _lib.stream_ptr()))
-        return out
-
-    def bond_reduce(self, Pm: torch.Tensor, plan, valence: bool = True):
-        """``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` and (``valence``) ``V_A = sum_{B != A} B_AB`` (``nq_orb_bond_reduce``) -> ``(bond [Q], valence [N] or
-        None)``, float64 on the device; ``bond`` is exactly symmetric inside each molecule's ``[n, n]`` block (``bond_layout``)."""
-        st, dev = self.state, self.state.buf.device
-        N, Q, mol_ptr, atom_ptr, bond_ptr = self._bond_tables(plan)
-        bond = self._scratch(Q)
-        val = torch.empty(N, dtype=torch.float64, device=dev) if valence else None
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().nq_orb_bond_reduce(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(Pm, st.P, "P")), N, Q, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
-                                                      _lib.ptr(bond_ptr), _lib.ptr(bond), _lib.ptr(val), _lib.stream_ptr()))
-        return bond, val
-
-    def bond_orders(self, D: torch.Tensor, plan, S_packed: Optional[torch.Tensor] = None):
-        """Mayer bond orders and valences of a packed closed-shell density ``D`` (float64 [P], carrying the factor 2: what ``density()`` returns) ->
-        ``(bond [Q], valence [N], P [P])``, float64 on the device: ``P = D S``, ``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` (``B_AA`` included; molecule b's
-        table is ``dense_bond_orders(bond, plan.mol_ptr, b)``), ``V_A = sum_{B != A} B_AB``.  ``plan``: the ``BlockAssembler`` / ``IrrepsAssembler`` plan of the batch
-        (its ``mol_ptr`` and per-atom ``orb_ptr``).  ``S_packed = None``: the Wiberg index of an orthogonal basis.  An atom with more than 32 orbitals gets NaN
-        in its row and column, a molecule the solver failed on NaN in all its entries.  Two launches (three with the valences); nothing is read back."""
-        Pm = self.bond_product(D, S_packed)
-        bond, val = self.bond_reduce(Pm, plan)
-        return bond, val, Pm
-
-    def bond_orders_backward(self, plan, g_bond, g_valence, Pm: torch.Tensor, D=None, S_packed=None, want_d: bool = True, want_s: bool = False, return_e: bool = False):
-        """The reverse of ``bond_orders`` (``nq_orb_bond_backward``): upstream gradients ``g_bond`` [Q] and ``g_valence`` [N] (float64, each may be None) and the
-        ``P`` of the forward -> ``(gD or None, gS or None)``, packed float64 [P], exactly symmetric, with respect to symmetric ``D`` and ``S``:
-        ``sym(E S)`` and ``sym(D E)`` with ``E_mu,nu = (Gamma_AB + Gamma_BA) P_nu,mu``, ``Gamma_AB = g_bond_AB + (A != B) g_valence_A``.  ``want_s`` needs ``D`` and
-        ``S_packed``.  ``return_e``: ``E`` as a third member (for tests)."""
-        st, dev = self.state, self.state.buf.device
-        N, Q, mol_ptr, atom_ptr, bond_ptr = self._bond_tables(plan)
-        if not (want_d or want_s):
-            raise ValueError("bond_orders_backward: neither gradient is asked for")
-        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
-        if want_s and (S is None or D is None):
-            raise ValueError("bond_orders_backward: the gradient of S needs S_packed and D")
-        Dp = self._f64(D, st.P, "D") if want_s else None
-        gb = None if g_bond is None else self._f64(g_bond, Q, "g_bond")
-        gv = None if g_valence is None else self._f64(g_valence, N, "g_valence")
-        E, gD, gS = self._scratch(st.P), self._scratch(st.P, want_d), self._scratch(st.P, want_s)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().nq_orb_bond_backward(_lib.ptr(st.buf), *st._dims, _lib.ptr(gb), _lib.ptr(gv), _lib.ptr(self._f64(Pm, st.P, "P")), _lib.ptr(Dp),
-                                                        _lib.ptr(S), int(S is not None and S.dtype == torch.float64), N, Q, _lib.ptr(mol_ptr), _lib.ptr(atom_ptr),
-                                                        _lib.ptr(bond_ptr), _lib.ptr(E), _lib.ptr(gD), _lib.ptr(gS), _lib.stream_ptr()))
-        return (gD, gS, E) if return_e else (gD, gS)
-
-    # ---- Löwdin analysis (csrc/orblowdin.hip) ------------------------------------------------------------------------------------------------------------------
+    # ---- Löwdin analysis (csrc/orblowdin.hip): what reads the levels of S; the congruences are _LayoutLaunches' --------------------------------------------------
     def overlap_weights(self):
         """After a STANDARD solve of ``S`` itself (``solve(S_packed)``: ``energies`` = the levels ``s`` of ``S``): ``a = sqrt(s)`` and ``1 / a`` float64 [M],
         ``cond = s_max / s_min`` float64 [B] and ``info`` int32 [B] (``nq_orb_low_weights``) -> ``(w_half, w_inv_half, cond, info)`` on the device.  A molecule
@@ -619,8 +686,7 @@ class BatchedOrbitals:
         half, inv = self._scratch(st.M), self._scratch(st.M)
         cond = self._scratch(st.B)
         info = torch.empty(st.B, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().nq_orb_low_weights(_lib.ptr(st.buf), *st._dims, _lib.ptr(half), _lib.ptr(inv), _lib.ptr(cond), _lib.ptr(info), _lib.stream_ptr()))
+        st.call("nq_orb_low_weights", _lib.ptr(half), _lib.ptr(inv), _lib.ptr(cond), _lib.ptr(info))
         return half, inv, cond, info
 
     def overlap_functions(self):
@@ -630,63 +696,13 @@ class BatchedOrbitals:
         half, inv = self.weighted_gram(w_half, w_inv)
         return half, inv, cond, info
 
-    def low_product(self, Msym: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
-        """``Y = M X`` per molecule (``nq_orb_low_product``), packed float64 [P], not symmetric: ``Msym`` float32 or float64 [P] and ``X`` float64 [P] are
-        symmetric and only their lower triangles are read."""
-        st = self.state
-        Mp = _packed(Msym, st.P, "M")
-        out = self._scratch(st.P)
-        with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_low_product(_lib.ptr(st.buf), *st._dims, _lib.ptr(Mp), int(Mp.dtype == torch.float64), _lib.ptr(self._f64(X, st.P, "X")),
-                                                      _lib.ptr(out), _lib.stream_ptr()))
-        return out
-
-    def low_symprod(self, E: torch.Tensor, X: torch.Tensor, side: int, alpha: float = 1.0) -> torch.Tensor:
-        """``alpha sym(X E)`` (``side`` 0) or ``alpha sym(E X)`` (``side`` 1) per molecule (``nq_orb_low_symprod``), packed float64 [P], exactly symmetric: ``E``
-        any matrix, ``X`` symmetric, its lower triangle read."""
-        st = self.state
-        if side not in (0, 1):
-            raise ValueError(f"low_symprod: side must be 0 (sym(X E)) or 1 (sym(E X)), not {side!r}")
-        out = self._scratch(st.P)
-        with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_low_symprod(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(E, st.P, "E")), _lib.ptr(self._f64(X, st.P, "X")), int(side),
-                                                      float(alpha), _lib.ptr(out), _lib.stream_ptr()))
-        return out
-
-    def low_symmetrize(self, G: torch.Tensor) -> torch.Tensor:
-        """``(G + G^T) / 2`` per molecule (``nq_orb_low_symmetrize``), packed float64 [P], exactly symmetric: one elementwise launch on the device."""
-        st = self.state
-        out = self._scratch(st.P)
-        with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_low_symmetrize(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(G, st.P, "G")), _lib.ptr(out), _lib.stream_ptr()))
-        return out
-
-    def sym_congruence(self, X: torch.Tensor, Msym: torch.Tensor):
-        """``M^L = X M X`` for symmetric ``X`` (``S^(1/2)`` or ``S^(-1/2)``) and symmetric ``M`` (``D`` or ``H``, float32 or float64) -> ``(M_L, Y)``: ``Y = M X``
-        is kept for the reverse, ``M_L = sym(X Y)`` is exactly symmetric.  Two launches."""
-        Y = self.low_product(Msym, X)
-        return self.low_symprod(Y, X, 0), Y
-
-    def sym_congruence_backward(self, G: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, want_m: bool = True, want_x: bool = True, symmetric: bool = True):
-        """The reverse of ``sym_congruence`` for an upstream ``G = dL/dM^L`` -> ``(dL/dM or None, dL/dX or None)``: ``sym(X (G X))`` (two launches) and
-        ``Y G + G Y^T = 2 sym(Y G)`` (one), packed float64 [P], exactly symmetric.  ``symmetric=True`` (the default): ``G`` is symmetric and its lower triangle
-        is read; ``False``: any matrix, made symmetric first by one ``nq_orb_low_symmetrize`` launch."""
-        if not (want_m or want_x):
-            raise ValueError("sym_congruence_backward: neither gradient is asked for")
-        if not symmetric:
-            G = self.low_symmetrize(G)
-        gM = self.low_symprod(self.low_product(G, X), X, 0) if want_m else None
-        gX = self.low_symprod(Y, G, 1, 2.0) if want_x else None
-        return gM, gX
-
     def low_mo(self, T: torch.Tensor, kind: int) -> torch.Tensor:
         """``K o (U^T T)``, the diagonal included (``nq_orb_low_mo``), packed float64 [P]; ``kind`` 0: ``K_ij = 1 / (a_i + a_j)``, 1: ``-1 / (a_i a_j (a_i + a_j))``."""
         st = self.state
         if kind not in (0, 1):
             raise ValueError(f"low_mo: kind must be 0 (S^(1/2)) or 1 (S^(-1/2)), not {kind!r}")
         out = self._scratch(st.P)
-        with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_low_mo(_lib.ptr(st.buf), *st._dims, int(kind), _lib.ptr(self._f64(T, st.P, "T")), _lib.ptr(out), _lib.stream_ptr()))
+        st.call("nq_orb_low_mo", int(kind), _lib.ptr(self._f64(T, st.P, "T")), _lib.ptr(out))
         return out
 
     def matfun_response(self, g: torch.Tensor, kind: int) -> torch.Tensor:
@@ -698,45 +714,12 @@ class BatchedOrbitals:
         A = self.low_mo(self.resp_project(g, layout), kind)
         return self.syr2k(self.smear_back(A, None)[0], None, layout)[0]
 
-    # ---- SCF residual (csrc/orbcomm.hip) -------------------------------------------------------------------------------------------------------------------------
-    def commutator(self, X: torch.Tensor, Y: torch.Tensor, x_anti: bool = False, alpha: float = 1.0) -> torch.Tensor:
-        """``alpha (X Y - Y X)`` per molecule (``nq_orb_comm_product``), packed float64 [P].  ``Y`` is symmetric, its lower triangle is read.  ``x_anti=False``:
-        ``X`` symmetric (lower triangle read), the result exactly antisymmetric with a ``+0.0`` diagonal; ``x_anti=True``: ``X`` antisymmetric (strict lower
-        triangle read, the mirrored element is the negated one, the stored diagonal is ignored), the result exactly symmetric.  Only the layout of the state
-        is read: no solve is needed."""
-        st = self.state
-        out = self._scratch(st.P)
-        with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_comm_product(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(X, st.P, "X")), int(bool(x_anti)),
-                                                       _lib.ptr(self._f64(Y, st.P, "Y")), float(alpha), _lib.ptr(out), _lib.stream_ptr()))
-        return out
-
-    def antisymmetrize(self, G: torch.Tensor) -> torch.Tensor:
-        """``(G - G^T) / 2`` per molecule (``nq_orb_comm_antisymmetrize``), packed float64 [P], exactly antisymmetric with a ``+0.0`` diagonal."""
-        st = self.state
-        out = self._scratch(st.P)
-        with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_comm_antisymmetrize(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(G, st.P, "G")), _lib.ptr(out), _lib.stream_ptr()))
-        return out
-
-    def commutator_norms(self, R: torch.Tensor):
-        """``(sum_ij R_ij^2, max_ij |R_ij|)`` per molecule over the whole block (``nq_orb_comm_norms``), float64 [B] each on the device; the maximum of an SCF
-        residual is the DIIS error.  A molecule with ``status != 0`` or a NaN entry gets NaN in both."""
-        st = self.state
-        sumsq, maxabs = self._scratch(st.B), self._scratch(st.B)
-        with torch.cuda.device(st.buf.device):
-            _lib.check(_lib.load().nq_orb_comm_norms(_lib.ptr(st.buf), *st._dims, _lib.ptr(self._f64(R, st.P, "R")), _lib.ptr(sumsq), _lib.ptr(maxabs),
-                                                     _lib.stream_ptr()))
-        return sumsq, maxabs
-
     def check(self) -> "BatchedOrbitals":
         st = self.state
-        st.header()
-        status = st.status.cpu().numpy()
-        bad = np.nonzero(status)[0]
-        if bad.size:
-            b = int(bad[0])
-            raise RuntimeError(_failure_text(b, int(status[b]), int(st.info[b]), int(st.m[b])))
+        bad = st.first_failure()
+        if bad:
+            b, status = bad
+            raise RuntimeError(_failure_text(b, status, int(st.info[b]), int(st.m[b])))
         info = getattr(self, "_fermi_info", None)
         if info is not None:
             bad = np.nonzero(info.cpu().numpy())[0]
@@ -828,10 +811,6 @@ class BatchedMatrixRoot:
     iterations = property(lambda self: self.state.iters)
     orb_ptr = property(lambda self: self.state.orb_ptr_host)
     pack_ptr = property(lambda self: self.state.pack_ptr_host)
-    def _launch(self, name, *args):
-        st = self.state
-        with torch.cuda.device(st.buf.device):
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(st.buf), *st._dims, *args, _lib.stream_ptr()))
 
     @property
     def residuals(self) -> torch.Tensor:
@@ -860,13 +839,13 @@ class BatchedMatrixRoot:
         self.log = torch.empty(st.B, max_iter, dtype=torch.int32, device=dev)
         self.half = self.inv_half = None
         self._max_iter = max_iter
-        self._launch("nq_orb_sqrt_init", _lib.ptr(S), int(S.dtype == f64), max_iter, _lib.ptr(self.Y), _lib.ptr(self.Z), _lib.ptr(self.ctl), _lib.ptr(self.log))
+        self.state.call("nq_orb_sqrt_init", *_typed(S), max_iter, _lib.ptr(self.Y), _lib.ptr(self.Z), _lib.ptr(self.ctl), _lib.ptr(self.log))
         return self
 
     def step(self, k: int) -> "BatchedMatrixRoot":
         """Exactly one iteration, number ``k`` (``nq_orb_sqrt_step``; for tests: call them in order from 0)."""
         self._prepared()
-        self._launch("nq_orb_sqrt_step", int(k), self._max_iter, *self._iterates(), _lib.ptr(self.ctl), _lib.ptr(self.log))
+        self.state.call("nq_orb_sqrt_step", int(k), self._max_iter, *self._iterates(), _lib.ptr(self.ctl), _lib.ptr(self.log))
         return self
 
     def finish(self) -> "BatchedMatrixRoot":
@@ -874,13 +853,13 @@ class BatchedMatrixRoot:
         self._prepared()
         st = self.state
         self.half, self.inv_half = (torch.empty(st.P, dtype=torch.float64, device=st.buf.device) for _ in range(2))
-        self._launch("nq_orb_sqrt_finish", self._max_iter, _lib.ptr(self.Y), _lib.ptr(self.Z), _lib.ptr(self.Y2), _lib.ptr(self.Z2), _lib.ptr(self.ctl),
+        self.state.call("nq_orb_sqrt_finish", self._max_iter, _lib.ptr(self.Y), _lib.ptr(self.Z), _lib.ptr(self.Y2), _lib.ptr(self.Z2), _lib.ptr(self.ctl),
                      _lib.ptr(self.log), _lib.ptr(self.half), _lib.ptr(self.inv_half))
         return self
 
     def run(self, S_packed: torch.Tensor, max_iter: int = 100) -> "BatchedMatrixRoot":
         self.prepare(S_packed, max_iter)
-        self._launch("nq_orb_sqrt_run", self._max_iter, *self._iterates(), _lib.ptr(self.ctl), _lib.ptr(self.log))
+        self.state.call("nq_orb_sqrt_run", self._max_iter, *self._iterates(), _lib.ptr(self.ctl), _lib.ptr(self.log))
         self.finish()
         self.Y = self.Z = self.T = self.Y2 = self.Z2 = None            # five [P] arrays nobody needs after the final scaling
         return self
@@ -888,18 +867,16 @@ class BatchedMatrixRoot:
     def check(self) -> "BatchedMatrixRoot":
         self._prepared()
         st = self.state
-        st.header()
-        status = st.status.cpu().numpy()
-        bad = np.nonzero(status)[0]
-        if bad.size:
-            b = int(bad[0])
-            if status[b] == 1:
+        bad = st.first_failure()
+        if bad:
+            b, status = bad
+            if status == 1:
                 raise RuntimeError(f"molecule {b}: the overlap matrix is not positive definite (its largest absolute row sum is zero or not finite): no "
                                    "S^(1/2) (status 1)")
-            if status[b] == 4:
+            if status == 4:
                 raise RuntimeError(f"molecule {b}: the Newton-Schulz iteration did not converge in {self._max_iter} iterations: the overlap matrix is not "
                                    "positive definite, or its condition number is beyond about 1e8 (status 4)")
-            raise RuntimeError(_failure_text(b, int(status[b]), int(st.info[b]), int(st.m[b])))
+            raise RuntimeError(_failure_text(b, status, int(st.info[b]), int(st.m[b])))
         return self
 
 
@@ -916,7 +893,7 @@ Orthogonalizer.__doc__ = """What ``BatchedPurification.orthogonalize`` returns, 
 1-based Cholesky pivot; that molecule's block of ``Z`` is NaN) and the host ``orb_ptr`` it was built for."""
 
 
-class BatchedPurification:
+class BatchedPurification(_LayoutLaunches):
     """Closed-shell density matrices of every molecule of a batch and their gradients WITHOUT a solve (csrc/orbpurify.hip).
 
     ``BatchedPurification(orb_ptr)`` as ``BatchedOrbitals``.  ``orthogonalize(S_packed)`` -> ``Orthogonalizer`` (one latency-bound launch; the object is
@@ -947,28 +924,6 @@ class BatchedPurification:
     orb_ptr = property(lambda self: self.state.orb_ptr_host)
     pack_ptr = property(lambda self: self.state.pack_ptr_host)
     projector = property(lambda self: self.state.coeff)            # X [P]
-    _f64 = BatchedOrbitals._f64
-    _scratch = BatchedOrbitals._scratch
-    populations = BatchedOrbitals.populations
-    populations_backward = BatchedOrbitals.populations_backward
-    _bond_tables = BatchedOrbitals._bond_tables
-    bond_product = BatchedOrbitals.bond_product
-    bond_reduce = BatchedOrbitals.bond_reduce
-    bond_orders = BatchedOrbitals.bond_orders
-    bond_orders_backward = BatchedOrbitals.bond_orders_backward
-    low_product = BatchedOrbitals.low_product                     # the layout-only launches of csrc/orblowdin.hip
-    low_symprod = BatchedOrbitals.low_symprod
-    low_symmetrize = BatchedOrbitals.low_symmetrize
-    sym_congruence = BatchedOrbitals.sym_congruence
-    sym_congruence_backward = BatchedOrbitals.sym_congruence_backward
-    commutator = BatchedOrbitals.commutator                       # the layout-only launches of csrc/orbcomm.hip
-    antisymmetrize = BatchedOrbitals.antisymmetrize
-    commutator_norms = BatchedOrbitals.commutator_norms
-
-    def _call(self, name, *args):
-        st = self.state
-        with torch.cuda.device(st.buf.device):
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(st.buf), *st._dims, *args, _lib.stream_ptr()))
 
     def orthogonalize(self, S_packed: torch.Tensor) -> Orthogonalizer:
         st = self.state
@@ -976,7 +931,7 @@ class BatchedPurification:
         if S.device != st.buf.device:
             raise ValueError(f"the matrices must live on {st.buf.device}")
         Z = self._scratch(st.P)
-        self._call("nq_orb_pur_orthogonalizer", _lib.ptr(S), int(S.dtype == torch.float64), _lib.ptr(Z))
+        self.state.call("nq_orb_pur_orthogonalizer", *_typed(S), _lib.ptr(Z))
         self.orthogonalizer = Orthogonalizer(Z, st.status.clone(), st.info.clone(), st.orb_ptr_host)
         return self.orthogonalizer
 
@@ -987,7 +942,7 @@ class BatchedPurification:
         Ap = _packed(A, st.P, "A")
         out = self._scratch(st.P) if out is None else out
         tmp = None if Z is None else self._scratch(st.P)
-        self._call("nq_orb_pur_congruence", _lib.ptr(Z), int(bool(trans)), _lib.ptr(Ap), int(Ap.dtype == torch.float64), int(bool(symmetrize)), float(alpha),
+        self.state.call("nq_orb_pur_congruence", _lib.ptr(Z), int(bool(trans)), *_typed(Ap), int(bool(symmetrize)), float(alpha),
                    _lib.ptr(tmp), _lib.ptr(out))
         return out
 
@@ -995,7 +950,7 @@ class BatchedPurification:
         """``alpha A B + beta C`` per molecule (``nq_orb_pur_gemm``), packed float64 [P]."""
         P = self.state.P
         out = self._scratch(P)
-        self._call("nq_orb_pur_gemm", _lib.ptr(self._f64(A, P, "A")), _lib.ptr(self._f64(Bm, P, "B")), _lib.ptr(None if C is None else self._f64(C, P, "C")),
+        self.state.call("nq_orb_pur_gemm", _lib.ptr(self._f64(A, P, "A")), _lib.ptr(self._f64(Bm, P, "B")), _lib.ptr(None if C is None else self._f64(C, P, "C")),
                    float(alpha), float(beta), _lib.ptr(out))
         return out
 
@@ -1032,20 +987,20 @@ class BatchedPurification:
         self.ctl = torch.empty(st.B, 40 + max_iter, dtype=torch.float64, device=dev)
         self.log = torch.empty(st.B, max_iter, dtype=torch.int32, device=dev)
         if orth is None:
-            self._call("nq_orb_pur_init", _lib.ptr(H), int(H.dtype == torch.float64), None, _lib.ptr(no), max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
+            self.state.call("nq_orb_pur_init", *_typed(H), None, _lib.ptr(no), max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
         else:
             self.congruence(orth.Z, H, False, out=st.work)
-            self._call("nq_orb_pur_init", None, 1, _lib.ptr(orth.Z), _lib.ptr(no), max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
+            self.state.call("nq_orb_pur_init", None, 1, _lib.ptr(orth.Z), _lib.ptr(no), max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
         return self
 
     def step(self, k: int) -> "BatchedPurification":
         """Exactly one iteration, number ``k`` (``nq_orb_pur_step``; for tests: call them in order from 0)."""
-        self._call("nq_orb_pur_step", int(k), self._max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
+        self.state.call("nq_orb_pur_step", int(k), self._max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
         return self
 
     def purify(self, H_packed: torch.Tensor, n_occ, max_iter: int = 100, orthogonalizer: Optional[Orthogonalizer] = None) -> "BatchedPurification":
         self.prepare(H_packed, n_occ, max_iter, orthogonalizer)
-        self._call("nq_orb_pur_run", self._max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
+        self.state.call("nq_orb_pur_run", self._max_iter, _lib.ptr(self.ctl), _lib.ptr(self.log))
         return self
 
     def _purified(self):
@@ -1063,15 +1018,15 @@ class BatchedPurification:
         P = self.state.P
         Gt = self.congruence(None if self._orth is None else self._orth.Z, self._f64(G, P, "G"), False, 2.0, symmetrize=True)
         X1, Q = self._scratch(P), self._scratch(P)
-        self._call("nq_orb_pur_response_init", _lib.ptr(Gt), self._max_iter, _lib.ptr(self.ctl), _lib.ptr(X1))
+        self.state.call("nq_orb_pur_response_init", _lib.ptr(Gt), self._max_iter, _lib.ptr(self.ctl), _lib.ptr(X1))
         return Gt, X1, Q
 
     def response_step(self, k: int, X1: torch.Tensor, Q: torch.Tensor):
-        self._call("nq_orb_pur_response_step", int(k), self._max_iter, _lib.ptr(self.log), _lib.ptr(Q), _lib.ptr(X1))
+        self.state.call("nq_orb_pur_response_step", int(k), self._max_iter, _lib.ptr(self.log), _lib.ptr(Q), _lib.ptr(X1))
 
     def response(self, G: torch.Tensor, overlap: bool = True):
         Gt, X1, Q = self.response_start(G)
-        self._call("nq_orb_pur_response_run", self._max_iter, _lib.ptr(self.log), _lib.ptr(Q), _lib.ptr(X1))
+        self.state.call("nq_orb_pur_response_run", self._max_iter, _lib.ptr(self.log), _lib.ptr(Q), _lib.ptr(X1))
         st = self.state
         Z = None if self._orth is None else self._orth.Z
         gH = self.congruence(Z, X1, True)
@@ -1105,7 +1060,7 @@ class BatchedPurification:
         coef = torch.empty(2, st.M, dtype=torch.float64, device=dev)
         iters = torch.empty(st.B, 2, dtype=torch.int32, device=dev)
         conv = torch.empty(st.B, 2, dtype=torch.int32, device=dev)
-        self._call("nq_orb_front_lanczos", _lib.ptr(st.work), _lib.ptr(st.coeff), _lib.ptr(shift), _lib.ptr(self._n_occ), _lib.ptr(W), k_max, tol, _lib.ptr(V),
+        self.state.call("nq_orb_front_lanczos", _lib.ptr(st.work), _lib.ptr(st.coeff), _lib.ptr(shift), _lib.ptr(self._n_occ), _lib.ptr(W), k_max, tol, _lib.ptr(V),
                    _lib.ptr(vptr), _lib.ptr(eps), _lib.ptr(vec), _lib.ptr(coef), _lib.ptr(iters), _lib.ptr(res), _lib.ptr(conv))
         self._k_max = k_max
         return FrontierLevels(eps[:, 0], eps[:, 1], eps[:, 1] - eps[:, 0], coef, vec, iters, res, conv)
@@ -1121,7 +1076,7 @@ class BatchedPurification:
         eps = torch.stack((levels.homo, levels.lumo), 1).contiguous()
         gH = self._scratch(st.P)
         gS = self._scratch(st.P, bool(overlap))
-        self._call("nq_orb_front_gram", _lib.ptr(g), _lib.ptr(eps), _lib.ptr(self._f64(levels.coeff, 2 * st.M, "levels.coeff")), _lib.ptr(levels.converged),
+        self.state.call("nq_orb_front_gram", _lib.ptr(g), _lib.ptr(eps), _lib.ptr(self._f64(levels.coeff, 2 * st.M, "levels.coeff")), _lib.ptr(levels.converged),
                    _lib.ptr(gH), _lib.ptr(gS))
         return gH, gS
 
@@ -1138,17 +1093,15 @@ class BatchedPurification:
 
     def check(self) -> "BatchedPurification":
         st = self.state
-        st.header()
-        status = st.status.cpu().numpy()
-        bad = np.nonzero(status)[0]
-        if bad.size:
-            b = int(bad[0])
+        bad = st.first_failure()
+        if bad:
+            b, status = bad
             info = int(st.info[b])
-            if status[b] == 1 and self._orth is not None:
+            if status == 1 and self._orth is not None:
                 info = int(self._orth.info[b])
-            if status[b] == 4:
+            if status == 4:
                 info = int(self._max_iter)
-            raise RuntimeError(_failure_text(b, int(status[b]), info, int(st.m[b])))
+            raise RuntimeError(_failure_text(b, status, info, int(st.m[b])))
         return self
 
 

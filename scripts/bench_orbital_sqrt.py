@@ -146,7 +146,7 @@ def main():
 
     def init_and_loop():
         root.prepare(S, 100)
-        root._launch("nq_orb_sqrt_run", 100, *root._iterates(), _lib.ptr(root.ctl), _lib.ptr(root.log))
+        root.state.call("nq_orb_sqrt_run", 100, *root._iterates(), _lib.ptr(root.ctl), _lib.ptr(root.log))
     t_loop = leg("init_and_loop", init_and_loop, launches=201) - t_init
     leg("finish", lambda: root.finish(), launches=1)
     root.check()

@@ -1,41 +1,12 @@
 // Stand-alone host program (its own main, no Python, no device work): the host code that the entry points of csrc/orbbond.hip add -- argument checks, the
-// consistency of the bond table with the atom counts, the grid arithmetic -- run under the host sanitizers.  tests/test_orbbond_host_cpu.py builds and runs it:
+// consistency of the bond table with the atom counts, the grid arithmetic -- run under the host sanitizers.  tests/test_orb_host_cpu.py builds and runs it:
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         tests/host/orbbond_host_check.hip nabladft_amd/csrc/orbbond.hip -o orbbond_host_check && ./orbbond_host_check
 //
-// Every call below is refused by the argument checks before a stream or a kernel is touched, so the program needs no GPU.  The error and profiler hooks of
-// csrc/common.h, which engine.hip defines in the library, are defined here for this program alone.
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
-#include "../../nabladft_amd/csrc/orbstate.h"
-
-thread_local char nq_err_buf[512] = "";
-int nq_fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(nq_err_buf, sizeof(nq_err_buf), fmt, ap);
-  va_end(ap);
-  return code;
-}
-int nq_profile_on = 0;
-NqProfScope::NqProfScope(hipStream_t s, const char*) : st(s), slot(-1) {}
-NqProfScope::~NqProfScope() {}
-void NqProfScope::add_flops(double) {}
-
-static int failures = 0;
-#define EXPECT(cond)                                                          \
-  do {                                                                        \
-    if (!(cond)) {                                                            \
-      fprintf(stderr, "%s:%d: %s (last error: %s)\n", __FILE__, __LINE__, #cond, nq_err_buf); \
-      ++failures;                                                             \
-    }                                                                         \
-  } while (0)
-#define REFUSED(call, word) EXPECT((call) == NQ_ERR_ARG && strstr(nq_err_buf, word))
+// Every call below is refused by the argument checks before a stream or a kernel is touched, so the program needs no GPU.  The error and profiler hooks,
+// EXPECT / REFUSED and the final report are host_check.h's.
+#include "host_check.h"
 
 int main() {
   std::vector<double> host(320, 0.0);
@@ -100,10 +71,5 @@ int main() {
   REFUSED(nq_orb_bond_reduce(p, 1 << 25, 1 << 25, 1 << 25, q, 1 << 25, 1 << 25, ip, lq, lr, s, e, nullptr), "exceed the grid");
   EXPECT(orb_tile_rows(orb_largest_m_bound(Bbig, Mbig, Pbig)) == 16 && orb_tile_count(1024) == 136 && orb_tile_rows(orb_largest_m_bound(3, 10, 38)) == 1);
   for (double v : host) EXPECT(v == 0.0);
-  if (failures) {
-    fprintf(stderr, "orbbond_host_check: %d failure(s)\n", failures);
-    return 1;
-  }
-  printf("orbbond_host_check: ok\n");
-  return 0;
+  return host_check_report("orbbond_host_check");
 }

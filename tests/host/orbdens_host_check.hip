@@ -1,40 +1,12 @@
 // Stand-alone host program (its own main, no Python, no device work): the host code that nq_orb_wgram / nq_orb_population add -- argument checks, the state
-// layout, the tile arithmetic that sizes the grid -- run under the host sanitizers.  tests/test_orbdens_host_cpu.py builds and runs it:
+// layout, the tile arithmetic that sizes the grid -- run under the host sanitizers.  tests/test_orb_host_cpu.py builds and runs it:
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         tests/host/orbdens_host_check.hip nabladft_amd/csrc/orbdens.hip -o orbdens_host_check && ./orbdens_host_check
 //
-// Every call below is refused by the argument checks before a stream or a kernel is touched, so the program needs no GPU.  The error and profiler hooks of
-// csrc/common.h, which engine.hip defines in the library, are defined here for this program alone.
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
-#include "../../nabladft_amd/csrc/orbstate.h"
-
-thread_local char nq_err_buf[512] = "";
-int nq_fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(nq_err_buf, sizeof(nq_err_buf), fmt, ap);
-  va_end(ap);
-  return code;
-}
-int nq_profile_on = 0;
-NqProfScope::NqProfScope(hipStream_t s, const char*) : st(s), slot(-1) {}
-NqProfScope::~NqProfScope() {}
-void NqProfScope::add_flops(double) {}
-
-static int failures = 0;
-#define EXPECT(cond)                                                          \
-  do {                                                                        \
-    if (!(cond)) {                                                            \
-      fprintf(stderr, "%s:%d: %s (last error: %s)\n", __FILE__, __LINE__, #cond, nq_err_buf); \
-      ++failures;                                                             \
-    }                                                                         \
-  } while (0)
+// Every call below is refused by the argument checks before a stream or a kernel is touched, so the program needs no GPU.  The error and profiler hooks,
+// EXPECT / REFUSED and the final report are host_check.h's.
+#include "host_check.h"
 
 int main() {
   // ---- tiles: the decode inverts the enumeration for every tile a molecule of up to 1024 orbitals can have ----------------------------------------------
@@ -93,10 +65,5 @@ int main() {
   EXPECT(nq_orb_population(p, 2, 8, 34, p, nullptr, 0, nullptr, 0, 4, ip, lp, p, p, p, nullptr) == NQ_ERR_ARG && strstr(nq_err_buf, "needs H"));
   EXPECT(nq_orb_population(p, 2, 8, 34, p, nullptr, 0, nullptr, 0, 1, ip, lp, p, p, nullptr, nullptr) == NQ_ERR_ARG && strstr(nq_err_buf, "atoms"));
   for (double v : host) EXPECT(v == 0.0);
-  if (failures) {
-    fprintf(stderr, "orbdens_host_check: %d failure(s)\n", failures);
-    return 1;
-  }
-  printf("orbdens_host_check: ok\n");
-  return 0;
+  return host_check_report("orbdens_host_check");
 }

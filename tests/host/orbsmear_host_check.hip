@@ -5,39 +5,10 @@
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         tests/host/orbsmear_host_check.hip nabladft_amd/csrc/orbsmear.hip -o orbsmear_host_check && ./orbsmear_host_check
 //
-// Every call below is refused by the argument checks before a stream or a kernel is touched, so the program needs no GPU.  The error and profiler hooks of
-// csrc/common.h, which engine.hip defines in the library, are defined here for this program alone.
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
+// Every call below is refused by the argument checks before a stream or a kernel is touched, so the program needs no GPU.  The error and profiler hooks,
+// EXPECT / REFUSED and the final report are host_check.h's.
+#include "host_check.h"
 #include "../../nabladft_amd/csrc/orbsmear_math.h"
-#include "../../nabladft_amd/csrc/orbstate.h"
-
-thread_local char nq_err_buf[512] = "";
-int nq_fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(nq_err_buf, sizeof(nq_err_buf), fmt, ap);
-  va_end(ap);
-  return code;
-}
-int nq_profile_on = 0;
-NqProfScope::NqProfScope(hipStream_t s, const char*) : st(s), slot(-1) {}
-NqProfScope::~NqProfScope() {}
-void NqProfScope::add_flops(double) {}
-
-static int failures = 0;
-#define EXPECT(cond)                                                          \
-  do {                                                                        \
-    if (!(cond)) {                                                            \
-      fprintf(stderr, "%s:%d: %s (last error: %s)\n", __FILE__, __LINE__, #cond, nq_err_buf); \
-      ++failures;                                                             \
-    }                                                                         \
-  } while (0)
 
 int main() {
   // ---- the scalar functions on the grid: every pair of the base values, equal pairs among them, and every value against its neighbours one ulp away ----------
@@ -111,10 +82,5 @@ int main() {
   EXPECT(orb_tile_rows(orb_largest_m_bound(1, 1024, 1024LL * 1024)) == 16 && orb_tile_rows(orb_largest_m_bound(3, 10, 38)) == 1);
   EXPECT(orb_tile_rows(orb_largest_m_bound(2, 66, 65LL * 65 + 1)) == 2);
   for (double v : host) EXPECT(v == 0.0);
-  if (failures) {
-    fprintf(stderr, "orbsmear_host_check: %d failure(s)\n", failures);
-    return 1;
-  }
-  printf("orbsmear_host_check: ok\n");
-  return 0;
+  return host_check_report("orbsmear_host_check");
 }

@@ -424,7 +424,7 @@ def test_purified_frontier_gradients_against_torch_autograd(inputs):
 
 def test_nothing_is_launched_without_an_upstream_gradient_and_the_overlap_half_is_skipped(monkeypatch):
     import nabladft_amd as nq
-    from nabladft_amd.orbitals import BatchedPurification
+    from nabladft_amd.orbitals import BatchedPurification, OrbitalState
     r = autograd_reference("float64")[2]
     calls = []
     real = BatchedPurification.frontier_gradients
@@ -438,8 +438,8 @@ def test_nothing_is_launched_without_an_upstream_gradient_and_the_overlap_half_i
     assert calls == [(False, True, False)] and bool(torch.isfinite(Hd.grad).all())
     D, sol = nq.purified_density_matrix(Hd, Sd, op, [r["n"]], return_solution=True)
     runs = []
-    real_call = BatchedPurification._call
-    monkeypatch.setattr(BatchedPurification, "_call", lambda self, name, *a: (runs.append(name), real_call(self, name, *a))[1])
+    real_call = OrbitalState.call
+    monkeypatch.setattr(OrbitalState, "call", lambda self, name, *a: (runs.append(name), real_call(self, name, *a))[1])
     h2, l2 = nq.purified_frontier(Hd, Sd, op, [r["n"]], solution=sol)
     assert runs == ["nq_orb_front_lanczos"]                          # the shared solution is not purified again
     assert same_bits(h2.detach().cpu().numpy(), homo.detach().cpu().numpy()) and same_bits(l2.detach().cpu().numpy(), lumo.detach().cpu().numpy())
@@ -500,10 +500,10 @@ def test_qhnet_purified_frontier_task(monkeypatch):
     make = lambda cls, ls, cs: cls("QHNet", net, None, None, ls, None, None, cs)
     counts = dict(solve=0, orth=0)
     launches = []
-    real_solve, real_orth, real_call = OrbitalState.solve, BatchedPurification.orthogonalize, BatchedPurification._call
+    real_solve, real_orth, real_call = OrbitalState.solve, BatchedPurification.orthogonalize, OrbitalState.call
     monkeypatch.setattr(OrbitalState, "solve", lambda self, *a, **k: (counts.__setitem__("solve", counts["solve"] + 1), real_solve(self, *a, **k))[1])
     monkeypatch.setattr(BatchedPurification, "orthogonalize", lambda self, *a, **k: (counts.__setitem__("orth", counts["orth"] + 1), real_orth(self, *a, **k))[1])
-    monkeypatch.setattr(BatchedPurification, "_call", lambda self, name, *a: (launches.append(name), real_call(self, name, *a))[1])
+    monkeypatch.setattr(OrbitalState, "call", lambda self, name, *a: (launches.append(name), real_call(self, name, *a))[1])
     params = [p for p in net.parameters() if p.requires_grad]
 
     def step(task):

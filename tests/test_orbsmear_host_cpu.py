@@ -1,7 +1,7 @@
 """CPU: the host code behind the entry points of csrc/orbsmear.hip (argument checks, grid arithmetic) and the scalar functions of csrc/orbsmear_math.h under
 AddressSanitizer and UndefinedBehaviorSanitizer, and the accuracy of those functions.  A stand-alone program with its own ``main``
 (tests/host/orbsmear_host_check.hip) is compiled together with csrc/orbsmear.hip, the host side instrumented, and run as a child process: nothing is loaded
-into Python and no device is touched.  Sanitizer runs belong on hosts without a GPU: skipped where a device is visible, like tests/test_orbdens_host_cpu.py.
+into Python and no device is touched.  Sanitizer runs belong on hosts without a GPU: skipped where a device is visible, like tests/test_orb_host_cpu.py.
 
 The program checks finiteness, K_ij == K_ji, K <= 0 and K_kk == F' on the grid x_i, x_j in {0, +-1e-300, +-1e-9, +-1e-3, +-1, +-30, +-700, +-1e4, +-1e300}
 (all pairs, equal pairs, pairs one ulp apart; kT = 0.01 and 1) and prints the values; this file compares them with the same closed forms in ``np.longdouble``
