@@ -959,6 +959,30 @@ int nq_vib_eigh(void* state, int32_t N, int32_t B, int32_t D, int64_t P, int32_t
  *   NULL or aliased arrays, k_max, tol and impossible dimensions are refused on the host and touch nothing.  Plain float64 fma (memory-bound: no matrix-core
  *   instruction), no atomics, fixed summation orders: bitwise reproducible and independent of the rest of the batch; m = 1 .. 1024.  Only the layout and the
  *   status words of the state are read.
+ * Occupied levels without a full solve (csrc/orbocc.hip; entry points added, ABI 17 unchanged): ALL occupied orbital energies and coefficients from the
+ * projector X of a purification (state part `coeff`, kind "purification") and its orthogonalised Hamiltonian Ht (state part `work`).  An exact orthogonal
+ * projector of rank n_occ has a pivoted Cholesky factor X = Q^T Q whose n_occ rows are orthonormal, so Rayleigh-Ritz on Hs = Q Ht Q^T gives the occupied levels
+ * and C = V Q W their coefficients.  The stages, in order, with `occ` a second state of the batch as nq_orb_init left it (the results land in it) and `red` a
+ * third, of B molecules with max(n_occ_b, 1) orbitals each (Mr orbitals, Pr packed entries):
+ *   nq_orb_occ_factor(purification state): one workgroup per molecule, a left-looking pivoted Cholesky of X for exactly n_occ steps (n_occ int32 [B], clamped to
+ *     0..m); the pivot is the largest remaining diagonal entry, the first on ties.  Outputs: Q [P] (rows 0 .. n_occ - 1 of a molecule's block, the other rows
+ *     untouched; the entries of earlier pivots are exactly 0), pivots int32 [M] (-1 in the slots k >= n_occ), min_pivot [B] (+inf for n_occ = 0), defect [B]
+ *     (the largest |left-over diagonal entry|), status int32 [B]: the state's own word where that is not 0 (1, 4), 5 for a pivot < 1 / (2 m) or not finite or a
+ *     left-over diagonal entry >= 1 / (2 m) in magnitude (X is not a projector of rank n_occ: too few or too many pivots), else 0.  status != 0: NaN in the molecule's rows of Q, min_pivot and defect, -1 in its pivots; nothing else is touched.
+ *     A state that holds no purification: header status -3.
+ *   nq_orb_occ_reduce(occ, whose `coeff` is the Q of the factor): Hs = Q T for T = Ht Q^T, occupied-packed [m][n_occ] behind occ_ptr int64 [B+1] (O entries:
+ *     what nq_orb_resp_project(occ, ..., G = Ht, Gs, T) forms), into the reduced packed layout red_ptr int64 [B+1] (R = Pr entries): n_occ x n_occ, lower
+ *     triangle computed and mirrored (exactly symmetric); n_occ = 0: the 1 x 1 block [0]; status [B] (the factor's) != 0: a zero block.
+ *   nq_orb_solve(red, Hs, float64, S = NULL): the standard problem of the reduced blocks.
+ *   nq_orb_occ_back(occ, red): U [O] = V Q (V = the rows of red's `coeff`), C = U W for W_or_null [P] a general block, C[k][nu] = sum_mu U[k][mu] W[mu][nu] (the
+ *     lower-triangular Z of nq_orb_pur_orthogonalizer or a symmetric S^(-1/2) alike; NULL: C = U), the solver's sign rule (the largest-magnitude component of
+ *     every orbital positive, the first on ties); into occ: eps[k] = the reduced levels (ascending) and rows k of `coeff` for k < n_occ, NaN in every other
+ *     eps slot and coefficient row of the molecule, so that nq_orb_wgram with k_hi = n_occ and nq_orb_compare (its occupied figures) run on occ unchanged.
+ *     status int32 [B], in and out: the factor's word, else red's (2: the QL iteration of the reduced block did not converge) -- also written to occ's own
+ *     status words; != 0: NaN in all the molecule's eps slots and coefficient rows.  A state that holds a purification: header status -3.
+ *   NULL or aliased arrays, reduced dimensions that do not fit the batch and impossible dimensions are refused on the host and touch nothing.  float64; the
+ *   products on v_mfma_f64_16x16x4_f64, the factor in plain fma (memory-bound); no atomics, fixed summation orders: bitwise reproducible and independent of the
+ *   rest of the batch; m = 1 .. 1024, n_occ = 0 .. m.
  * Every call after nq_orb_init repeats the dimensions; on a mismatch the kernels do nothing and set the header status to -2. */
 size_t nq_orb_state_bytes(int32_t B, int32_t M, int64_t P);
 int nq_orb_state_layout(int32_t B, int32_t M, int64_t P, size_t* offsets_host);
@@ -1033,6 +1057,12 @@ int nq_orb_front_lanczos(void* state, int32_t B, int32_t M, int64_t P, const dou
                          double* res, int32_t* conv, void* stream);
 int nq_orb_front_gram(void* state, int32_t B, int32_t M, int64_t P, const double* g, const double* eps_or_null, const double* coef, const int32_t* conv, double* out_gH,
                       double* out_gS_or_null, void* stream);
+int nq_orb_occ_factor(void* state, int32_t B, int32_t M, int64_t P, const int32_t* n_occ, double* Q, int32_t* pivots, double* min_pivot, double* defect,
+                      int32_t* status, void* stream);
+int nq_orb_occ_reduce(void* state, int32_t B, int32_t M, int64_t P, const int32_t* n_occ, const int64_t* occ_ptr, int64_t O, const double* T, const int32_t* status,
+                      const int64_t* red_ptr, int64_t R, double* Hs, void* stream);
+int nq_orb_occ_back(void* state, void* reduced_state, int32_t B, int32_t M, int64_t P, int32_t Mr, int64_t Pr, const int32_t* n_occ, const int64_t* occ_ptr, int64_t O,
+                    const double* W_or_null, int32_t* status, double* U, void* stream);
 
 /* ---- Graphormer3D building blocks (csrc/graphormer.hip; reference nablaDFT/graphormer/graphormer_3d.py) --------------------------------------------------
  * Ragged layout: atoms [N] behind ptr int32[B+1] (atom_mol int32[N] = molecule of each atom); molecule b owns the n_b^2 ordered pairs (i, j), i = j included,

@@ -40,6 +40,9 @@ Public surface mirrors the reference plugin classes for this path:
   nabladft_amd.purified_frontier / FrontierLoss / FrontierLevels / QHNetPurifiedFrontierLightning <-> the same slots, for HOMO, LUMO and the gap alone: a
                                     projected Lanczos recurrence on what the SP2 purification leaves, and the levels' gradients, no solve (orbitals.py,
                                     orbital_loss.py; no reference code, tested against numpy, torch autograd and the solver route)
+  nabladft_amd.purified_occupied_energies / OccupiedEnergyLoss / OccupiedOrbitals / PurifiedOrbitalErrors / QHNetPurifiedOrbitalLightning <-> the same slots, for
+                                    ALL occupied levels and coefficients: a pivoted Cholesky factor of the purified projector and an n_occ x n_occ solve
+                                    (orbitals.py, orbital_loss.py; no reference code, tested against numpy, scipy, torch autograd and the solver route)
   nabladft_amd.spk.*            <-> the schnetpack classes config/model/{painn,schnet}.yaml instantiate (parity unpinned)
   nabladft_amd.read_energy_database / ArenaLoader <-> PyGNablaDFT.process + DataLoader collate (dataset/pyg_datasets.py:101-109)
 """
@@ -60,13 +63,14 @@ from .md import BatchedMD, PYGAseInterface  # noqa: F401
 from . import vibrations  # noqa: F401
 from .vibrations import BatchedVibrations  # noqa: F401
 from . import orbitals  # noqa: F401
-from .orbitals import BatchedOrbitals, BatchedPurification, FermiResult, OrbitalErrors, OrbitalState, electron_counts, mulliken_charges, occupied_counts, bond_layout, dense_bond_orders, LowdinBasis, BatchedMatrixRoot, ScfResidualErrors, FrontierLevels  # noqa: F401
+from .orbitals import BatchedOrbitals, BatchedPurification, FermiResult, OrbitalErrors, OrbitalState, electron_counts, mulliken_charges, occupied_counts, bond_layout, dense_bond_orders, LowdinBasis, BatchedMatrixRoot, ScfResidualErrors, FrontierLevels, OccupiedOrbitals, PurifiedOrbitalErrors  # noqa: F401
 from .orbital_loss import (DensityMatrixLoss, MullikenChargeLoss, OrbitalEnergyLoss, QHNetDensityLightning, QHNetOrbitalLightning,  # noqa: F401
                            QHNetSmearedDensityLightning, SmearedSolution, density_matrix, orbital_energies, orbital_solution, populations,
                            smeared_density_matrix, smeared_solution, purified_density_matrix, QHNetPurifiedDensityLightning, bond_orders, BondOrderLoss,
                            QHNetBondOrderLightning, lowdin_basis, lowdin_density, lowdin_hamiltonian, lowdin_populations, lowdin_charges, lowdin_bond_orders,
                            LowdinChargeLoss, QHNetLowdinLightning, commutator, scf_residual, scf_residual_to_target, ScfResidualLoss, ScfTarget, scf_target,
-                           scf_target_iterative, scf_target_blocks, QHNetCommutatorLightning, purified_frontier, FrontierLoss, QHNetPurifiedFrontierLightning)
+                           scf_target_iterative, scf_target_blocks, QHNetCommutatorLightning, purified_frontier, FrontierLoss, QHNetPurifiedFrontierLightning,
+                           purified_occupied_energies, OccupiedEnergyLoss, QHNetPurifiedOrbitalLightning)
 from .data import ArenaLoader, ConformerArena, HamiltonianBatch, HamiltonianDatabase, HamiltonianDataset, hamiltonian_batch, read_energy_database  # noqa: F401
 
 __all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "GemNetOCLightning", "eSCN", "eSCNLightning", "EquiformerV2_OC20", "EquiformerV2_OC20_Lightning", "Graphormer3D", "Graphormer3DLightning", "DimeNetPlusPlusPotential", "DimeNetPlusPlusLightning", "DimeNetPlusPlusForceLightning", "AtomisticTaskFixed", "ModelOutput", "L2Loss", "FusedTrainStep", "Batch", "build_neighbor_list", "NeighborList", "ArenaLoader", "ConformerArena",
@@ -74,4 +78,5 @@ __all__ = ["PaiNN", "PaiNNLightning", "QHNet", "QHNetLightning", "GemNetOC", "Ge
            "bond_layout", "dense_bond_orders", "LowdinBasis", "lowdin_basis", "lowdin_density", "lowdin_hamiltonian", "lowdin_populations", "lowdin_charges",
            "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning", "commutator", "scf_residual", "scf_residual_to_target", "ScfResidualLoss", "ScfTarget",
            "scf_target", "scf_target_iterative", "scf_target_blocks", "BatchedMatrixRoot", "QHNetCommutatorLightning", "ScfResidualErrors", "purified_frontier", "FrontierLoss",
-           "FrontierLevels", "QHNetPurifiedFrontierLightning"]
+           "FrontierLevels", "QHNetPurifiedFrontierLightning", "purified_occupied_energies", "OccupiedEnergyLoss", "QHNetPurifiedOrbitalLightning", "OccupiedOrbitals",
+           "PurifiedOrbitalErrors"]

@@ -267,6 +267,9 @@ SYMBOLS = {
     "nq_orb_sqrt_finish": (C.c_int, [_P, _I32, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nq_orb_front_lanczos": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _I32, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nq_orb_front_gram": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "nq_orb_occ_factor": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "nq_orb_occ_reduce": (C.c_int, [_P, _I32, _I32, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _P]),
+    "nq_orb_occ_back": (C.c_int, [_P, _P, _I32, _I32, _I64, _I32, _I64, _P, _P, _I64, _P, _P, _P, _P]),
     "nq_g3d_max_mol_atoms": (C.c_int32, []),
     "nq_g3d_pair_forward": (C.c_int, [_P] * 9 + [_I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "nq_g3d_pair_scratch_floats": (_SZ, [_I32, _I64, _I32]),

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libnablaq.so")
-SOURCES = ["graph.hip", "gemm.hip", "gemm_bf16.hip", "edge.hip", "molpair.hip", "updfuse.hip", "node.hip", "schnet.hip", "hblock.hip", "so3.hip", "qhnet.hip", "qhgen.hip", "gemnet_graph.hip", "gemnet.hip", "escn.hip", "equiformer.hip", "geobasis.hip", "graphormer.hip", "dimenet.hip", "lbfgs.hip", "md.hip", "vib.hip", "orbitals.hip", "orbdens.hip", "orbresp.hip", "orbsmear.hip", "orbpurify.hip", "orbbond.hip", "orblowdin.hip", "orbcomm.hip", "orbsqrt.hip", "orbfrontier.hip", "rccl.hip", "engine.hip"]
+SOURCES = ["graph.hip", "gemm.hip", "gemm_bf16.hip", "edge.hip", "molpair.hip", "updfuse.hip", "node.hip", "schnet.hip", "hblock.hip", "so3.hip", "qhnet.hip", "qhgen.hip", "gemnet_graph.hip", "gemnet.hip", "escn.hip", "equiformer.hip", "geobasis.hip", "graphormer.hip", "dimenet.hip", "lbfgs.hip", "md.hip", "vib.hip", "orbitals.hip", "orbdens.hip", "orbresp.hip", "orbsmear.hip", "orbpurify.hip", "orbbond.hip", "orblowdin.hip", "orbcomm.hip", "orbsqrt.hip", "orbfrontier.hip", "orbocc.hip", "rccl.hip", "engine.hip"]
 # molpair.hip: the SLP vectoriser packs neighbouring scalar f32 operations into v_pk_* beside the matrix instructions, which costs more than it saves there
 # (MI355X_MICROARCH.md, "packed f32 VALU beside MFMAs"; measured 6.51 -> 6.18 ms per step, profiles/r06_gwr_mol_variants.txt)
 # md.hip: no contraction of a * b + c, so that the float64 integrator rounds like the operation-by-operation restatement it is tested against (tests/md_ref.py)
@@ -35,7 +35,9 @@ SOURCES = ["graph.hip", "gemm.hip", "gemm_bf16.hip", "edge.hip", "molpair.hip", 
 # sides of the diagonal (it shares orbresp_tiles.h with orbpurify.hip)
 # orbfrontier.hip: the same, for the projected Lanczos recurrence of the frontier levels: its sums are written with fma(), and c_i c_j is one product on both
 # sides of the diagonal (it includes orbbond_tiles.h for the tiles' constants; its molecule lookup is orbstate.h's)
-EXTRA = {"molpair.hip": ["-fno-slp-vectorize"], "md.hip": ["-ffp-contract=off"], "vib.hip": ["-ffp-contract=off"], "orbitals.hip": ["-ffp-contract=off"], "orbdens.hip": ["-ffp-contract=off"], "orbresp.hip": ["-ffp-contract=off"], "orbsmear.hip": ["-ffp-contract=off"], "orbpurify.hip": ["-ffp-contract=off"], "orbbond.hip": ["-ffp-contract=off"], "orblowdin.hip": ["-ffp-contract=off"], "orbcomm.hip": ["-ffp-contract=off"], "orbsqrt.hip": ["-ffp-contract=off"], "orbfrontier.hip": ["-ffp-contract=off"]}
+# orbocc.hip: the same, for the projector's Cholesky factor and the occupied levels: its column sums are written with fma() in the order of the rows, and the
+# reduced matrix is the mirrored number on both sides of the diagonal (its products are rs_gemm of orbresp_tiles.h)
+EXTRA = {"molpair.hip": ["-fno-slp-vectorize"], "md.hip": ["-ffp-contract=off"], "vib.hip": ["-ffp-contract=off"], "orbitals.hip": ["-ffp-contract=off"], "orbdens.hip": ["-ffp-contract=off"], "orbresp.hip": ["-ffp-contract=off"], "orbsmear.hip": ["-ffp-contract=off"], "orbpurify.hip": ["-ffp-contract=off"], "orbbond.hip": ["-ffp-contract=off"], "orblowdin.hip": ["-ffp-contract=off"], "orbcomm.hip": ["-ffp-contract=off"], "orbsqrt.hip": ["-ffp-contract=off"], "orbfrontier.hip": ["-ffp-contract=off"], "orbocc.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=on", "-Wall", "-Wno-unused-function"]
 
 

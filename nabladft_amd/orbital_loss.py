@@ -60,8 +60,16 @@ semidefinite operators, which ``purified_frontier`` finds by a fully reorthogona
 side, tens to about two hundred matrix-vector steps, no ``m^3`` work).  With ``c = Z^T v`` the gradients are ``d eps / dH = c c^T`` and
 ``d eps / dS = -eps c c^T``, the convention of ``orbital_energies``: no eigenvector response.  ``FrontierLoss`` is the loss on them (``("mae", "both")`` equals
 ``OrbitalEnergyLoss("mae", "frontier")``), ``QHNetPurifiedFrontierLightning`` the task with the key ``"frontier"``; a purified density term of the same step
-shares the purification (``solution=``).  These two are the only orbital energies the purification route has.  Tested against ``np.linalg.eigh``,
+shares the purification (``solution=``).  These two are the only VIRTUAL-side information the purification route has; ``purified_occupied_energies`` (below) gives every occupied level.  Tested against ``np.linalg.eigh``,
 ``torch.linalg`` autograd and ``BatchedOrbitals.frontier`` (tests/orbital_frontier_ref.py).
+
+**All occupied levels without a full solve.**  An exact orthogonal projector of rank ``n_occ`` has a pivoted Cholesky factor ``X = Q^T Q`` whose rows are
+orthonormal (``X^2 = X`` forces ``Q Q^T = I``; every Schur complement is again a projector, so every pivot is at least ``1/m``): the occupied levels are the standard
+eigenvalues of the ``n_occ x n_occ`` matrix ``Q Ht Q^T`` and ``C = V Q Z`` their coefficients (csrc/orbocc.hip; the reduced blocks go through the batched solver).
+``purified_occupied_energies`` returns them with NaN in the virtual slots; the gradients are ``c_k c_k^T`` and ``-eps_k c_k c_k^T`` again, one ``nq_orb_wgram`` launch.
+``OccupiedEnergyLoss`` is ``OrbitalEnergyLoss(kind, "occupied")`` for such energies, ``QHNetPurifiedOrbitalLightning`` takes the key ``"occupied_energies"`` and shares
+the purification with the density, charge and frontier terms, ``PurifiedOrbitalErrors`` reports ``eps_mae_occ`` / ``similarity`` of a test loop.  Closed shells, an open
+gap, occupied levels only.  Tested against ``np.linalg.eigh``, ``scipy.linalg.eigh``, ``torch.linalg`` autograd and the solver route (tests/orbital_occupied_ref.py).
 
 **Bond orders.**  ``bond_orders`` gives the Mayer bond-order table and the atomic valences of a closed-shell density under ``S``: with ``P = D S``,
 ``B_AB = sum_{mu in A, nu in B} P_mu,nu P_nu,mu`` and ``V_A = sum_{B != A} B_AB`` (``S = None``: the Wiberg index of an orthogonal basis).  The reverse forms
@@ -109,7 +117,7 @@ from torch import nn
 
 from .lightning import QHNetLightning
 from .orbitals import (BatchedMatrixRoot, BatchedOrbitals, BatchedPurification, FrontierLevels, LowdinBasis, Orthogonalizer, _orb_ptr_of, _require_gpu, bond_layout, check_occupied, dense_bond_orders,  # noqa: F401
-                       ScfResidualErrors, electron_counts, mulliken_charges, occupied_counts)
+                       ScfResidualErrors, electron_counts, mulliken_charges, occupied_counts, OccupiedOrbitals, PurifiedOrbitalErrors)
 
 
 class _OrbitalEnergies(torch.autograd.Function):
@@ -1247,10 +1255,166 @@ class QHNetPurifiedFrontierLightning(QHNetPurifiedDensityLightning):
         return preds, targets, loss_args
 
 
+class _PurifiedOccupied(torch.autograd.Function):
+    """Forward: ``BatchedPurification.purify`` (unless the solution came purified) and ``occupied``.  Backward: ONE ``nq_orb_wgram`` launch on the occupied state
+    with ``w = g`` and ``w = -eps g`` over ``k < n_occ``; nothing is launched without an upstream gradient, and the ``S`` half is skipped when ``S`` asks for
+    nothing."""
+
+    @staticmethod
+    def forward(ctx, pur, H, S, n_occ, orth, max_iter, fresh):
+        if fresh:
+            pur.purify(H, n_occ, max_iter, orth)
+        occ = pur.occupied()
+        ctx.set_materialize_grads(False)
+        ctx.occ = occ
+        ctx.h = (H.shape, H.dtype)
+        ctx.s = None if S is None else (S.shape, S.dtype)
+        pur.occupied_orbitals = occ
+        return occ.energies.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        none = (None,) * 7
+        want_h = ctx.needs_input_grad[1]
+        want_s = ctx.s is not None and ctx.needs_input_grad[2]
+        if g is None or not (want_h or want_s):
+            return none
+        occ = ctx.occ
+        g = g.to(torch.float64).reshape(-1).contiguous()
+        if want_s:
+            gH, gS = occ.weighted_gram(g, -(occ.energies * g))
+            gS = gS.to(ctx.s[1]).view(ctx.s[0])
+        else:
+            gH, gS = occ.weighted_gram(g), None
+        return (None, gH.to(ctx.h[1]).view(ctx.h[0]) if want_h else None, gS) + none[3:]
+
+
+def purified_occupied_energies(H_packed: torch.Tensor, S_packed: Optional[torch.Tensor], plan_or_orb_ptr, n_occ, orthogonalizer: Optional[Orthogonalizer] = None,
+                               max_iter: int = 100, solution: Optional[BatchedPurification] = None, return_solution: bool = False):
+    """ALL occupied orbital energies of every molecule WITHOUT a full solve -> ``eps`` float64 [M] on the device, ascending in the slots ``k < n_occ`` of each
+    molecule and NaN in the others (``return_solution=True``: ``(eps, BatchedPurification)``; its ``occupied_orbitals`` attribute holds the
+    ``OccupiedOrbitals``), differentiable with respect to ``H_packed`` and ``S_packed``: SP2 purification, a pivoted Cholesky factor of the projector and the
+    ``n_occ x n_occ`` Rayleigh-Ritz problem (``BatchedPurification.occupied``).
+
+    Arguments as for ``purified_frontier``.  ``solution``: the ``BatchedPurification`` that ``purified_density_matrix(..., return_solution=True)`` already ran on the
+    SAME ``H_packed`` (and ``S_packed``) -- the prediction is then purified once per step.  The gradients need no eigenvector response: ``d eps_k / dH = c_k c_k^T``,
+    ``d eps_k / dS = -eps_k c_k c_k^T`` (the convention of ``orbital_energies``), one ``nq_orb_wgram`` launch over ``k < n_occ``, cast to the inputs' dtypes;
+    nothing is launched without an upstream gradient and the ``S`` half is skipped when ``S`` is None or requires no gradient.  The NaN slots take no gradient
+    (mask them with ``torch.where`` before reducing, as ``OccupiedEnergyLoss`` does).  A molecule whose purification failed (status 1 / 4) or whose projector is
+    not one (status 5) is NaN in all its slots and gives NaN gradient blocks for that molecule only (``solution.occupied_orbitals.check()`` reports it).  Needs
+    an open gap, like the purification it follows; closed shells, occupied levels only."""
+    _require_gpu(H_packed)
+    if S_packed is not None:
+        _require_gpu(S_packed)
+    elif orthogonalizer is not None:
+        raise ValueError("purified_occupied_energies: an orthogonalizer without S_packed")
+    fresh = solution is None
+    if fresh:
+        pur = BatchedPurification(plan_or_orb_ptr, H_packed.device)
+        if S_packed is not None and orthogonalizer is None:
+            orthogonalizer = pur.orthogonalize(S_packed)
+    else:
+        pur = solution
+        pur._purified()
+        if not np.array_equal(pur.orb_ptr, _orb_ptr_of(plan_or_orb_ptr)):
+            raise ValueError("purified_occupied_energies: the solution belongs to another batch")
+        if (pur._orth is None) != (S_packed is None):
+            raise ValueError("purified_occupied_energies: the solution was purified with an overlap and S_packed is None, or the reverse")
+    eps = _PurifiedOccupied.apply(pur, H_packed, S_packed, n_occ, orthogonalizer, max_iter, fresh)
+    return (eps, pur) if return_solution else eps
+
+
+class OccupiedEnergyLoss(nn.Module):
+    """``kind`` "mae" | "mse" of the occupied orbital energies: the mean over the ``n_occ`` occupied levels of each molecule, then the mean over the molecules --
+    ``OrbitalEnergyLoss(kind, "occupied")`` for energies whose virtual slots are NaN (what ``purified_occupied_energies`` / ``OccupiedOrbitals.energies`` give): the
+    slots ``k >= n_occ`` are masked with ``torch.where``, so they neither count nor take a gradient.  ``("mae")`` is the ``eps_mae_occ`` of ``OrbitalErrors`` /
+    ``PurifiedOrbitalErrors``.  ``charge`` is what the task counts the occupied orbitals with."""
+
+    packed = True
+
+    def __init__(self, kind: str = "mae", charge=0):
+        super().__init__()
+        if kind not in ("mae", "mse"):
+            raise ValueError(f"kind must be 'mae' or 'mse', not {kind!r}")
+        self.kind, self.charge = kind, charge
+
+    def occupied(self, z, ptr, orb_ptr=None) -> torch.Tensor:
+        return occupied_counts(z, ptr, self.charge, orb_ptr)
+
+    def forward(self, eps_pred: torch.Tensor, eps_target: torch.Tensor, n_occ, orb_ptr) -> torch.Tensor:
+        op = _orb_ptr_of(orb_ptr)
+        no = check_occupied(n_occ, op)
+        m = np.diff(op)
+        B, M = m.shape[0], int(op[-1])
+        if eps_pred.numel() != M or eps_target.numel() != M:
+            raise ValueError(f"the energies have {eps_pred.numel()} / {eps_target.numel()} entries, orb_ptr counts {M}")
+        k = np.arange(M) - np.repeat(op[:-1], m)
+        sel = k < np.repeat(no.astype(np.int64), m)
+        weight = torch.from_numpy(sel / np.repeat(no.astype(np.float64), m) / B).to(eps_pred.device)        # float64 [M]: mean over the occupied, then the molecules
+        d = eps_pred.reshape(-1).to(torch.float64) - eps_target.reshape(-1).to(torch.float64).detach()
+        d = torch.where(weight > 0, d, torch.zeros_like(d))          # a virtual slot is NaN: it neither counts nor takes a gradient
+        return torch.sum(weight * (d.abs() if self.kind == "mae" else d * d))
+
+
+class QHNetPurifiedOrbitalLightning(QHNetPurifiedFrontierLightning):
+    """``QHNetPurifiedFrontierLightning`` with a term on ALL occupied orbital energies, still without a full solve: ``losses`` / ``loss_coefs`` take
+    ``"occupied_energies"`` (an ``OccupiedEnergyLoss``).  Per step ONE orthogonalizer of ``batch.overlap`` and ONE purification of the prediction
+    (``nq_orb_pur_run``), shared with any active ``"density_matrix"`` / ``"mulliken_charges"`` / ``"frontier"`` term; the prediction's levels come from
+    ``purified_occupied_energies``, the target's from a detached ``purify().occupied()``; the only ``nq_orb_solve`` launches are those of the ``n_occ x n_occ``
+    blocks.  The parent's refusal of ``"orbital_energies"`` stays (no virtual levels).  With the ``"occupied_energies"`` coefficient at 0 (or without the key) the
+    step is the parent's."""
+
+    KEYS = QHNetPurifiedFrontierLightning.KEYS + ("occupied_energies",)
+
+    def _evaluate(self, batch):
+        active = self._active()
+        if "occupied_energies" not in active:
+            return super()._evaluate(batch)
+        if not self._packed():
+            raise ValueError("QHNetPurifiedOrbitalLightning needs packed losses (HamiltonianLoss, OccupiedEnergyLoss, FrontierLoss, DensityMatrixLoss, MullikenChargeLoss)")
+        if "orbital_energies" in active:
+            raise ValueError("QHNetPurifiedOrbitalLightning: purification has the occupied orbital energies only (\"occupied_energies\"); use QHNetDensityLightning "
+                             "for an \"orbital_energies\" term")
+        preds, targets, loss_args = QHNetLightning._evaluate(self, batch)
+        charges = [getattr(self.hparams.losses[k], "charge", 0) for k in active]
+        if any(not np.array_equal(np.asarray(c), np.asarray(charges[0])) for c in charges[1:]):
+            raise ValueError("the orbital losses count the occupied orbitals with different charges")
+        plan, asm = self.net.last_plan, self.net._asm
+        overlap = getattr(batch, "overlap", None)
+        S = None if overlap is None else asm.pack_targets(plan, overlap)
+        op = _orb_ptr_of(plan)
+        n_occ = occupied_counts(batch.z, batch.ptr, charges[0], op)
+        Hp, Ht = preds["hamiltonian"], targets["hamiltonian"]
+        pur_t = BatchedPurification(op, Hp.device)
+        orth = None if S is None else pur_t.orthogonalize(S)
+        pur_t.purify(Ht, n_occ, self.max_iter, orth)
+        eps_t = pur_t.occupied().energies
+        pur_p = None
+        if any(k in ("density_matrix", "mulliken_charges") for k in active):
+            D_t = pur_t.density()
+            D, pur_p = purified_density_matrix(Hp, S, op, n_occ, orth, self.max_iter, return_solution=True)
+        eps, pur_p = purified_occupied_energies(Hp, S, op, n_occ, orth, self.max_iter, solution=pur_p, return_solution=True)
+        for k in active:
+            if k == "occupied_energies":
+                preds[k], targets[k], preds[k + "_args"] = eps, eps_t, (n_occ, op)
+            elif k == "frontier":
+                lv_t = pur_t.frontier(self.k_max, self.tol)
+                homo, lumo = purified_frontier(Hp, S, op, n_occ, orth, self.max_iter, self.k_max, self.tol, solution=pur_p)
+                preds[k], targets[k], preds[k + "_args"] = torch.stack((homo, lumo)), torch.stack((lv_t.homo, lv_t.lumo)), (n_occ, op)
+            elif k == "density_matrix":
+                preds[k], targets[k], preds[k + "_args"] = D, D_t, (op,)
+            else:
+                preds[k] = mulliken_charges(batch.z, populations(D, plan, S, None, pur_p)[0])
+                targets[k] = mulliken_charges(batch.z, pur_t.populations(D_t, plan, S)[0])
+                preds[k + "_args"] = (batch.ptr,)
+        return preds, targets, loss_args
+
+
 __all__ = ["orbital_energies", "OrbitalEnergyLoss", "QHNetOrbitalLightning", "mulliken_charges", "orbital_solution", "density_matrix", "populations",
            "DensityMatrixLoss", "MullikenChargeLoss", "QHNetDensityLightning", "electron_counts", "SmearedSolution", "smeared_solution", "smeared_density_matrix",
            "QHNetSmearedDensityLightning", "purified_density_matrix", "QHNetPurifiedDensityLightning", "bond_orders", "BondOrderLoss", "QHNetBondOrderLightning",
            "bond_layout", "dense_bond_orders", "LowdinBasis", "lowdin_basis", "lowdin_density", "lowdin_hamiltonian", "lowdin_populations", "lowdin_charges",
            "lowdin_bond_orders", "LowdinChargeLoss", "QHNetLowdinLightning", "commutator", "scf_residual", "scf_residual_to_target", "ScfResidualLoss", "ScfTarget",
            "scf_target", "scf_target_iterative", "scf_target_blocks", "BatchedMatrixRoot", "QHNetCommutatorLightning", "ScfResidualErrors", "purified_frontier", "FrontierLoss",
-           "QHNetPurifiedFrontierLightning", "FrontierLevels"]
+           "QHNetPurifiedFrontierLightning", "FrontierLevels", "purified_occupied_energies", "OccupiedEnergyLoss", "QHNetPurifiedOrbitalLightning",
+           "OccupiedOrbitals", "PurifiedOrbitalErrors"]

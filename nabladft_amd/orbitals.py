@@ -47,7 +47,11 @@ gradient chain over all orbital pairs, evaluated without dividing by a differenc
 (``nabladft_amd.orbital_loss.purified_density_matrix`` is the differentiable call).  Closed shells only, needs an open gap, no smearing, no orbital energies
 other than HOMO and LUMO: ``frontier()`` gives those two from ``X``, ``Ht`` and the bounds by a projected Lanczos recurrence (csrc/orbfrontier.hip; one
 workgroup per molecule and side, no ``m^3`` work), ``frontier_gradients`` their gradients ``c c^T`` and ``-eps c c^T``
-(``nabladft_amd.orbital_loss.purified_frontier`` is the differentiable call).
+(``nabladft_amd.orbital_loss.purified_frontier`` is the differentiable call).  ``occupied()`` gives ALL occupied levels and coefficients, still without a
+full solve (csrc/orbocc.hip): an exact projector of rank ``n_occ`` has a pivoted Cholesky factor ``X = Q^T Q`` with orthonormal rows, so Rayleigh-Ritz on the
+``n_occ x n_occ`` matrix ``Q Ht Q^T`` gives them (``OccupiedOrbitals``; ``nabladft_amd.orbital_loss.purified_occupied_energies`` is the differentiable call,
+``PurifiedOrbitalErrors`` accumulates the figures of a test loop).  Closed shells, an open gap, occupied levels only, 1..1024 orbitals; no virtual level
+other than the LUMO of ``frontier()``.
 
 Limits (each raises, nothing degrades silently): 1..``MAX_ORBITALS`` = 1024 orbitals per molecule; closed shells only in ``occupied_counts`` / ``density``
 (``occupied_counts`` refuses an odd electron count; the smeared calls take any count in (0, 2m)); MI355X only, no CPU path.
@@ -909,8 +913,9 @@ class BatchedPurification(_LayoutLaunches):
     ``frontier(k_max=256, tol=2**-44, transform=None)`` -> ``FrontierLevels``: HOMO, LUMO and the gap by a projected Lanczos recurrence (one launch,
     csrc/orbfrontier.hip); ``transform``: a packed float64 [P] back-transform in place of the orthogonaliser of the last purify (``S^(-1/2)`` after a purification of
     the standard problem in the Löwdin basis).  ``frontier_gradients(levels, g_homo, g_lumo, overlap=True)`` -> ``(dL/dH, dL/dS or None)``;
-    ``frontier_check(levels)`` raises naming the first molecule and side that did not converge in ``k_max`` steps.  No energies other than HOMO and LUMO, no
-    smearing, closed shells only."""
+    ``frontier_check(levels)`` raises naming the first molecule and side that did not converge in ``k_max`` steps.  ``occupied(transform=None)`` ->
+    ``OccupiedOrbitals``: all occupied levels and coefficients from a Cholesky factor of ``X`` and an ``n_occ x n_occ`` solve (csrc/orbocc.hip).  No virtual
+    level other than the LUMO, no smearing, closed shells only."""
 
     def __init__(self, orb_ptr, device="cuda"):
         self.state = OrbitalState(orb_ptr, device)
@@ -963,6 +968,7 @@ class BatchedPurification(_LayoutLaunches):
         if bad.size:
             b = int(bad[0])
             raise ValueError(f"molecule {b}: n_occ={int(no[b])} outside 0..m={int(st.m[b])}")
+        self._n_occ_host = no.astype(np.int64)                       # occupied() sizes its reduced layout by it without a read-back
         return torch.from_numpy(no).to(st.buf.device)
 
     def _orthogonalizer(self, orth):
@@ -1091,6 +1097,20 @@ class BatchedPurification(_LayoutLaunches):
                                f"(k_max={getattr(self, '_k_max', None)}, m={int(self.state.m[b])})")
         return self
 
+    def occupied(self, transform: Optional[torch.Tensor] = None) -> "OccupiedOrbitals":
+        """ALL occupied levels and coefficients of the last ``purify`` WITHOUT a full solve (csrc/orbocc.hip) -> ``OccupiedOrbitals``: a pivoted Cholesky factor
+        ``X = Q^T Q`` of the projector (``nq_orb_occ_factor``), ``Hs = Q Ht Q^T`` (``nq_orb_resp_project`` for ``Ht Q^T``, ``nq_orb_occ_reduce``), the standard
+        problem of the ``n_occ x n_occ`` blocks (``nq_orb_solve`` on a reduced state) and ``C = V Q W`` with the solver's sign rule (``nq_orb_occ_back``), on the
+        current stream; nothing is read back.  ``transform``: a packed float64 [P] back-transform ``W`` in place of the orthogonaliser of the last purify, as in
+        ``frontier``."""
+        self._purified()
+        st = self.state
+        if transform is None:
+            W = None if self._orth is None else self._orth.Z
+        else:
+            W = self._f64(transform, st.P, "transform")
+        return OccupiedOrbitals(self, W)
+
     def check(self) -> "BatchedPurification":
         st = self.state
         bad = st.first_failure()
@@ -1103,6 +1123,149 @@ class BatchedPurification(_LayoutLaunches):
                 info = int(self._max_iter)
             raise RuntimeError(_failure_text(b, status, info, int(st.m[b])))
         return self
+
+
+OCCUPIED_FIGURES = ("eps_mae_occ", "similarity", "similarity_min", "homo_abs_err")
+
+
+class OccupiedOrbitals:
+    """What ``BatchedPurification.occupied`` returns, all on the device: ``energies`` float64 [M] (ascending in the slots ``k < n_occ`` of each molecule, NaN in
+    the others), ``coefficients`` packed float64 [P] (row k of a block = occupied orbital k, ``c^T S c = 1``, the solver's sign rule; NaN rows for ``k >= n_occ``),
+    ``n_occ`` int32 [B], ``pivots`` int32 [M] (the Cholesky pivots, -1 for ``k >= n_occ``), ``min_pivot`` / ``defect`` float64 [B] (the smallest pivot, >= 1/m
+    for an exact projector; the largest left-over diagonal entry) and ``status`` int32 [B]: 0, the purification's own 1 / 4, 5 where the projector is not a
+    projector of rank ``n_occ`` (a pivot below 1/(2m), or a left-over diagonal entry above it), 2 where the QL iteration of the reduced block did not converge; a molecule with a non-zero status has
+    NaN in its own slots only.  ``weighted_gram(w0, w1=None)`` -> ``sum_{k < n_occ} w[k] c_k c_k^T`` (one ``nq_orb_wgram`` launch); ``density()`` ->
+    ``2 sum_{k < n_occ} c_k c_k^T``, the ``BatchedPurification.density()`` to rounding; ``compare(target, S_packed)`` -> float64 [4, B], the rows of
+    ``OCCUPIED_FIGURES``: the occupied-energy MAE, the mean and the minimum of ``|c_k^T S c'_k|`` over the occupied k and ``|Delta HOMO|`` against another
+    ``OccupiedOrbitals`` of the batch (the occupied rows of ``nq_orb_compare``, which never reads a virtual slot for them; NaN where ``n_occ = 0``);
+    ``check()`` reads the status once (a host synchronisation) and raises naming the molecule.  Occupied levels only: no ``frontier``, no response chain, no
+    smearing.  The inputs are detached (``nabladft_amd.orbital_loss.purified_occupied_energies`` is the differentiable call)."""
+
+    def __init__(self, pur: "BatchedPurification", W: Optional[torch.Tensor]):
+        ps, dev = pur.state, pur.state.buf.device
+        no_host = self.n_occ_host = pur._n_occ_host
+        self.n_occ = pur._n_occ
+        self._max_iter, self._orth = pur._max_iter, pur._orth
+        B, M, P = ps.B, ps.M, ps.P
+        st = self.state = OrbitalState(ps.orb_ptr_host, dev)
+        occ_host = np.concatenate([[0], np.cumsum(no_host * ps.m)]).astype(np.int64)
+        rows = np.maximum(no_host, 1)
+        red = self.reduced = OrbitalState(np.concatenate([[0], np.cumsum(rows)]).astype(np.int64), dev)
+        self._layout = (self.n_occ, torch.from_numpy(occ_host).to(dev), int(occ_host[-1]))
+        O = self._layout[2]
+        f64, i32 = torch.float64, torch.int32
+        self.pivots = torch.empty(M, dtype=i32, device=dev)
+        self.min_pivot, self.defect = torch.empty(B, dtype=f64, device=dev), torch.empty(B, dtype=f64, device=dev)
+        self.status = torch.empty(B, dtype=i32, device=dev)
+        ps.call("nq_orb_occ_factor", _lib.ptr(self.n_occ), _lib.ptr(st.coeff), _lib.ptr(self.pivots), _lib.ptr(self.min_pivot), _lib.ptr(self.defect),
+                _lib.ptr(self.status))
+        Gs, T = torch.empty(P, dtype=f64, device=dev), torch.empty(max(O, 1), dtype=f64, device=dev)
+        st.call("nq_orb_resp_project", *_ptrs(self._layout[:2]), O, _lib.ptr(ps.work), _lib.ptr(Gs), _lib.ptr(T))
+        Hs = torch.empty(red.P, dtype=f64, device=dev)
+        st.call("nq_orb_occ_reduce", *_ptrs(self._layout[:2]), O, _lib.ptr(T), _lib.ptr(self.status), _lib.ptr(red.pack_ptr), red.P, _lib.ptr(Hs))
+        red.solve(Hs)
+        with torch.cuda.device(dev):
+            # two states in front of the dimensions, like nq_orb_compare
+            _lib.check(_lib.load().nq_orb_occ_back(_lib.ptr(st.buf), _lib.ptr(red.buf), *st._dims, red.M, red.P, *_ptrs(self._layout[:2]), O, _lib.ptr(W),
+                                                   _lib.ptr(self.status), _lib.ptr(T), _lib.stream_ptr()))
+        self._pur_header = ps.header_dev
+        self._orbitals = BatchedOrbitals.__new__(BatchedOrbitals)
+        self._orbitals.state = st
+
+    energies = property(lambda self: self.state.eps)
+    coefficients = property(lambda self: self.state.coeff)
+    orb_ptr = property(lambda self: self.state.orb_ptr_host)
+    pack_ptr = property(lambda self: self.state.pack_ptr_host)
+
+    def weighted_gram(self, w0: torch.Tensor, w1: Optional[torch.Tensor] = None):
+        return self._orbitals.weighted_gram(w0, w1, None, self.n_occ)
+
+    def density(self) -> torch.Tensor:
+        st = self.state
+        return self.weighted_gram(torch.full((st.M,), 2.0, dtype=torch.float64, device=st.buf.device))
+
+    def compare(self, target: "OccupiedOrbitals", S_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if not isinstance(target, OccupiedOrbitals):
+            raise TypeError(f"compare: target must be an OccupiedOrbitals, not {type(target).__name__}")
+        st, tt = self.state, target.state
+        if st._dims != tt._dims or not np.array_equal(st.orb_ptr_host, tt.orb_ptr_host) or not np.array_equal(self.n_occ_host, target.n_occ_host):
+            raise ValueError("the two solutions belong to different batches")
+        S = None if S_packed is None else _packed(S_packed, st.P, "S_packed")
+        out = torch.empty(len(FIGURES), st.B, dtype=torch.float64, device=st.buf.device)
+        with torch.cuda.device(st.buf.device):
+            _lib.check(_lib.load().nq_orb_compare(_lib.ptr(st.buf), _lib.ptr(tt.buf), *st._dims, *_typed(S), _lib.ptr(self.n_occ), _lib.ptr(out), _lib.stream_ptr()))
+        return out[[FIGURES.index(k) for k in ("eps_mae_occ", "psi_sim_occ", "psi_sim_min_occ", "homo_abs_err")]]
+
+    def check(self) -> "OccupiedOrbitals":
+        st = self.state
+        st.header()
+        self.reduced.header()
+        if int(self._pur_header[4]) == -3:
+            raise RuntimeError("occupied(): the state does not hold a purification")
+        status = self.status.cpu().numpy()
+        bad = np.nonzero(status)[0]
+        if bad.size:
+            b, s = int(bad[0]), int(status[bad[0]])
+            if s == 5:
+                raise RuntimeError(f"molecule {b}: the purified matrix is not a projector of rank n_occ={int(self.n_occ_host[b])} (a Cholesky pivot below 1/(2m) or a left-over "
+                                   f"diagonal entry above it, m={int(st.m[b])}; status 5)")
+            info = int(self._max_iter) if s == 4 else (int(self._orth.info[b]) if s == 1 and self._orth is not None else 0)
+            raise RuntimeError(_failure_text(b, s, info, int(st.m[b])))
+        return self
+
+
+class PurifiedOrbitalErrors:
+    """The occupied-orbital figures of a test loop WITHOUT a full solve, accumulated over batches: the ``update(pred_packed, target_packed, overlap_packed,
+    plan_or_orb_ptr, z, ptr)`` / ``compute()`` contract of ``OrbitalErrors``.  ``update`` sends both Hamiltonians through ONE orthogonaliser of the common overlap
+    (``None``: the standard problem), two purifications and two ``occupied()`` calls and adds the four per-molecule figures of ``OCCUPIED_FIGURES``
+    (``eps_mae_occ``, ``similarity``, ``similarity_min``, ``homo_abs_err``: the ``eps_mae_occ``, ``psi_sim_occ``, ``psi_sim_min_occ`` and ``homo_abs_err`` of
+    ``FIGURES``) to running sums on the device; nothing is read back.  ``compute()`` first reads the status words kept of every batch and raises
+    ``RuntimeError`` naming the batch, the side and the molecule for a failure in ANY batch since the last ``reset()`` (status 1: the overlap, 4: no gap, 5:
+    not a projector, 2: the reduced QL iteration); otherwise -> dict of the means over all molecules seen.  ``max_iter`` caps the purification."""
+
+    def __init__(self, charge=0, max_iter: int = 100):
+        self.charge, self.max_iter = charge, int(max_iter)
+        self.reset()
+
+    def reset(self):
+        self._sum = None
+        self._count = None
+        self._flags = []          # per update: int32 [2, B] on the device = (predicted, target) status, the overlap's pivots, and m
+
+    def update(self, pred_packed, target_packed, overlap_packed, plan_or_orb_ptr, z, ptr):
+        _require_gpu(pred_packed)
+        op = _orb_ptr_of(plan_or_orb_ptr)
+        n_occ = check_occupied(occupied_counts(z, ptr, self.charge), op)
+        dev = pred_packed.device
+        pur_p, pur_t = BatchedPurification(op, dev), BatchedPurification(op, dev)
+        orth = None if overlap_packed is None else pur_p.orthogonalize(overlap_packed)
+        occ_p = pur_p.purify(pred_packed, n_occ, self.max_iter, orth).occupied()
+        occ_t = pur_t.purify(target_packed, n_occ, self.max_iter, orth).occupied()
+        figs = occ_p.compare(occ_t, overlap_packed)
+        ok = ~torch.isnan(figs)
+        if self._sum is None:
+            self._sum = torch.zeros(len(OCCUPIED_FIGURES), dtype=torch.float64, device=figs.device)
+            self._count = torch.zeros(len(OCCUPIED_FIGURES), dtype=torch.float64, device=figs.device)
+        self._sum += torch.where(ok, figs, torch.zeros_like(figs)).sum(1)
+        self._count += ok.sum(1).to(torch.float64)
+        info = torch.zeros_like(occ_p.status) if orth is None else orth.info
+        self._flags.append((torch.stack([occ_p.status, occ_t.status, info]), occ_p.state.m))
+        return self
+
+    def compute(self) -> dict:
+        if self._sum is None:
+            raise RuntimeError("PurifiedOrbitalErrors.compute() before any update()")
+        for i, (flags, m) in enumerate(self._flags):
+            flags = flags.cpu().numpy()
+            for side, name in enumerate(("predicted", "target")):
+                bad = np.nonzero(flags[side])[0]
+                if bad.size:
+                    b, s = int(bad[0]), int(flags[side, bad[0]])
+                    if s == 5:
+                        raise RuntimeError(f"batch {i}, {name} Hamiltonian, molecule {b}: the purified matrix is not a projector of rank n_occ (status 5)")
+                    raise RuntimeError(f"batch {i}, {name} Hamiltonian, " + _failure_text(b, s, self.max_iter if s == 4 else int(flags[2, b]), int(m[b])))
+        mean = (self._sum / self._count).cpu().tolist()
+        return dict(zip(OCCUPIED_FIGURES, mean))
 
 
 class OrbitalErrors:
@@ -1207,4 +1370,4 @@ def mulliken_charges(z, atom_pop: torch.Tensor) -> torch.Tensor:
     return zz.to(device=atom_pop.device, dtype=torch.float64).reshape(-1) - atom_pop.to(torch.float64)
 
 
-__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "FrontierLevels", "LowdinBasis", "BatchedMatrixRoot", "OrbitalState", "OrbitalErrors", "ScfResidualErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES"]
+__all__ = ["BatchedOrbitals", "BatchedPurification", "Orthogonalizer", "FrontierLevels", "LowdinBasis", "BatchedMatrixRoot", "OrbitalState", "OrbitalErrors", "ScfResidualErrors", "FermiResult", "occupied_counts", "electron_counts", "check_occupied", "mulliken_charges", "bond_layout", "dense_bond_orders", "MAX_ORBITALS", "MAX_ATOM_ORBITALS", "FIGURES", "OccupiedOrbitals", "PurifiedOrbitalErrors", "OCCUPIED_FIGURES"]
